@@ -376,7 +376,13 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="run the N>1 step (store + RCCL all-reduce) even at world size 1: exercises the multi-GPU "
                          "code path on a single-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step computed to DIR/counters.npy: the "
+                         "32 counters a caller of the step receives (N = 1: one pass's share of the accumulated counters; "
+                         "N > 1: the all-reduced counters), as float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "RANK" not in os.environ and (args.gpus > 1 or args.force_dist):
         sys.exit(spawn_ranks(max(1, args.gpus)))   # no launcher: start the ranks ourselves (before any GPU call)
@@ -745,6 +751,10 @@ def main():
         passes = 1 if multi else args.steps   # N = 1 accumulated `steps` identical passes
         assert not (got % np.uint64(passes)).any(), "accumulated counters are not a multiple of the step count"
         got = got // np.uint64(passes)
+        if args.dump_outputs:
+            # every count is far below 2^53: float64 holds it exactly
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "counters.npy"), got.astype(np.float64))
         parity = "not checked"
         if args.parity == "full":
             # checker: the oracle regenerates every rank's whole shard (counter-based generator) on all

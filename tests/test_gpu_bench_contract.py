@@ -29,8 +29,11 @@ def run_bench(*extra):
     return json.loads(lines[0])
 
 
-def test_single_gpu_line(hip):
-    d = run_bench()
+def test_single_gpu_line(hip, tmp_path):
+    import numpy as np
+
+    import oracle
+    d = run_bench("--dump-outputs", str(tmp_path))
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "parity"):
         assert k in d, k
@@ -53,6 +56,11 @@ def test_single_gpu_line(hip):
         assert a["cores"] == m["cores"] >= 1 and a["value"] > 0 and m["value"] > 0 and "contiguous shards" in m["sample"]
         assert m["min"] <= m["value"] <= m["max"]
     assert d["parity"].startswith("bit-exact")
+    # --dump-outputs: the last step's 32 counters (one pass over the default-seeded workload), exact in float64
+    dumped = np.load(str(tmp_path / "counters.npy"))
+    assert dumped.dtype == np.float64 and dumped.shape == (32,)
+    want = oracle.flagstat_generated(oracle.GEN_UNIFORM, 2026, 0xFFFF, 0, 2 ** 27)
+    assert np.array_equal(dumped, want.astype(np.float64)) and int(dumped[25]) == d["counters_fail_qc_reads"]
 
 
 def test_multi_gpu_step_at_world_size_one_self_spawned(hip):

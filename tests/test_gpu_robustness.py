@@ -142,31 +142,50 @@ def test_default_engine_callers_overlap(hip):
 
         for a, w in zip(arrays, wants):           # warm: engines, staging, pinned buffers
             assert np.array_equal(call(a), w)
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            call(arrays[0])
-        one = reps * n / (time.perf_counter() - t0)
-        results = [None] * 4
-        barrier = threading.Barrier(5)
 
-        def worker(t):
-            for _ in range(3):                    # untimed: every thread meets its side engine once
-                call(arrays[t])
-            barrier.wait()
+        def one_thread():
+            t0 = time.perf_counter()
             for _ in range(reps):
-                results[t] = call(arrays[t])
+                call(arrays[0])
+            return reps * n / (time.perf_counter() - t0)
 
-        threads = [threading.Thread(target=worker, args=(t,)) for t in range(4)]
-        for th in threads:
-            th.start()
-        barrier.wait()
-        t0 = time.perf_counter()
-        for th in threads:
-            th.join()
-        four = 4 * reps * n / (time.perf_counter() - t0)
-        for t in range(4):
-            assert np.array_equal(results[t], wants[t]), (n, t)
-        print("%d flags per call: one caller thread %.2f Gflags/s, four together %.2f Gflags/s (%.2fx)" % (n, one / 1e9, four / 1e9, four / one))
+        def four_threads():
+            results = [None] * 4
+            barrier = threading.Barrier(5)
+
+            def worker(t):
+                # untimed, all four together for a fixed time: the side engines are made on first need, and each one's second
+                # stream a few ms later by a helper thread, which holds a runtime lock for 8-20 ms -- none of that may fall
+                # into the timed window (a fixed number of calls here takes well under a millisecond)
+                t_end = time.perf_counter() + 0.3
+                call(arrays[t])
+                while time.perf_counter() < t_end:
+                    call(arrays[t])
+                barrier.wait()
+                for _ in range(reps):
+                    results[t] = call(arrays[t])
+
+            threads = [threading.Thread(target=worker, args=(t,)) for t in range(4)]
+            for th in threads:
+                th.start()
+            barrier.wait()
+            t0 = time.perf_counter()
+            for th in threads:
+                th.join()
+            rate = 4 * reps * n / (time.perf_counter() - t0)
+            for t in range(4):
+                assert np.array_equal(results[t], wants[t]), (n, t)
+            return rate
+
+        # the timed windows last 10-30 ms: a shared host's scheduler can stall any one of them, so both forms run three
+        # times, alternately, and the best of each is compared
+        ones, fours = [], []
+        for _ in range(3):
+            ones.append(one_thread())
+            fours.append(four_threads())
+        one, four = max(ones), max(fours)
+        print("%d flags per call: one caller thread %.2f Gflags/s, four together %.2f Gflags/s (%.2fx); rounds: one %s, four %s"
+              % (n, one / 1e9, four / 1e9, four / one, ["%.2f" % (x / 1e9) for x in ones], ["%.2f" % (x / 1e9) for x in fours]))
         return one, four
 
     one, four = measure(1 << 18, 300)
