@@ -75,6 +75,30 @@ int FLAGSTATS_u16_x64_superset(const uint16_t* array, uint64_t n, uint64_t* out)
 int FLAGSTATS_hip_device_u16_superset(const uint16_t* d_array, uint64_t n, uint64_t* d_out, void* stream); /* async */
 int FLAGSTATS_hip_device_u16_superset_sync(const uint16_t* d_array, uint64_t n, uint64_t* out);
 
+/* ================= segmented flagstat: one counter row per segment, many segments in one launch =================
+ * Segment i (i < nseg) is [offsets[i], offsets[i+1]) of the array (CSR offsets, nseg + 1 of them, uint64); its counters go to
+ * out[i * 32 + slot], every row with the slot contract above (and with the superset flag, slots 0 / 16 and slot 9 = the
+ * segment's length minus its slot 25, as the superset forms below).  Offsets must be non-decreasing with offsets[nseg] <= n;
+ * flags before offsets[0] or after offsets[nseg] are ignored; empty segments are allowed; nseg == 0 does nothing and succeeds.
+ * `flags`: bit 0 = store (out = counters: all 32 slots of every row written, never-written slots and empty segments as 0)
+ * instead of +=, bit 1 = superset.
+ * DEVICE offsets are not checked for order (that would need a synchronisation): every offset the kernel reads is clamped to
+ * [0, n] and a segment whose end lies before its begin is empty, so malformed device offsets never read outside the array or
+ * write outside d_out[nseg][32] -- only their counters are undefined.  The kernel reads d_offsets[0..nseg] only.
+ * HOST offsets are validated first: decreasing offsets, offsets[nseg] > n, NULL pointers with nseg > 0 and an nseg whose
+ * nseg * 256 bytes of device counters cannot be allocated fail (non-zero, message), and `out` is left untouched. */
+/* DEVICE array, DEVICE offsets[nseg+1] (uint64), DEVICE out[nseg][32] (uint64); asynchronous on `stream` (one kernel; the store
+ * form puts one memset in front of it).  The adds are atomic: launches on several streams may share d_out in the += form. */
+int FLAGSTATS_hip_device_u16_segments(const uint16_t* d_array, uint64_t n, const uint64_t* d_offsets, uint64_t nseg,
+                                      uint64_t* d_out, int flags, void* stream);
+/* DEVICE array, HOST offsets, HOST out[nseg][32]; synchronous */
+int FLAGSTATS_hip_device_u16_segments_sync(const uint16_t* d_array, uint64_t n, const uint64_t* offsets, uint64_t nseg,
+                                           uint64_t* out, int flags);
+/* HOST array, HOST offsets, HOST out[nseg][32]; synchronous.  Only [offsets[0], offsets[nseg]) crosses the bus, in the engine's
+ * chunks (knob "chunk_flags"); a segment that spans chunks is summed on the device. */
+int FLAGSTATS_hip_u16_x64_segments(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint64_t nseg,
+                                   uint64_t* out, int flags);
+
 /* 64-bit positional popcount in this library's convention: out[16] += bit counts (host array / device array) */
 int FLAGSTATS_hip_pospopcnt_u16_x64(const uint16_t* array, uint64_t n, uint64_t* out);
 int FLAGSTATS_hip_device_pospopcnt_u16(const uint16_t* d_array, uint64_t n, uint64_t* d_out, void* stream);

@@ -7,11 +7,21 @@ Only what the path needs:
 * ``pyflagstats``    mirror of the reference's Python entry point
                      (``python/libflagstats.pyx``): ``flagstats(values)``
 * ``device``         device-resident arrays, on-device input makers, torch interop
+* ``segments``       per-segment counters (CSR offsets) in one launch: host arrays,
+                     device pointers, torch tensors
 * ``dist``           shard + single all-reduce for multi-GPU runs
 
 The hot path has no CPU fallback: importing the compute entry points without the
 built extension raises.
 """
 from .pyflagstats import SAM_FLAG_NAMES, flagstats, flagstats_x64  # noqa: F401
+from .segments import (  # noqa: F401
+    count_segments_device_ptr,
+    count_segments_torch,
+    flagstats_segments,
+    offsets_from_lengths,
+    segment_dicts,
+)
 
-__all__ = ["flagstats", "flagstats_x64", "SAM_FLAG_NAMES"]
+__all__ = ["flagstats", "flagstats_x64", "SAM_FLAG_NAMES", "flagstats_segments", "offsets_from_lengths",
+           "count_segments_device_ptr", "count_segments_torch", "segment_dicts"]

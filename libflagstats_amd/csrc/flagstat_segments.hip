@@ -1,0 +1,687 @@
+// flagstat_segments.hip -- segmented flagstat: one row of 32 counters per CSR segment of a uint16 FLAG array, in one launch.
+//
+// Work split.  The flags are addressed on the 16-byte grid of the array's aligned-down base (as K1 does) and cut into units of
+// 4096 flags (8 KiB: 8 rows of 512 flags, one 16-byte vector per lane and row, so every load instruction of a wave covers 1 KiB
+// contiguously).  Every wave of the grid owns one contiguous run of units -- a writer -- and walks the segments that intersect
+// it: it finds the first one with a 64-ary search over the offsets (one load per lane and round), then walks forward through
+// a window of 64 offsets held one per lane.  Each wave counts into the bit-sliced lane state of K1 (flagstat_count_core.h) and,
+// whenever a segment ends or its range does, reduces the lane counters over the wave (DPP), maps the 21 totals to the 32 slots
+// and adds them to out[seg][32] with relaxed agent-scope atomics (K1's direct epilogue, per segment).  No workspace, no second
+// kernel.  A segment that lies entirely inside one writer's range is stored with plain stores in the store form (which zeroes
+// out[] in front, so empty segments and never-written slots read 0).
+//
+// Two regimes, chosen per stretch:
+//   * a run of at least `min_units` whole units inside one segment goes through K1's carry-save chain with K1's rolling load
+//     schedule (6 vectors in flight per lane), restated below from flagstat_kernels.hip; the chain is flushed (exact at any
+//     step count) when the segment ends;
+//   * every other unit -- a segment's ragged head and tail, and units dense with boundaries -- is loaded once (8 vectors in
+//     flight) and counted per flag: front4's bytes are popcounted into the lane counters, one piece of the unit per segment it
+//     holds (lanes and flags outside the piece read as zero, which counts nothing), and the wave reduction runs once per
+//     segment end, not per flag or per row.
+// The threshold is measured (tests/perf/segments_sweep.py).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <atomic>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <new>
+
+#include "../../include/libflagstats_hip.h"
+#include "flagstat_count_core.h"
+#include "flagstat_engine.h"
+#include "flagstat_segments.h"
+
+namespace fsk {
+
+constexpr int kSegDepth = 8;                       // chain depth as K1: epochs of 255 units
+constexpr int kSegRowVecs = 64;                    // vectors per row (one per lane)
+constexpr int kSegUnitVecs = kSegWaveFlags / 8;    // 512 vectors per unit
+
+// K1's step at the default schedule (flagstat_kernels.hip, STAGE 9 with non-temporal loads, each wave a contiguous 8 KiB):
+// vector u's registers are re-issued for vector u + 6 of the same unit (`cur`) or u - 2 of the next (`next`, if HAS_NEXT).
+template <bool HAS_NEXT>
+__device__ __forceinline__ void seg_step(Lane<kSegDepth>& s, uint4 (&v)[kUnroll], uint32_t blk, const uint4* __restrict__ cur,
+                                         const uint4* __restrict__ next)
+{
+    uint32_t t8a = 0, t8b = 0, f8a = 0, f8b = 0, s8a = 0, s8b = 0;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        uint32_t t4a = 0, t4b = 0, f4a = 0, f4b = 0, s4a = 0, s4b = 0;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            uint32_t T[4], F[4], S[4];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                uint32_t L0, H0, L1, H1;
+                const int uu = half * 4 + q * 2 + k;
+                constexpr int RD = 6;
+                __builtin_amdgcn_sched_barrier(0);
+                split_out(v[uu], L0, H0, L1, H1);
+                if (uu + RD < 8)
+                    v[uu + RD] = load_vec<true>(cur + (uu + RD) * kSegRowVecs);
+                else if constexpr (HAS_NEXT)
+                    v[uu + RD - 8] = load_vec<true>(next + (uu + RD - 8) * kSegRowVecs);
+                __builtin_amdgcn_sched_barrier(0);
+                uint32_t qa, qb, ka, kb;
+                front4(L0, H0, T[2 * k], qa, ka);
+                front4(L1, H1, T[2 * k + 1], qb, kb);
+                F[2 * k] = T[2 * k] & perm(0u, 0xFF00FF00u, qa);
+                F[2 * k + 1] = T[2 * k + 1] & perm(0u, 0xFF00FF00u, qb);
+                S[2 * k] = perm(0u, 0x84428140u, qa) & (ka | 0x3F3F3F3Fu);
+                S[2 * k + 1] = perm(0u, 0x84428140u, qb) & (kb | 0x3F3F3F3Fu);
+            }
+            uint32_t t2a, t2b, f2a, f2b, s2a, s2b;
+            csa(t2a, s.t1, s.t1, T[0], T[1]);
+            csa(t2b, s.t1, s.t1, T[2], T[3]);
+            csa(f2a, s.f1, s.f1, F[0], F[1]);
+            csa(f2b, s.f1, s.f1, F[2], F[3]);
+            csa(s2a, s.s1, s.s1, S[0], S[1]);
+            csa(s2b, s.s1, s.s1, S[2], S[3]);
+            csa(q ? t4b : t4a, s.t2, s.t2, t2a, t2b);
+            csa(q ? f4b : f4a, s.f2, s.f2, f2a, f2b);
+            csa(q ? s4b : s4a, s.s2, s.s2, s2a, s2b);
+        }
+        csa(half ? t8b : t8a, s.t4, s.t4, t4a, t4b);
+        csa(half ? f8b : f8a, s.f4, s.f4, f4a, f4b);
+        csa(half ? s8b : s8a, s.s4, s.s4, s4a, s4b);
+    }
+    uint32_t ct, cf, cs;
+    csa(ct, s.t8, s.t8, t8a, t8b);
+    csa(cf, s.f8, s.f8, f8a, f8b);
+    csa(cs, s.s8, s.s8, s8a, s8b);
+    chain_push<0, kSegDepth>(s, blk, ct, cf, cs);
+}
+
+template <bool HAS_NEXT>
+__device__ __forceinline__ void seg_step_and_count(Lane<kSegDepth>& s, uint4 (&v)[kUnroll], uint32_t& blk, const uint4* cur,
+                                                   const uint4* next)
+{
+    blk = __builtin_amdgcn_readfirstlane(blk);
+    seg_step<HAS_NEXT>(s, v, blk, cur, next);
+    ++blk;
+    if (blk == (1u << kSegDepth) - 1u) {
+        flush(s, (1u << kSegDepth) - 1u);
+        blk = 0;
+    }
+}
+
+// Per-flag form: the 8 flags of one vector straight into the 21 lane counters (T bits 0-7, F bits 0-7, S bits 0-2 and 6-7).
+__device__ __forceinline__ void count8(uint32_t (&acc)[kInternal], const uint4& x)
+{
+    const uint32_t L0 = perm(x.y, x.x, 0x06040200u), H0 = perm(x.y, x.x, 0x07050301u);
+    const uint32_t L1 = perm(x.w, x.z, 0x06040200u), H1 = perm(x.w, x.z, 0x07050301u);
+    uint32_t T0, T1, qa, qb, ka, kb;
+    front4(L0, H0, T0, qa, ka);
+    front4(L1, H1, T1, qb, kb);
+    const uint32_t F0 = T0 & perm(0u, 0xFF00FF00u, qa), F1 = T1 & perm(0u, 0xFF00FF00u, qb);
+    const uint32_t S0 = perm(0u, 0x84428140u, qa) & (ka | 0x3F3F3F3Fu), S1 = perm(0u, 0x84428140u, qb) & (kb | 0x3F3F3F3Fu);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const uint32_t m = 0x01010101u << c;
+        acc[c] += __builtin_popcount(T0 & m) + __builtin_popcount(T1 & m);
+        acc[8 + c] += __builtin_popcount(F0 & m) + __builtin_popcount(F1 & m);
+    }
+#pragma unroll
+    for (int c = 0; c < kInternal - 16; ++c) {
+        const uint32_t m = 0x01010101u << (c < 3 ? c : c + 3);
+        acc[16 + c] += __builtin_popcount(S0 & m) + __builtin_popcount(S1 & m);
+    }
+}
+
+// the flags of vector x (grid positions q .. q+7) that lie in [b, e); the others become 0
+__device__ __forceinline__ uint4 mask_vec(uint4 x, uint64_t q, uint64_t b, uint64_t e)
+{
+    const uint32_t lk = b > q ? static_cast<uint32_t>(b - q < 8 ? b - q : 8) : 0u;  // first kept element
+    const uint32_t hk = e > q ? static_cast<uint32_t>(e - q < 8 ? e - q : 8) : 0u;  // one past the last
+    auto keep = [&](uint32_t k) { return k >= lk && k < hk; };
+    x.x &= (keep(0) ? 0xFFFFu : 0u) | (keep(1) ? 0xFFFF0000u : 0u);
+    x.y &= (keep(2) ? 0xFFFFu : 0u) | (keep(3) ? 0xFFFF0000u : 0u);
+    x.z &= (keep(4) ? 0xFFFFu : 0u) | (keep(5) ? 0xFFFF0000u : 0u);
+    x.w &= (keep(6) ? 0xFFFFu : 0u) | (keep(7) ? 0xFFFF0000u : 0u);
+    return x;
+}
+
+// the piece [b, e) of the unit starting at grid position w0 (its 8 rows in v[]) into the lane counters
+__device__ __forceinline__ void count_piece(uint32_t (&acc)[kInternal], const uint4 (&v)[kUnroll], uint64_t w0, uint64_t b,
+                                            uint64_t e, uint32_t lane)
+{
+#pragma unroll
+    for (int r = 0; r < kUnroll; ++r) {
+        const uint64_t r0 = w0 + static_cast<uint64_t>(r) * 512u;
+        if (r0 + 512u <= b || r0 >= e) continue;  // wave-uniform
+        if (r0 >= b && r0 + 512u <= e)
+            count8(acc, v[r]);
+        else
+            count8(acc, mask_vec(v[r], r0 + 8u * lane, b, e));
+    }
+}
+
+// what lane t < 32 contributes to slot t of a segment row (K1's slot_value, indexed by lane instead of thread)
+__device__ __forceinline__ uint64_t seg_slot_value(const uint32_t* tot, uint32_t t, int mode, uint64_t len)
+{
+    // slot -> internal T index + 1, one nibble per slot (0: no T/F counter): 2->2, 6->6, 7->7, 8->0, 11->3, 12->1, 13->4, 14->5
+    constexpr uint64_t kTOfSlot = 0x0652400187000300ull;
+    const uint32_t slot = t & 15u;
+    const bool fail = t >= 16;
+    const int ti = static_cast<int>((kTOfSlot >> (4 * slot)) & 15u) - 1;
+    uint64_t add = 0;
+    if (ti >= 0) add = fail ? tot[8 + ti] : static_cast<uint64_t>(tot[ti]) - tot[8 + ti];
+    if (slot == 10) add = fail ? tot[18] : tot[17];
+    if (slot == 9 && fail) add = static_cast<uint64_t>(tot[16]) + tot[18];
+    if (mode & 2) {
+        if (slot == 0) add = fail ? tot[20] : tot[19];
+        if (slot == 9 && !fail) add = len - (static_cast<uint64_t>(tot[16]) + tot[18]);
+    }
+    return add;
+}
+
+// grid position of offset i: clamped to the chunk [base, base + m]
+__device__ __forceinline__ uint64_t seg_pos(const uint64_t* __restrict__ off, uint64_t i, uint64_t base, uint64_t m, uint64_t lo0)
+{
+    uint64_t v = off[i];
+    v = v < base ? base : v;
+    v = v > base + m ? base + m : v;
+    return v - base + lo0;
+}
+
+__device__ __forceinline__ uint64_t uniform64(uint64_t x)
+{
+    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x));
+    const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x >> 32));
+    return (static_cast<uint64_t>(hi) << 32) | lo;
+}
+
+// every lane of the wave active, all arguments wave-uniform
+struct SegWalk {
+    const uint64_t* off;
+    uint64_t nseg, base, m, lo0;
+    uint32_t lane;
+    uint64_t wb;             // window: lane i holds the grid position of offset wb + i (clamped to nseg)
+    uint32_t wlo, whi;
+
+    __device__ __forceinline__ void load_window(uint64_t first)
+    {
+        wb = first;
+        const uint64_t i = first + lane;
+        const uint64_t v = seg_pos(off, i <= nseg ? i : nseg, base, m, lo0);
+        wlo = static_cast<uint32_t>(v);
+        whi = static_cast<uint32_t>(v >> 32);
+    }
+    // offsets s and s + 1 (s < nseg)
+    __device__ __forceinline__ void bounds(uint64_t s, uint64_t& sb, uint64_t& se)
+    {
+        if (s + 1 >= wb + 64) load_window(s);
+        const int k = static_cast<int>(s - wb);
+        sb = (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(whi), k))) << 32) |
+             static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(wlo), k));
+        se = (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(whi), k + 1))) << 32) |
+             static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(wlo), k + 1));
+    }
+    // the first segment s whose (clamped) end lies beyond grid position p; nseg if none.  64-ary search: one load per lane and
+    // round; with monotone offsets the answer is exact, with any offsets it is an index in [0, nseg].
+    __device__ __forceinline__ uint64_t first_segment(uint64_t p)
+    {
+        uint64_t lo = 1, hi = nseg + 1;  // the answer + 1 lies in [lo, hi]
+        while (lo < hi) {
+            const uint64_t step = (hi - lo + 63) / 64;
+            const uint64_t i = lo + lane * step;
+            bool gt = true;
+            if (i < hi) gt = seg_pos(off, i, base, m, lo0) > p;
+            const uint64_t mask = __ballot(gt);
+            if (mask == 0) {
+                lo = lo + 63 * step + 1;
+                continue;
+            }
+            const uint64_t f = static_cast<uint64_t>(__builtin_ctzll(mask));
+            const uint64_t nhi = lo + f * step < hi ? lo + f * step : hi;
+            lo = f ? lo + (f - 1) * step + 1 : lo;
+            hi = nhi;
+            lo = uniform64(lo);
+            hi = uniform64(hi);
+        }
+        return lo - 1;
+    }
+};
+
+// the wave's counters of the piece of segment s it holds -> out[s][32]
+__device__ __forceinline__ void seg_emit(Lane<kSegDepth>& st, uint32_t& blk, uint32_t* red, uint64_t* __restrict__ out, uint64_t s,
+                                         uint64_t len, bool plain, int mode, uint32_t lane)
+{
+    if (blk) {
+        flush(st, blk);
+        blk = 0;
+    }
+    uint32_t w[kInternal];
+#pragma unroll
+    for (int c = 0; c < kInternal; ++c) {
+        w[c] = wave_sum_lane63(st.acc[c]);
+        st.acc[c] = 0;
+    }
+    if (lane == 63) {
+#pragma unroll
+        for (int c = 0; c < kInternal; ++c) red[c] = w[c];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane < 32) {
+        const uint64_t add = seg_slot_value(red, lane, mode, len);
+        uint64_t* o = out + s * 32 + lane;
+        if (plain)
+            *o = add;  // store form, the whole segment in this wave: all 32 slots
+        else if (add)
+            (void)__hip_atomic_fetch_add(o, add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __builtin_amdgcn_wave_barrier();  // red[] is rewritten by the next segment's totals only after every lane has read it
+}
+
+// a0: 16-B aligned-down base; the chunk's flags occupy grid positions [lo0, hi0) and are global flags [base, base + hi0 - lo0).
+// nunits = ceil(hi0 / 4096).  mode: bit 0 store form (out[] zeroed in front), bit 1 superset.
+__global__ __launch_bounds__(kThreads) void flagstat_segments(const uint4* __restrict__ a0, uint64_t lo0, uint64_t hi0, uint64_t base,
+                                                              const uint64_t* __restrict__ off, uint64_t nseg,
+                                                              uint64_t* __restrict__ out, int mode, uint64_t nunits,
+                                                              uint32_t min_units)
+{
+    __shared__ uint32_t red_all[kThreads / 64][24];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = threadIdx.x >> 6;
+    const uint64_t waves = static_cast<uint64_t>(gridDim.x) * (kThreads / 64);
+    const uint64_t gw = static_cast<uint64_t>(blockIdx.x) * (kThreads / 64) + wave;
+    const uint64_t u_begin = gw * nunits / waves, u_end = (gw + 1) * nunits / waves;
+    const uint64_t p0 = u_begin * kSegWaveFlags > lo0 ? u_begin * kSegWaveFlags : lo0;  // this writer: grid positions [p0, E)
+    const uint64_t E = u_end * kSegWaveFlags < hi0 ? u_end * kSegWaveFlags : hi0;
+    if (p0 >= E) return;
+    uint32_t* red = red_all[wave];
+
+    SegWalk sw{off, nseg, base, hi0 - lo0, lo0, lane, 0, 0, 0};
+    uint64_t s = sw.first_segment(p0);
+    if (s >= nseg) return;
+    sw.load_window(s);
+
+    Lane<kSegDepth> st;
+    lane_init(st);
+    uint32_t blk = 0;
+    bool open = false;  // st holds counts of segment s not yet emitted
+    uint64_t sb = 0, se = 0;
+    auto emit = [&](uint64_t seg, uint64_t b_, uint64_t e_) {
+        const uint64_t pb = b_ > p0 ? b_ : p0, pe = e_ < E ? e_ : E;
+        seg_emit(st, blk, red, out, seg, pe - pb, (mode & 1) && b_ >= p0 && e_ <= E, mode, lane);
+    };
+
+    uint64_t u = p0 / kSegWaveFlags;
+    while (s < nseg && u < u_end) {
+        sw.bounds(s, sb, se);
+        const uint64_t w0 = u * kSegWaveFlags;
+        const uint64_t x = w0 > p0 ? w0 : p0;
+        // A segment that begins at or past this writer's end is not its business, nor (monotone offsets) is any later one.  This
+        // test comes first: a launch on one chunk of a longer array (the host form) clamps every later segment to an empty one
+        // at the chunk's end, and stepping through those one by one would cost the chunk's last writer O(nseg) per launch.
+        if (sb >= E) break;
+        if (se <= sb || se <= x) {  // empty (or, with malformed offsets, reversed or behind)
+            ++s;
+            continue;
+        }
+        if (sb >= w0 + kSegWaveFlags) {  // flags before the segment belong to none: skip whole units unread
+            u = sb / kSegWaveFlags;
+            continue;
+        }
+        const uint64_t seg_e = se < E ? se : E;
+        if (sb <= w0 && w0 >= lo0) {
+            const uint64_t k = (seg_e - w0) / kSegWaveFlags;  // whole units of segment s from here on
+            if (k >= min_units && k > 0) {
+                const uint4* p = a0 + u * kSegUnitVecs + lane;
+                uint4 v[kUnroll];
+#pragma unroll
+                for (int r = 0; r < 6; ++r) {
+                    v[r] = load_vec<true>(p + r * kSegRowVecs);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                for (uint64_t i = 1; i < k; ++i) {
+                    const uint4* pn = p + kSegUnitVecs;
+                    seg_step_and_count<true>(st, v, blk, p, pn);
+                    p = pn;
+                }
+                seg_step_and_count<false>(st, v, blk, p, nullptr);
+                u += k;
+                open = true;
+                if (u * kSegWaveFlags >= se) {
+                    emit(s, sb, se);
+                    open = false;
+                    ++s;
+                }
+                continue;
+            }
+        }
+        // per-flag unit: its 8 rows loaded at once, then every segment piece in it
+        uint4 v[kUnroll];
+        const uint64_t j0 = u * kSegUnitVecs + lane;
+        if (w0 >= lo0 && w0 + kSegWaveFlags <= hi0) {
+#pragma unroll
+            for (int r = 0; r < kUnroll; ++r) v[r] = load_vec<true>(a0 + j0 + r * kSegRowVecs);
+        } else {
+#pragma unroll
+            for (int r = 0; r < kUnroll; ++r) v[r] = load_guarded(a0, j0 + r * kSegRowVecs, lo0, hi0);
+        }
+        const uint64_t w1 = w0 + kSegWaveFlags;
+        uint64_t xx = x;
+        for (;;) {
+            // s < nseg, sb < se, se > xx, sb < w1
+            const uint64_t b = sb > xx ? sb : xx, e = se < w1 ? se : w1;
+            count_piece(st.acc, v, w0, b, e, lane);
+            open = true;
+            if (e < se) break;  // segment s goes on in the next unit
+            emit(s, sb, se);
+            open = false;
+            ++s;
+            xx = e;
+            bool more = false;
+            while (s < nseg) {
+                sw.bounds(s, sb, se);
+                if (sb >= E) break;  // (as in the outer walk: before the empty test)
+                if (se <= sb || se <= xx) {
+                    ++s;
+                    continue;
+                }
+                more = sb < w1;
+                break;
+            }
+            if (!more) break;
+        }
+        ++u;
+    }
+    if (open) emit(s, sb, se);  // this writer's range ends inside segment s
+}
+
+}  // namespace fsk
+
+// ------------------------------------------------------------------ launcher
+static std::atomic<uint32_t> g_seg_min_units{2};      // whole units in one segment from which the chain pays
+static std::atomic<uint32_t> g_seg_blocks_per_cu{1};
+
+extern "C" void fsk_segments_policy(uint32_t* min_units, uint32_t* blocks_per_cu)
+{
+    *min_units = g_seg_min_units.load();
+    *blocks_per_cu = g_seg_blocks_per_cu.load();
+}
+
+extern "C" void fsk_set_segments_policy(uint32_t min_units, uint32_t blocks_per_cu)
+{
+    g_seg_min_units = min_units;
+    g_seg_blocks_per_cu = blocks_per_cu < 1 ? 1 : (blocks_per_cu > 8 ? 8 : blocks_per_cu);
+}
+
+extern "C" hipError_t fsk_launch_segments(const uint16_t* d_chunk, uint64_t base, uint64_t m, const uint64_t* d_offsets, uint64_t nseg,
+                                          uint64_t* d_out, int mode, uint32_t grid, hipStream_t stream)
+{
+    if (nseg == 0) return hipSuccess;
+    if (d_out == nullptr || d_offsets == nullptr || grid == 0 || (m && d_chunk == nullptr)) return hipErrorInvalidValue;
+    const uintptr_t addr = reinterpret_cast<uintptr_t>(d_chunk);
+    if (addr & 1u) return hipErrorInvalidValue;
+    if (mode & 1) {
+        const hipError_t e = hipMemsetAsync(d_out, 0, nseg * 32 * sizeof(uint64_t), stream);
+        if (e != hipSuccess) return e;
+    }
+    if (m == 0) return hipSuccess;
+    const uintptr_t a0 = addr & ~static_cast<uintptr_t>(15);
+    const uint64_t lo0 = (addr - a0) / 2, hi0 = lo0 + m;
+    const uint64_t nunits = (hi0 + fsk::kSegWaveFlags - 1) / fsk::kSegWaveFlags;
+    const uint64_t want = (nunits + 3) / 4;  // one unit per wave at least
+    const uint32_t g = want < grid ? static_cast<uint32_t>(want) : grid;
+    hipLaunchKernelGGL(fsk::flagstat_segments, dim3(g), dim3(fsk::kThreads), 0, stream, reinterpret_cast<const uint4*>(a0), lo0, hi0,
+                       base, d_offsets, nseg, d_out, mode & 3, nunits, g_seg_min_units.load());
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ C entry points (include/libflagstats_hip.h)
+using fsint::DeviceGuard;
+using fsint::Engine;
+using fsint::fail_hip;
+using fsint::fail_text;
+
+namespace {
+
+#define SEG_TRY(expr)                                      \
+    do {                                                   \
+        hipError_t e_ = (expr);                            \
+        if (e_ != hipSuccess) return fail_hip(#expr, e_);  \
+    } while (0)
+
+constexpr uint64_t kMaxSegments = (~0ull) / 256 - 1;  // nseg * 256 bytes of counters must be a size
+
+uint32_t seg_grid(const Engine& e) { return static_cast<uint32_t>(e.cus) * g_seg_blocks_per_cu.load(); }
+
+// host offsets: non-decreasing, last <= n
+int check_host_offsets(const uint64_t* offsets, uint64_t nseg, uint64_t n)
+{
+    char buf[192];
+    for (uint64_t i = 0; i < nseg; ++i) {
+        if (offsets[i + 1] < offsets[i]) {
+            std::snprintf(buf, sizeof buf, "offsets must be non-decreasing: offsets[%llu] = %llu > offsets[%llu] = %llu",
+                          static_cast<unsigned long long>(i), static_cast<unsigned long long>(offsets[i]),
+                          static_cast<unsigned long long>(i + 1), static_cast<unsigned long long>(offsets[i + 1]));
+            return fail_text(buf);
+        }
+    }
+    if (offsets[nseg] > n) {
+        std::snprintf(buf, sizeof buf, "offsets[nseg] = %llu exceeds the array's %llu flags",
+                      static_cast<unsigned long long>(offsets[nseg]), static_cast<unsigned long long>(n));
+        return fail_text(buf);
+    }
+    return 0;
+}
+
+// a device pointer's allocation must hold `bytes` from it on (skipped where the runtime does not know the range)
+int check_extent(const void* p, uint64_t bytes, const char* what)
+{
+    hipDeviceptr_t b = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&b, &size, const_cast<void*>(p)) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    const uintptr_t end = reinterpret_cast<uintptr_t>(b) + size, at = reinterpret_cast<uintptr_t>(p);
+    if (at < reinterpret_cast<uintptr_t>(b) || end - at < bytes) {
+        char buf[192];
+        std::snprintf(buf, sizeof buf, "%s (%p) is %llu bytes short of the %llu the call needs", what, p,
+                      static_cast<unsigned long long>(bytes - (end > at ? end - at : 0)), static_cast<unsigned long long>(bytes));
+        return fail_text(buf);
+    }
+    return 0;
+}
+
+// device counters + device offsets of one synchronous call
+struct SegBuffers {
+    uint64_t* cnt = nullptr;
+    uint64_t* off = nullptr;
+    ~SegBuffers()
+    {
+        if (cnt) (void)hipFree(cnt);
+        if (off) (void)hipFree(off);
+    }
+    int alloc(uint64_t nseg)
+    {
+        hipError_t e = hipMalloc(&cnt, nseg * 32 * sizeof(uint64_t));
+        if (e != hipSuccess) {
+            cnt = nullptr;
+            (void)hipGetLastError();
+            char buf[160];
+            std::snprintf(buf, sizeof buf, "cannot allocate %llu bytes of device counters for %llu segments",
+                          static_cast<unsigned long long>(nseg * 256), static_cast<unsigned long long>(nseg));
+            return fail_text(buf);
+        }
+        e = hipMalloc(&off, (nseg + 1) * sizeof(uint64_t));
+        if (e != hipSuccess) {
+            off = nullptr;
+            return fail_hip("hipMalloc(segment offsets)", e);
+        }
+        return 0;
+    }
+};
+
+int host_args(const uint64_t* offsets, uint64_t nseg, const void* out)
+{
+    if (!offsets || !out) return fail_text("NULL offsets or out with nseg > 0");
+    if (nseg > kMaxSegments) return fail_text("nseg is too large: its counters cannot be allocated");
+    return 0;
+}
+
+// host copy of the device rows: allocated without exceptions (none may cross the C boundary), before any GPU work is queued
+struct HostRows {
+    std::unique_ptr<uint64_t[]> p;
+    uint64_t words = 0;
+    int alloc(uint64_t nseg)
+    {
+        words = nseg * 32;
+        p.reset(new (std::nothrow) uint64_t[words]);
+        if (!p) {
+            char buf[160];
+            std::snprintf(buf, sizeof buf, "cannot allocate %llu bytes of host memory for the rows of %llu segments",
+                          static_cast<unsigned long long>(words * 8), static_cast<unsigned long long>(nseg));
+            return fail_text(buf);
+        }
+        return 0;
+    }
+};
+
+void apply(uint64_t* out, const HostRows& got, int flags)
+{
+    if (flags & 1)
+        std::memcpy(out, got.p.get(), got.words * sizeof(uint64_t));
+    else
+        for (uint64_t i = 0; i < got.words; ++i) out[i] += got.p[i];
+}
+
+}  // namespace
+
+extern "C" {
+
+int FLAGSTATS_hip_device_u16_segments(const uint16_t* d_array, uint64_t n, const uint64_t* d_offsets, uint64_t nseg, uint64_t* d_out,
+                                      int flags, void* stream)
+{
+    FS_ENTRY();
+    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
+    if (nseg == 0) return 0;
+    if (!d_offsets || !d_out) return fail_text("NULL d_offsets or d_out with nseg > 0");
+    if (n && !d_array) return fail_text("NULL array with n > 0");
+    if (nseg > kMaxSegments) return fail_text("nseg is too large for its counters to be a size");
+    if (reinterpret_cast<uintptr_t>(d_array) & 1u) return fail_text("array must be 2-byte aligned");
+    int dev_out = -1, dev = -1;
+    bool plain = false;
+    int rc = fsint::device_of_pointer(d_out, "d_out", &dev_out, &plain);
+    if (rc) return rc;
+    if (!plain) return fail_text("d_out must be device memory (the counters are added with device atomics)");
+    rc = fsint::device_of_pointer(d_offsets, "d_offsets", &dev);
+    if (rc) return rc;
+    if (dev != dev_out) return fail_text("d_offsets and d_out live on different devices");
+    if (n) {
+        rc = fsint::device_of_pointer(d_array, "d_array", &dev);
+        if (rc) return rc;
+        if (dev != dev_out) return fail_text("d_array and d_out live on different devices");
+    }
+    Engine* e = fsint::engine_for_device(dev_out);
+    if (!e) return -1;
+    DeviceGuard guard(e->device);
+    if (!guard.ok()) return -1;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = fsint::check_stream_device(s, e->device);
+    if (rc) return rc;
+    if ((rc = check_extent(d_out, nseg * 32 * sizeof(uint64_t), "d_out")) || (rc = check_extent(d_offsets, (nseg + 1) * sizeof(uint64_t), "d_offsets")))
+        return rc;
+    if (n && (rc = check_extent(d_array, n * sizeof(uint16_t), "d_array"))) return rc;
+    SEG_TRY(fsk_launch_segments(d_array, 0, n, d_offsets, nseg, d_out, flags & 3, seg_grid(*e), s));
+    return 0;
+}
+
+int FLAGSTATS_hip_device_u16_segments_sync(const uint16_t* d_array, uint64_t n, const uint64_t* offsets, uint64_t nseg, uint64_t* out,
+                                           int flags)
+{
+    FS_ENTRY();
+    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
+    if (nseg == 0) return 0;
+    int rc = host_args(offsets, nseg, out);
+    if (rc) return rc;
+    if (n && !d_array) return fail_text("NULL array with n > 0");
+    if (reinterpret_cast<uintptr_t>(d_array) & 1u) return fail_text("array must be 2-byte aligned");
+    Engine* ep = nullptr;
+    if (n) {
+        int dev = -1;
+        rc = fsint::device_of_pointer(d_array, "d_array", &dev);
+        if (rc) return rc;
+        ep = fsint::engine_for_device(dev);
+    } else {
+        ep = fsint::default_engine();
+    }
+    if (!ep) return -1;
+    Engine& e = *ep;
+    std::lock_guard<std::mutex> lk(e.mu);
+    if (fsint::engine_alive(e)) return -1;
+    DeviceGuard guard(e.device);
+    if (!guard.ok()) return -1;
+    SegBuffers buf;
+    HostRows got;
+    if ((rc = buf.alloc(nseg)) || (rc = got.alloc(nseg))) return rc;
+    if ((rc = check_host_offsets(offsets, nseg, n))) return rc;
+    if (n && (rc = check_extent(d_array, n * sizeof(uint16_t), "d_array"))) return rc;
+    hipStream_t s = e.stream[0];
+    SEG_TRY(hipMemcpyAsync(buf.off, offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    SEG_TRY(fsk_launch_segments(d_array, 0, n, buf.off, nseg, buf.cnt, 1 | (flags & 2), seg_grid(e), s));
+    SEG_TRY(hipMemcpyAsync(got.p.get(), buf.cnt, got.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    SEG_TRY(hipStreamSynchronize(s));
+    apply(out, got, flags);
+    return 0;
+}
+
+int FLAGSTATS_hip_u16_x64_segments(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint64_t nseg, uint64_t* out, int flags)
+{
+    FS_ENTRY();
+    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
+    if (nseg == 0) return 0;
+    int rc = host_args(offsets, nseg, out);
+    if (rc) return rc;
+    if (n && !array) return fail_text("NULL array with n > 0");
+    Engine* ep = fsint::default_engine();
+    if (!ep) return -1;
+    Engine& e = *ep;
+    std::lock_guard<std::mutex> lk(e.mu);
+    if (fsint::engine_alive(e)) return -1;
+    DeviceGuard guard(e.device);
+    if (!guard.ok()) return -1;
+    fsint::lz4_gpu_other_use(e);
+    SegBuffers buf;
+    HostRows got;
+    if ((rc = buf.alloc(nseg)) || (rc = got.alloc(nseg))) return rc;
+    if ((rc = check_host_offsets(offsets, nseg, n))) return rc;
+    if ((rc = fsint::engine_second(e))) return rc;
+    // only the flags some segment covers cross the bus: [offsets[0], offsets[nseg]) in chunks of "chunk_flags", alternating
+    // between the engine's two streams and staging buffers (the copy of chunk k + 1 overlaps the kernel on chunk k); every
+    // chunk's launch adds the pieces of the segments it holds to the same device counters
+    const uint64_t chunk = fsint::knobs().chunk_flags.load() < 8 ? 8 : fsint::knobs().chunk_flags.load();
+    const uint64_t first = offsets[0], last = offsets[nseg];
+    const int slots = last - first > chunk ? 2 : 1;
+    for (int i = 0; i < slots; ++i)
+        if ((rc = fsint::stage_reserve(e, i, last - first < chunk ? (last - first ? last - first : 1) : chunk))) return rc;
+    hipStream_t s0 = e.stream[0];
+    SEG_TRY(hipMemsetAsync(buf.cnt, 0, nseg * 32 * sizeof(uint64_t), s0));
+    SEG_TRY(hipMemcpyAsync(buf.off, offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s0));
+    if (slots == 2 && (rc = fsint::stream_wait_stream(e, e.stream[1], s0))) return rc;
+    const uint32_t grid = seg_grid(e);
+    const int mode = flags & 2;
+    uint64_t k = 0;
+    for (uint64_t pos = first; pos < last; pos += chunk, ++k) {
+        const int sl = static_cast<int>(k % static_cast<uint64_t>(slots));
+        const uint64_t c = last - pos < chunk ? last - pos : chunk;
+        SEG_TRY(hipMemcpyAsync(e.stage[sl], array + pos, c * sizeof(uint16_t), hipMemcpyHostToDevice, e.stream[sl]));
+        SEG_TRY(fsk_launch_segments(e.stage[sl], pos, c, buf.off, nseg, buf.cnt, mode, grid, e.stream[sl]));
+    }
+    if (slots == 2 && (rc = fsint::stream_wait_stream(e, s0, e.stream[1]))) return rc;
+    SEG_TRY(hipMemcpyAsync(got.p.get(), buf.cnt, got.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s0));
+    SEG_TRY(hipStreamSynchronize(s0));
+    if (slots == 2) SEG_TRY(hipStreamSynchronize(e.stream[1]));
+    apply(out, got, flags);
+    return 0;
+}
+
+}  // extern "C"

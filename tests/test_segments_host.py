@@ -1,0 +1,118 @@
+"""Segmented flagstat, host side (no GPU): the Python module's argument checks, the offsets helper, the test oracle itself,
+and the C entries' loud failure on a box without a GPU."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from segments_oracle import segmented_counters  # noqa: E402
+
+
+@pytest.mark.parametrize("offsets, why", [
+    ([0, 5, 3, 10], "non-decreasing"),
+    ([0, 5, 11], "exceeds"),
+    (np.array([[0, 5], [5, 10]]), "1-D"),
+    (np.array([0.0, 5.0, 10.0]), "integer"),
+    (np.array([-1, 5, 10], dtype=np.int64), "negative"),
+    (np.array([], dtype=np.uint64), ">= 1"),
+])
+def test_bad_offsets_raise_before_the_library_is_touched(monkeypatch, offsets, why):
+    from libflagstats_amd import _lib, segments
+
+    def untouchable():
+        raise AssertionError("the library was called before the offsets were checked")
+
+    monkeypatch.setattr(_lib, "lib", untouchable)
+    values = np.zeros(10, dtype=np.uint16)
+    with pytest.raises(ValueError, match=why):
+        segments.flagstats_segments(values, offsets)
+    with pytest.raises(ValueError, match=why):
+        segments.count_segments_device_ptr(0x1000, 10, offsets)
+
+
+def test_flagstats_segments_wants_a_uint16_vector(monkeypatch):
+    from libflagstats_amd import _lib, segments
+    monkeypatch.setattr(_lib, "lib", lambda: (_ for _ in ()).throw(AssertionError("library touched")))
+    with pytest.raises(ValueError):
+        segments.flagstats_segments(np.zeros(10, dtype=np.int32), [0, 10])
+    with pytest.raises(ValueError):
+        segments.flagstats_segments(np.zeros((2, 5), dtype=np.uint16), [0, 10])
+
+
+def test_offsets_from_lengths_round_trips():
+    from libflagstats_amd.segments import offsets_from_lengths
+    rng = np.random.RandomState(3)
+    for lengths in ([], [0], [5], [0, 0, 3, 0], rng.randint(0, 2000, 1000)):
+        o = offsets_from_lengths(lengths)
+        assert o.dtype == np.uint64 and o.size == len(lengths) + 1 and o[0] == 0
+        assert np.array_equal(np.diff(o.astype(np.int64)), np.asarray(lengths, dtype=np.int64))
+    assert np.array_equal(offsets_from_lengths(np.array([2, 3], dtype=np.int32)), [0, 2, 5])
+    with pytest.raises(ValueError):
+        offsets_from_lengths([3, -1])
+    with pytest.raises(ValueError):
+        offsets_from_lengths([[1, 2]])
+
+
+def test_segment_dicts_shape():
+    from libflagstats_amd.segments import segment_dicts
+    c = np.zeros((2, 32), dtype=np.uint64)
+    c[1, 2] = 3          # FUNMAP pass
+    d = segment_dicts(c, [0, 4, 10])
+    assert [x["n_values"] for x in d] == [4, 6]
+    assert d[1]["passed"]["FUNMAP"] == 3 and d[1]["passed"]["mapped"] == 3
+    with pytest.raises(ValueError):
+        segment_dicts(c, [0, 4])
+
+
+def test_segmented_oracle_agrees_with_the_oracle_per_segment(oracle_mod):
+    rng = np.random.RandomState(11)
+    x = rng.randint(0, 65536, 400_000).astype(np.uint16)
+    lengths = rng.choice([0, 0, 1, 2, 7, 8, 9, 100, 1000, 4095, 4096, 4097, 16383, 16384, 16385], 60)
+    for head, tail in ((0, 0), (13, 0), (0, 17), (5, 9)):
+        o = head + np.concatenate([[0], np.cumsum(lengths)])
+        assert o[-1] + tail <= x.size
+        xs = x[:o[-1] + tail]
+        got = segmented_counters(xs, o)
+        for i in range(len(lengths)):
+            assert np.array_equal(got[i], oracle_mod.flagstat_hist(xs[o[i]:o[i + 1]])), (head, tail, i)
+        # superset slots: 0/16 primary paired by QC class, 9 = length - slot 25
+        sup = segmented_counters(xs, o, superset=True)
+        for i in range(len(lengths)):
+            a = xs[o[i]:o[i + 1]]
+            pp = ((a & 0x100) == 0) & ((a & 0x800) == 0) & ((a & 1) == 1)
+            fail = (a & 0x200) != 0
+            want = oracle_mod.flagstat_hist(a).copy()
+            want[0], want[16], want[9] = int((pp & ~fail).sum()), int((pp & fail).sum()), a.size - int(fail.sum())
+            assert np.array_equal(sup[i], want), (head, tail, i)
+    # all empty, no segments, an empty array
+    assert not segmented_counters(x, [5, 5, 5]).any()
+    assert segmented_counters(x, [7]).shape == (0, 32)
+    assert segmented_counters(x[:0], [0, 0]).shape == (1, 32)
+
+
+def test_no_gpu_means_the_segment_entries_fail_loudly():
+    """Without a GPU the segmented entries return non-zero with a message and leave `out` alone; nothing is computed on the
+    CPU."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    from libflagstats_amd import _lib, segments
+    lib = _lib.lib()
+    a = np.arange(100, dtype=np.uint16)
+    o = np.array([0, 40, 100], dtype=np.uint64)
+    out = np.full((2, 32), 7, dtype=np.uint64)
+    calls = [
+        ("FLAGSTATS_u16_x64_segments", lambda: lib.FLAGSTATS_hip_u16_x64_segments(a.ctypes.data, a.size, o.ctypes.data, 2, out.ctypes.data, 0)),
+        ("device_u16_segments_sync", lambda: lib.FLAGSTATS_hip_device_u16_segments_sync(a.ctypes.data, a.size, o.ctypes.data, 2, out.ctypes.data, 1)),
+        ("device_u16_segments", lambda: lib.FLAGSTATS_hip_device_u16_segments(a.ctypes.data, a.size, o.ctypes.data, 2, out.ctypes.data, 0, None)),
+    ]
+    for name, call in calls:
+        assert call() != 0, name
+        assert lib.FLAGSTATS_hip_last_error(), name
+        assert (out == 7).all(), name
+    with pytest.raises(_lib.FlagstatsHipError):
+        segments.flagstats_segments(a, o)
+    # nseg == 0 does nothing and succeeds, GPU or not
+    assert lib.FLAGSTATS_hip_u16_x64_segments(a.ctypes.data, a.size, o.ctypes.data, 0, out.ctypes.data, 0) == 0
