@@ -22,7 +22,8 @@ extern "C" {
 // Bounds: every offset the kernel reads is clamped to [base, base + m] and a segment whose end lies before its begin is
 // empty, so malformed offsets never make it read outside d_chunk[0 .. m) or write outside d_out[0 .. nseg * 32); only their
 // counters are undefined.  The kernel reads d_offsets[0 .. nseg] and nothing beyond.  `grid` = workgroups (of 256 threads)
-// at most; 0 is refused.
+// at most; 0 is refused.  Limit: a wave's totals are uint32, so every wave must own fewer than 2^32 flags, i.e. m < 2^32 * 4 *
+// (workgroups launched); the public entries launch >= 4 waves per CU and cannot reach it, direct callers with a small grid can.
 hipError_t fsk_launch_segments(const uint16_t* d_chunk, uint64_t base, uint64_t m, const uint64_t* d_offsets, uint64_t nseg,
                                uint64_t* d_out, int mode, uint32_t grid, hipStream_t stream);
 // workgroups per CU of the segmented kernel and the shortest run of whole wave units (4096 flags) inside one segment that

@@ -302,24 +302,50 @@ def test_error_paths_leave_out_untouched(hip):
     d.free()
 
 
-@pytest.mark.parametrize("layout", ["blocks", "random"])
+@pytest.mark.parametrize("layout", ["blocks", "random", "whole", "long"])
 def test_full_size_device_resident(hip, layout):
-    """2^32 flags on the device cut into 512,000-flag blocks (the column store's block size) or random lengths; every segment
-    checked against the oracle's generator without a host copy of the 8 GiB."""
+    """2^32 flags on the device cut into 512,000-flag blocks (the column store's block size), random lengths, one segment (1,024
+    units per wave: four chain epochs each) or long unaligned segments of 1-8 M flags; every segment checked against the
+    oracle's generator without a host copy of the 8 GiB, in the store and += forms; then the same layout over a periodic array
+    (filled on the device) with superset, against segments_oracle.periodic_counters."""
     import oracle
+    import torch
     from libflagstats_amd import device
+    from segments_oracle import SEG_EPOCH, periodic_counters, writer_ranges
     n = 1 << 32
     kind, seed, mask = oracle.GEN_UNIFORM, 77, 0xFFFF
     d = device.DeviceFlags(n).generate(kind, seed=seed, mask=mask)
     if layout == "blocks":
         o = np.append(np.arange(0, n, 512_000, dtype=np.int64), n)
-    else:
+    elif layout == "random":
         rng = np.random.RandomState(4)
         o = np.concatenate([[0], np.cumsum(rng.randint(0, 1_024_000, 9000))]).astype(np.int64) + 999
         o = np.append(o[o < n - 5], n - 5)
+    elif layout == "whole":
+        o = np.array([0, n], dtype=np.int64)
+    else:
+        rng = np.random.RandomState(5)
+        o = np.concatenate([[0], np.cumsum(rng.randint(1_000_000, 8_000_001, 1100))]).astype(np.int64) + 7
+        o = np.append(o[o < n - 3], n - 3)
+    w = writer_ranges(d.ptr % 16, n, hip.FLAGSTATS_hip_compute_units())
+    chain = w.pieces(o)["chain"]
+    if layout == "whole":
+        assert (chain == 1024).all() and chain.size == w.waves == 1024, (chain.min(), chain.max())
+    if layout == "long":
+        assert chain.max() > SEG_EPOCH
     got = device_counts(hip, d.ptr, n, o, 1)
+    acc = device_counts(hip, d.ptr, n, o, 0)
     for i in range(o.size - 1):
         want = oracle.flagstat_generated(kind, seed, mask, first_index=int(o[i]), n=int(o[i + 1] - o[i]), threads=16)
         assert np.array_equal(got[i], want), (layout, i)
+        assert np.array_equal(acc[i], want), (layout, i, "+=")
     assert np.array_equal(got.sum(axis=0), d.count(offset=int(o[0]), n=int(o[-1] - o[0])))
     d.free()
+    pattern = np.random.RandomState(78).randint(0, 65536, 65_521).astype(np.uint16)
+    t = torch.from_numpy(pattern.view(np.int16)).cuda().repeat(-(-n // pattern.size))
+    torch.cuda.synchronize()
+    want = periodic_counters(pattern, o, superset=True)
+    for flags in (3, 2):
+        assert np.array_equal(device_counts(hip, t.data_ptr(), n, o, flags), want), (layout, "superset", flags)
+    del t
+    torch.cuda.empty_cache()   # 8-16 GiB back to the device for the tests after this one

@@ -116,3 +116,94 @@ def test_no_gpu_means_the_segment_entries_fail_loudly():
         segments.flagstats_segments(a, o)
     # nseg == 0 does nothing and succeeds, GPU or not
     assert lib.FLAGSTATS_hip_u16_x64_segments(a.ctypes.data, a.size, o.ctypes.data, 0, out.ctypes.data, 0) == 0
+
+
+def test_periodic_oracle_agrees_with_the_segmented_oracle():
+    from segments_oracle import periodic_counters, segmented_counters_many
+    rng = np.random.RandomState(23)
+    for trial in range(40):
+        period = int(rng.choice([1, 2, 3, 4, 7, 8, 64, 511, 4096, 4099, rng.randint(1, 20_000)]))
+        pattern = rng.randint(0, 65536, period).astype(np.uint16)
+        phase = int(rng.randint(0, 3 * period))
+        n = int(rng.randint(1, 200_000))
+        x = np.resize(np.roll(pattern, -(phase % period)), n)
+        cuts = np.sort(rng.randint(0, n + 1, rng.randint(0, 60)))
+        o = np.concatenate([[0], cuts, [n]]) if trial % 2 else np.concatenate([cuts[:1], cuts, cuts[-1:]]) if cuts.size else np.array([0, n])
+        for sup in (False, True):
+            want = segmented_counters(x, o, superset=sup)
+            assert np.array_equal(periodic_counters(pattern, o, superset=sup, phase=phase), want), (trial, period, sup)
+            assert np.array_equal(segmented_counters_many(x, [o, o[::2]], superset=sup)[0], want), (trial, sup)
+    # far past any host array: the counts scale by whole periods
+    pattern = rng.randint(0, 65536, 4099).astype(np.uint16)
+    big = periodic_counters(pattern, [0, 4099 * (1 << 22), 4099 * (1 << 22) + 4099], superset=True)
+    one = segmented_counters(pattern, [0, 4099], superset=True)[0]
+    assert np.array_equal(big[0], one * np.uint64(1 << 22)) and np.array_equal(big[1], one)
+
+
+def test_batched_oracle_matches_per_layout():
+    from segments_oracle import segmented_counters_many
+    rng = np.random.RandomState(29)
+    x = rng.randint(0, 65536, 300_001).astype(np.uint16)
+    layouts = [np.array([0, x.size]), np.array([5, 5, 7, 4096, 4097, 300_000]), np.array([9]),
+               np.concatenate([[0], np.sort(rng.randint(0, x.size + 1, 500)), [x.size]])]
+    for sup in (False, True):
+        for o, got in zip(layouts, segmented_counters_many(x, layouts, superset=sup)):
+            assert np.array_equal(got, segmented_counters(x, o, superset=sup))
+
+
+def _source(*parts):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, *parts)) as f:
+        return f.read()
+
+
+def test_writer_mirror_matches_the_sources():
+    """The writer split the GPU regime tests place their boundaries by (segments_oracle.WriterSplit) restates the launcher's
+    and the kernel prologue's arithmetic: if either changes, this test names what to update."""
+    import re
+
+    import segments_oracle as so
+    hdr = _source("libflagstats_amd", "csrc", "flagstat_segments.h")
+    src = re.sub(r"\s+", " ", _source("libflagstats_amd", "csrc", "flagstat_segments.hip"))
+    k1 = _source("libflagstats_amd", "csrc", "flagstat_kernels.h")
+    assert int(re.search(r"constexpr int kSegWaveFlags = (\d+);", hdr).group(1)) == so.SEG_UNIT
+    assert int(re.search(r"constexpr int kThreads = (\d+);", k1).group(1)) == 64 * so.SEG_WAVES_PER_BLOCK
+    assert (1 << int(re.search(r"constexpr int kSegDepth = (\d+);", src).group(1))) - 1 == so.SEG_EPOCH
+    assert "static std::atomic<uint32_t> g_seg_min_units{%d};" % so.SEG_MIN_UNITS in src
+    for rule in ("const uint64_t lo0 = (addr - a0) / 2, hi0 = lo0 + m;",
+                 "const uint64_t nunits = (hi0 + fsk::kSegWaveFlags - 1) / fsk::kSegWaveFlags;",
+                 "const uint64_t want = (nunits + 3) / 4;",
+                 "const uint32_t g = want < grid ? static_cast<uint32_t>(want) : grid;",
+                 "const uint64_t waves = static_cast<uint64_t>(gridDim.x) * (kThreads / 64);",
+                 "const uint64_t u_begin = gw * nunits / waves, u_end = (gw + 1) * nunits / waves;",
+                 "const uint64_t p0 = u_begin * kSegWaveFlags > lo0 ? u_begin * kSegWaveFlags : lo0;",
+                 "const uint64_t E = u_end * kSegWaveFlags < hi0 ? u_end * kSegWaveFlags : hi0;",
+                 "if (k >= min_units && k > 0) {",
+                 "if (blk == (1u << kSegDepth) - 1u) {",
+                 "(mode & 1) && b_ >= p0 && e_ <= E"):
+        assert rule in src, rule
+
+
+def test_writer_mirror_partitions_the_array():
+    from segments_oracle import SEG_UNIT, writer_ranges
+    rng = np.random.RandomState(31)
+    for addr in range(0, 16, 2):
+        for n, grid in ((1, 1), (4096, 1), (4096 * 9 + 3, 2), (1 << 20, 7), (12_345_679, 3), (1 << 25, 1024)):
+            w = writer_ranges(addr, n, grid)
+            assert w.begin[0] == 0 and w.end[-1] == n and (w.begin[1:] == w.end[:-1]).all() and (w.end >= w.begin).all()
+            assert w.grid == min(grid, (w.nunits + 3) // 4) and w.waves == 4 * w.grid
+            inner = (w.u_end * SEG_UNIT - w.lo0)[:-1]   # every seam is a unit boundary
+            assert np.array_equal(w.end[:-1], np.clip(inner, 0, n))
+            cuts = np.sort(rng.randint(0, n + 1, 50))
+            o = np.concatenate([[0], cuts, [n]])
+            for mu in (0, 1, 2, 255, 0xFFFFFFFF):
+                p = w.pieces(o, mu)
+                lengths = np.bincount(p["seg"], weights=p["e"] - p["b"], minlength=o.size - 1)
+                assert np.array_equal(lengths, np.diff(o)), (addr, n, grid)
+                assert np.array_equal(p["head"] + p["chain"] * SEG_UNIT + p["tail"], p["e"] - p["b"])
+                assert (p["head"] >= 0).all() and (p["tail"] >= 0).all() and (p["tail"] < SEG_UNIT).all()
+                assert (p["chain"] == 0).all() or mu != 0xFFFFFFFF
+                assert ((p["head"][p["chain"] > 0] + p["b"][p["chain"] > 0] + w.lo0) % SEG_UNIT == 0).all()
+                # the store form's plain rows are exactly the segments held by one writer
+                per_seg = np.bincount(p["seg"], minlength=o.size - 1)
+                assert np.array_equal(p["plain"], per_seg[p["seg"]] == 1)
