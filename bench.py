@@ -13,8 +13,10 @@ the rendezvous (unique id, barriers, max-over-ranks of the timings).
 
 Order of a run: generate -> read-bandwidth probe (untimed; also lets the chip settle: after idle the
 first ~20 launches of ANY kernel run 5-40 % slow, tools/step_times.py) -> W warm-up steps -> barrier ->
-exactly K timed steps, one hipEvent per step on the launch stream -> barrier -> parity of the WHOLE
-array against the oracle -> CPU baseline.
+exactly K timed steps, one hipEvent per step on the launch stream -> barrier -> --dump-outputs -> the line.
+That is all a plain run does.  `--full` adds what takes work of its own beyond the headline: N > 1, the
+collective alone and every rank's K1 alone (between the warm-up and the timed steps); the shader clock
+under load; parity of the WHOLE array against the oracle; the CPU baseline.
 
 `--gpus N` without a launcher (no RANK in the environment) starts the N ranks itself: N fresh child processes of this
 script with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, spawned before anything in the parent has touched the GPU, rank
@@ -23,8 +25,8 @@ already there and nothing is spawned.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects: "roofline"
 (HBM: algorithmic bytes = 2 B/flag over the event-timed average step on the launch stream) and
-"cpu_baseline" (the reference's own dispatcher kernel, oracle/_ref, timed on this host on a bounded
-sample).
+"cpu_baseline" (--full only: the reference's own dispatcher kernel, oracle/_ref, timed on this host on a
+bounded sample; null otherwise).
 """
 import argparse
 import ctypes
@@ -345,7 +347,10 @@ def main():
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--flags-per-gpu", type=int, default=2 ** 32, help="default 2^32 flags = 8 GiB uint16")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="0 disables the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: N > 1 the collective alone and every "
+                         "rank's K1 alone, the shader clock under load, parity of the whole workload, the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="with --full; 0 disables the CPU baseline leg")
     ap.add_argument("--cpu-sample", type=int, default=2 ** 27)
     ap.add_argument("--cpu-dram-per-core", type=int, default=2 ** 27,
                     help="flags per core of the all-cores-over-DRAM leg (default 2^27 = 256 MiB per pinned thread; 0: skip)")
@@ -353,8 +358,9 @@ def main():
     ap.add_argument("--probe-reps", type=int, default=40,
                     help="read-only bandwidth probe launches before the warm-up steps (0: no probe; the first timed "
                          "steps then carry the chip's after-idle transient when --warmup is small)")
-    ap.add_argument("--parity", choices=("full", "off"), default="full",
-                    help="full: every rank's whole shard vs the oracle (all host cores, ~1 s per 2^32 flags)")
+    ap.add_argument("--parity", choices=("full", "off"), default=None,
+                    help="full: every rank's whole shard vs the oracle (all host cores, ~1 s per 2^32 flags); "
+                         "default: full with --full, off without")
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: --flags-per-gpu is the TOTAL array, split into contiguous shards over the ranks "
                          "(default is weak scaling: every rank holds its own --flags-per-gpu shard)")
@@ -383,6 +389,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.parity is None:
+        args.parity = "full" if args.full else "off"
 
     if "RANK" not in os.environ and (args.gpus > 1 or args.force_dist):
         sys.exit(spawn_ranks(max(1, args.gpus)))   # no launcher: start the ranks ourselves (before any GPU call)
@@ -662,10 +670,10 @@ def main():
         step()
     drain()
     injected_fault("warmup", rank)
-    # N > 1, untimed: what the collective alone costs here (stream events around 10 all-reduces of a scratch uint64[32] on
-    # the launch stream; the slowest rank's figure) -- so that a first 8-GPU number can be read: step = K1 + K2 + this
+    # N > 1, --full, untimed: what the collective alone costs here (stream events around 10 all-reduces of a scratch uint64[32]
+    # on the launch stream; the slowest rank's figure) -- so that a first 8-GPU number can be read: step = K1 + K2 + this
     allreduce_us = None
-    if multi:
+    if multi and args.full:
         scratch = torch.zeros(32, dtype=torch.int64, device=dev)
         allreduce(scratch, main_stream)
         torch.cuda.synchronize()
@@ -678,11 +686,12 @@ def main():
         t = torch.tensor([a0.elapsed_time(a1) * 100.0], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         allreduce_us = round(float(t[0]), 2)
-    # N > 1, untimed: every rank's OWN K1 (the N = 1 form: one launch, atomic epilogue, no K2, no collective) over its shard, 20
-    # launches between stream events -- so that a scaling number can be taken apart without a second run: step - K1 alone = what
-    # K2 + the collective + waiting for the slowest rank cost; the spread of K1 alone over the ranks = chip-to-chip variation
+    # N > 1, --full, untimed: every rank's OWN K1 (the N = 1 form: one launch, atomic epilogue, no K2, no collective) over its
+    # shard, 20 launches between stream events -- so that a scaling number can be taken apart without a second run: step - K1
+    # alone = what K2 + the collective + waiting for the slowest rank cost; the spread of K1 alone over the ranks = chip-to-chip
+    # variation
     per_rank_k1_ms = None
-    if multi:
+    if multi and args.full:
         k1_scratch = torch.zeros(32, dtype=torch.int64, device=dev)
         for _ in range(3):
             device.count_torch(flags, k1_scratch)
@@ -728,9 +737,9 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         wall, ev_ms = float(tmax[0]), float(tmax[1])
 
-    # shader clock under K1's load, measured after the timed region (same thermal state, a few ms later)
+    # --full: shader clock under K1's load, measured after the timed region (same thermal state, a few ms later)
     sclk = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             mhz = ctypes.c_double(0.0)
             _lib.check(lib.FLAGSTATS_hip_sclk_under_load(flags.data_ptr(), n, max(3, min(20, int(30.0 / max(ev_ms / args.steps, 1e-3)))),
@@ -776,7 +785,7 @@ def main():
             if not ok:
                 print("PARITY MISMATCH", got, want, file=sys.stderr)
         cpu = None
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             cpu = cpu_baseline(args.cpu_seconds, min(args.cpu_sample, n), args.seed, args.cpu_dram_per_core)
         traffic = None
         traffic_note = None
@@ -820,6 +829,7 @@ def main():
                          "frac_of_read_probe": round(achieved / probe_gbs, 4) if probe_gbs else None},
             "cpu_baseline": cpu,
             "parity": parity,
+            "full": args.full,
             "counters_fail_qc_reads": int(got[25]),
         }
         if cpu:

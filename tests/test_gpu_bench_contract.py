@@ -1,6 +1,7 @@
 """GPU: bench.py's output contract (the driver parses ONE JSON line from rank 0): a small end-to-end run
 must print exactly one JSON object with the agreed keys, the roofline and cpu_baseline objects, a
-bit-exact parity verdict, and numbers that are consistent with each other."""
+bit-exact parity verdict, and numbers that are consistent with each other.  The CPU baseline, the
+parity check and the per-kernel figures are --full's; a plain run prints the headline alone."""
 import json
 import os
 import subprocess
@@ -13,7 +14,7 @@ from conftest import ROOT
 pytestmark = pytest.mark.gpu
 
 
-def run_bench(*extra):
+def run_bench(*extra, full=True):
     import socket
     with socket.socket() as sk:            # a free rendezvous port for the --force-dist run
         sk.bind(("127.0.0.1", 0))
@@ -21,7 +22,7 @@ def run_bench(*extra):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--flags-per-gpu", str(2 ** 27), "--steps", "6",
                         "--warmup", "2", "--cpu-seconds", "0.5", "--cpu-sample", str(2 ** 22), "--cpu-dram-per-core", str(2 ** 23),
-                        "--probe-reps", "3", *extra],
+                        "--probe-reps", "3", *(("--full",) if full else ()), *extra],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -61,6 +62,39 @@ def test_single_gpu_line(hip, tmp_path):
     assert dumped.dtype == np.float64 and dumped.shape == (32,)
     want = oracle.flagstat_generated(oracle.GEN_UNIFORM, 2026, 0xFFFF, 0, 2 ** 27)
     assert np.array_equal(dumped, want.astype(np.float64)) and int(dumped[25]) == d["counters_fail_qc_reads"]
+    assert d["full"] is True
+
+
+def test_plain_run_prints_the_headline_alone(hip, tmp_path):
+    """Without --full: set-up, warm-up, the timed steps, --dump-outputs and the line -- the same headline keys and numbers
+    that agree with each other, but no CPU baseline, no parity check, no shader clock reading (even with --cpu-seconds
+    given).  What the steps computed is checked here instead, from the dumped counters."""
+    import numpy as np
+
+    import oracle
+    d = run_bench("--dump-outputs", str(tmp_path), full=False)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "parity"):
+        assert k in d, k
+    assert d["unit"] == "Gflags/s" and d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 2
+    assert d["higher_is_better"] is True and d["dtype"] == "u16" and d["value"] > 0
+    r = d["roofline"]
+    assert abs(d["value"] * 2.0 / r["achieved"] - 1.0) < 0.1
+    assert abs(d["ms_per_step"] / r["event_ms_per_launch"] - 1.0) < 0.1
+    assert d["full"] is False and d["cpu_baseline"] is None and d["parity"] == "not checked" and r["sclk_mhz"] is None
+    dumped = np.load(str(tmp_path / "counters.npy"))
+    want = oracle.flagstat_generated(oracle.GEN_UNIFORM, 2026, 0xFFFF, 0, 2 ** 27)
+    assert np.array_equal(dumped, want.astype(np.float64)) and int(dumped[25]) == d["counters_fail_qc_reads"]
+
+
+def test_plain_two_rank_run_leaves_the_per_kernel_figures_to_full(hip):
+    """Without --full an N > 1 run times its steps as --full does, but runs neither the collective alone nor every rank's K1
+    alone: those figures are null, every rank's own step time is still there."""
+    d = run_bench("--gpus", "2", "--same-device", "--backend", "gloo", "--allreduce", "torch", "--cpu-seconds", "0", full=False)
+    c = d["config"]
+    assert d["n_gpus"] == 2 and c["parallelism"] == "shard2" and d["parity"] == "not checked"
+    assert len(c["per_rank_ms"]) == 2 and all(t > 0 for t in c["per_rank_ms"])
+    assert c["allreduce_us"] is None and c["per_rank_k1_alone_ms"] is None
 
 
 def test_multi_gpu_step_at_world_size_one_self_spawned(hip):

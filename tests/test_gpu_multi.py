@@ -242,7 +242,7 @@ def test_two_rccl_ranks_in_two_processes(hip):
     from conftest import ROOT
     for extra in ((), ("--overlap",)):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--flags-per-gpu", str(2 ** 28), "--steps", "10",
-                            "--warmup", "3", "--cpu-seconds", "0", "--probe-reps", "3", *extra],
+                            "--warmup", "3", "--cpu-seconds", "0", "--probe-reps", "3", "--full", *extra],
                            capture_output=True, text=True, timeout=600, cwd=ROOT)
         assert r.returncode == 0, r.stdout + r.stderr
         d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

@@ -5,7 +5,7 @@
 
 Every line is a fresh `bench.py` process (this parent never touches the GPU).  Columns: wall ms per step, event-timed ms
 per step, median step, the delta of the event time over the N = 1 line of the same size in us (the cost of store form + K2 +
-all-reduce), `allreduce_us` (10 all-reduces of a scratch buffer between stream events, untimed part of bench.py), the form
+all-reduce), `allreduce_us` (10 all-reduces of a scratch buffer between stream events, untimed part of bench.py --full), the form
 and who issued the collective.  VERDICT r05 item 1; the budget these numbers are read against is in DESIGN.md "Multi-GPU".
 """
 import argparse
@@ -35,7 +35,7 @@ def run(size, steps, warmup, extra):
             k, v = x[4:].split("=", 1)
             env[k] = v
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--flags-per-gpu", str(size), "--steps", str(steps), "--warmup",
-           str(warmup), "--cpu-seconds", "0"] + [x for x in extra if not x.startswith("ENV:")]
+           str(warmup), "--full", "--cpu-seconds", "0"] + [x for x in extra if not x.startswith("ENV:")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     if r.returncode != 0 or len(lines) != 1:
