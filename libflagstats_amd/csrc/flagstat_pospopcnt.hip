@@ -8,6 +8,10 @@
 // scalar-steered binary-counter chain.  Same load schedule as K1 (non-temporal 16 B/lane loads,
 // waves interleaved at 1 KiB, rolling re-issue, one workgroup per CU), same zero-fill treatment
 // of ragged heads and tails (a zero word has no bits).  HBM-bound: 2 bytes per word.
+//
+// Limit: a wave's totals are uint32 (lane counters, wave_sum_lane63), so one wave may count at most 2^32 - 1 words, i.e. a
+// workgroup about 2^34 words (the cross-wave sum is uint64).  Product grids (at least one workgroup per CU) cannot reach it:
+// that would be 2^34 words per CU, 8 TiB on 256 CUs.  Direct launches on a grid of a few workgroups must stay below it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -96,6 +96,18 @@ def test_two_streams_one_counter_array(hip, knob):
     want = reps * (oracle.flagstat_generated(oracle.GEN_UNIFORM, 1, 0xFFFF, 0, n) +
                    oracle.flagstat_generated(oracle.GEN_NA12878, 2, 1, 0, n))
     assert np.array_equal(out.cpu().numpy().view(np.uint64), want)
+    # the positional popcount's device entry: the same two streams adding into one out[16]
+    pos = torch.full((16,), 5, dtype=torch.int64, device="cuda:0")
+    torch.cuda.synchronize()
+    for _ in range(reps):
+        with torch.cuda.stream(s1):
+            device.pospopcnt_torch(a, pos)
+        with torch.cuda.stream(s2):
+            device.pospopcnt_torch(b[1:], pos)
+    torch.cuda.synchronize()
+    want = reps * (oracle.pospopcnt(oracle.generate(oracle.GEN_UNIFORM, 1, 0xFFFF, 0, n)) +
+                   oracle.pospopcnt(oracle.generate(oracle.GEN_NA12878, 2, 1, 1, n - 1)))
+    assert np.array_equal(pos.cpu().numpy().view(np.uint64), want + np.uint64(5))
 
 
 def test_pinned_host_counters_use_k2(hip, knob):
@@ -116,6 +128,13 @@ def test_pinned_host_counters_use_k2(hip, knob):
         want = oracle.flagstat_generated(oracle.GEN_UNIFORM, 31, 0x0FFF, 0, n)
         live = want != 0
         assert np.array_equal(host[live], want[live] + 3) and (host[~live] == 3).all()
+        # the positional popcount's device entry with pinned-host counters (partials + its finalize launch), at an odd word
+        host[:16] = 11
+        rest = host[16:].copy()
+        _lib.check(hip.FLAGSTATS_hip_device_pospopcnt_u16(d.ptr + 2, n - 1, hp, None), "device pospopcnt(host counters)")
+        _lib.check(hip.FLAGSTATS_hip_synchronize(), "sync")
+        want16 = oracle.pospopcnt(oracle.generate(oracle.GEN_UNIFORM, 31, 0x0FFF, 1, n - 1))
+        assert np.array_equal(host[:16], want16 + np.uint64(11)) and np.array_equal(host[16:], rest)
     finally:
         hip.FLAGSTATS_hip_host_free(hp)
         d.free()

@@ -38,4 +38,32 @@ def test_device_array_longer_than_2_pow_32(hip):
     m = 3 * 65536
     got = d.count(offset=off, n=m)
     assert np.array_equal(got, kat * np.uint64(3))                   # any 65536-aligned-length window of a ramp
+    # the positional popcount on the same array: every bit is set in 32,768 of every 65,536 words of a ramp
+    tail5 = oracle.pospopcnt(np.arange(5, dtype=np.uint16))
+    assert np.array_equal(pospopcnt_device(d.ptr, n), np.uint64(32768 * (65536 + 3)) + tail5)
+    assert np.array_equal(pospopcnt_device(d.ptr + 2 * off, m), np.full(16, 3 * 32768, dtype=np.uint64))
     d.free()
+
+
+def pospopcnt_device(ptr, n):
+    import torch
+    from libflagstats_amd import _lib
+    out = torch.zeros(16, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    _lib.check(_lib.lib().FLAGSTATS_hip_device_pospopcnt_u16(ptr, n, out.data_ptr(), None), "device pospopcnt")
+    torch.cuda.synchronize()
+    return out.cpu().numpy().view(np.uint64)
+
+
+def test_pospopcnt_host_array_past_2_pow_32(hip):
+    """STORM_pospopcnt_u16 keeps the reference's uint32 out[16] (python/libalgebra.h:3496): on 2^32 + 5 all-ones words every
+    count wraps to 5.  The 64-bit entry returns 2^32 + 5."""
+    from libflagstats_amd import _lib
+    n = 2 ** 32 + 5
+    a = np.full(n, 0xFFFF, dtype=np.uint16)
+    raw = np.full(16, 0xDEADBEEF, dtype=np.uint32)
+    assert hip.STORM_pospopcnt_u16(a.ctypes.data, n, raw.ctypes.data) == 0
+    assert (raw == 5).all(), raw
+    wide = np.zeros(16, dtype=np.uint64)
+    _lib.check(hip.FLAGSTATS_hip_pospopcnt_u16_x64(a.ctypes.data, n, wide.ctypes.data), "pospopcnt x64")
+    assert (wide == n).all(), wide

@@ -7,10 +7,28 @@ import numpy as np
 import pytest
 
 from conftest import case_input, inmemory_input, load_golden
+from steps_oracle import periodic_pospopcnt
 
 pytestmark = pytest.mark.gpu
 
 U64 = np.uint64
+RAMP = np.arange(65536, dtype=np.uint32).astype(np.uint16)   # GEN_RAMP with seed 0: x[i] = i mod 2^16
+
+
+def pospopcnt_device(hip, ptr, n, epilogue):
+    """FLAGSTATS_hip_device_pospopcnt_u16 into a zeroed device out[16] under the given `epilogue` knob, synchronous"""
+    import torch
+    from libflagstats_amd import _lib
+    old = hip.FLAGSTATS_hip_get(b"epilogue")
+    _lib.check(hip.FLAGSTATS_hip_set(b"epilogue", epilogue), "set epilogue")
+    try:
+        out = torch.zeros(16, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        _lib.check(hip.FLAGSTATS_hip_device_pospopcnt_u16(ptr, n, out.data_ptr(), None), "device pospopcnt")
+        torch.cuda.synchronize()
+        return out.cpu().numpy().view(np.uint64)
+    finally:
+        hip.FLAGSTATS_hip_set(b"epilogue", old)
 
 
 def capi_u16(hip, a, flags=None):
@@ -147,6 +165,12 @@ def test_any_grid_size(hip, bpc):
         d = device.DeviceFlags(n).generate(device.GEN_NA12878, seed=5, mask=1)
         want = oracle.flagstat_generated(oracle.GEN_NA12878, 5, 1, 0, n)
         assert np.array_equal(d.count(), want)
+        # the positional popcount's device entry at the same geometry, both epilogue forms, on a ramp (closed form)
+        d.generate(device.GEN_RAMP, seed=0)
+        for off, cnt in ((0, n), (3, n - 11)):
+            for epilogue in (1, 0):
+                got = pospopcnt_device(hip, d.ptr + 2 * off, cnt, epilogue)
+                assert np.array_equal(got, periodic_pospopcnt(RAMP, off, off + cnt)), (bpc, off, epilogue)
         d.free()
     finally:
         hip.FLAGSTATS_hip_set(b"blocks_per_cu", old)
@@ -165,6 +189,14 @@ def test_multi_epoch_single_workgroup_column(hip):
         d = device.DeviceFlags(n).generate(device.GEN_UNIFORM, seed=1234, mask=0xFFFF)
         want = oracle.flagstat_generated(oracle.GEN_UNIFORM, 1234, 0xFFFF, 0, n)
         assert np.array_equal(d.count(), want)
+        # the positional popcount through the device entry: 600+ steps per workgroup too, both epilogue forms, on a ramp
+        # that starts at 7 (closed form: no multi-GiB host copy)
+        d.generate(device.GEN_RAMP, seed=7)
+        ramp7 = np.roll(RAMP, -7)
+        for epilogue in (1, 0):
+            assert np.array_equal(pospopcnt_device(hip, d.ptr, n, epilogue), periodic_pospopcnt(ramp7, 0, n)), epilogue
+            got = pospopcnt_device(hip, d.ptr + 2 * 5, n - 9, epilogue)
+            assert np.array_equal(got, periodic_pospopcnt(ramp7, 5, n - 4)), epilogue
         d.free()
     finally:
         hip.FLAGSTATS_hip_set(b"blocks_per_cu", old)
@@ -193,10 +225,17 @@ def test_host_streaming_chunks_and_pinned(hip):
     want = oracle.flagstat_hist(a)
     old = hip.FLAGSTATS_hip_get(b"chunk_flags")
     try:
+        pos_start = np.arange(1000, 1016, dtype=np.uint64)
         for chunk in (1_000_003, 65536, old):
             _lib.check(hip.FLAGSTATS_hip_set(b"chunk_flags", chunk), "set chunk")
             assert np.array_equal(capi_x64(hip, a), want), chunk
             assert np.array_equal(capi_x64(hip, a[1:]), oracle.flagstat_hist(a[1:])), chunk
+            # the positional popcount's host entry through the same chunks (both staging slots, a partial last chunk, an odd
+            # host offset), added onto counters that already hold values
+            for lo in (0, 1):
+                out = pos_start.copy()
+                _lib.check(hip.FLAGSTATS_hip_pospopcnt_u16_x64(a[lo:].ctypes.data, a.size - lo, out.ctypes.data), "pos x64")
+                assert np.array_equal(out, pos_start + oracle.pospopcnt(a[lo:])), (chunk, lo)
         # pinned host memory from the library's allocator
         p = hip.FLAGSTATS_hip_host_alloc(a.nbytes)
         assert p
@@ -204,6 +243,9 @@ def test_host_streaming_chunks_and_pinned(hip):
         out = np.zeros(32, dtype=np.uint64)
         _lib.check(hip.FLAGSTATS_u16_x64(p, a.size, out.ctypes.data), "x64 pinned")
         assert np.array_equal(out, want)
+        out = pos_start.copy()
+        _lib.check(hip.FLAGSTATS_hip_pospopcnt_u16_x64(p + 2, a.size - 1, out.ctypes.data), "pos x64 pinned")
+        assert np.array_equal(out, pos_start + oracle.pospopcnt(a[1:]))
         hip.FLAGSTATS_hip_host_free(p)
     finally:
         hip.FLAGSTATS_hip_set(b"chunk_flags", old)

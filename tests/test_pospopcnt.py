@@ -56,7 +56,9 @@ def test_gpu_device_entry_large_and_ragged(hip, epilogue):
 
 
 def _device_entry_large_and_ragged(torch, oracle, device):
-    n = 300_000_007                                          # > one epoch per workgroup, ragged tail
+    # 18,311 steps of 16,384 words: 71-72 per workgroup on 256 CUs, well short of an epoch (255); the epoch flushes are
+    # test_gpu_epoch_regimes.py's.  Ragged tail.
+    n = 300_000_007
     t = torch.empty(n + 8, dtype=torch.int16, device="cuda:0")
     device.generate_torch(t, device.GEN_UNIFORM, seed=77, mask=0xFFFF)
     host = None
