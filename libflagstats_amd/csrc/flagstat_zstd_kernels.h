@@ -44,7 +44,8 @@ constexpr uint32_t kZstdWindow = FLAGSTAT_ZSTD_WINDOW;
 // the host decodes such a file with libzstd.
 enum {
     kZstdOk = 0,
-    kZstdBadHeader = 1,        // frame header damaged / content size differs from the declared block size
+    kZstdBadHeader = 1,        // frame header damaged / content size differs from the declared block size (a smaller one with bytes
+                               // behind the frame's last block is kZstdTrailingData: several frames in one payload)
     kZstdBadBlock = 2,         // block header: reserved type, size past the payload
     kZstdBadLiterals = 3,      // literals section: sizes past the block, stream table, Huffman stream not consumed exactly
     kZstdBadHuffman = 4,       // Huffman tree description

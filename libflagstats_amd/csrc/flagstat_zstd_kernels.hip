@@ -493,8 +493,29 @@ __global__ __launch_bounds__(64) void zstd_prepare(const uint8_t* __restrict__ c
                 uint64_t content = 0;
                 for (uint32_t i = 0; i < fcs_bytes; ++i) content |= static_cast<uint64_t>(frame[p + i]) << (8u * i);
                 if (fcs_bytes == 2u) content += 256u;
-                if (content != dst_len) fail(kZstdBadHeader);
                 p += fcs_bytes;
+                if (content != dst_len) {
+                    // A frame that says it is SMALLER than the payload's declared size and has bytes behind its last block is the
+                    // first of several frames in one payload: valid Zstandard that is not taken, not damage.  Only the block
+                    // headers are walked to see where it ends (every step moves on by three bytes at least).
+                    bool whole = content < dst_len, fin = false;
+                    uint32_t q = p;
+                    while (whole && !fin) {
+                        if (q + 3u > n) {
+                            whole = false;
+                            break;
+                        }
+                        const uint32_t bh = ld_le24(frame + q);
+                        const uint32_t type = (bh >> 1) & 3u, size = bh >> 3;
+                        const uint32_t span = type == 1u ? 1u : size;
+                        fin = bh & 1u;
+                        if (type == 3u || size > kBlockMax || q + 3u + span > n)
+                            whole = false;
+                        else
+                            q += 3u + span;
+                    }
+                    fail(whole && q < n ? kZstdTrailingData : kZstdBadHeader);
+                }
             }
         }
     }

@@ -19,6 +19,7 @@ import numpy as np  # noqa: E402
 import blockfile_tool as bt  # noqa: E402
 from libflagstats_amd import _lib  # noqa: E402
 from zstd_kernel_check import decode_frames  # noqa: E402
+from zstd_frame_writer import random_frame  # noqa: E402
 from zstd_fuzz_gen import compress_with_parameters, damage, synthetic  # noqa: E402
 
 
@@ -34,6 +35,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seeds", type=int, default=200)
     ap.add_argument("--first", type=int, default=0)
+    ap.add_argument("--shapes", action="store_true", help="frames from tests/zstd_frame_writer.random_frame (valid Zstandard no compressor "
+                    "writes: every form, lengths and distances at the kernels' boundaries) instead of libzstd-compressed payloads")
     args = ap.parse_args()
     lib = _lib.lib()
     _lib.check(lib.FLAGSTATS_hip_init(0), "init")
@@ -46,11 +49,15 @@ def main():
         for seed in range(s0, min(s0 + batch, args.first + args.seeds)):
             rng = random.Random(seed)
             nrng = np.random.default_rng(seed)
-            raw = synthetic(rng, nrng)
-            level = rng.choice([1, 1, 2, 3, 5, 7, 9, 12, 15, 19, -1, -5])
-            comp = compress_with_parameters(z, rng, raw) if seed % 3 == 2 else None
-            if comp is None:
-                comp = bt.compress_block(raw, "zstd", level)
+            if args.shapes:
+                comp, raw = random_frame(rng)
+                assert ref_decode(z, comp, len(raw)) == raw, "seed %d: libzstd does not decode the writer's frame to the writer's bytes" % seed
+            else:
+                raw = synthetic(rng, nrng)
+                level = rng.choice([1, 1, 2, 3, 5, 7, 9, 12, 15, 19, -1, -5])
+                comp = compress_with_parameters(z, rng, raw) if seed % 3 == 2 else None
+                if comp is None:
+                    comp = bt.compress_block(raw, "zstd", level)
             frames.append(comp)
             sizes.append(len(raw))
             raws.append(raw)
@@ -94,8 +101,8 @@ def main():
                 differ += 1
                 print("DIFFER: seed %d (damaged frame %d)" % (s0 + i // 3, i), flush=True)
         print("seeds %d..%d done: %d exact so far" % (s0, min(s0 + batch, args.first + args.seeds) - 1, exact), flush=True)
-    print("%d synthetic frames (a third of them from ZSTD_compress2 with random advanced parameters): %d exact (%d of them in the second pass over frames of many blocks), %d not taken (status >= 64), %d wrong | %d damaged frames: both reject %d, both accept with equal bytes %d, GPU stricter %d, GPU more lenient %d, different bytes %d" % (
-        exact + wrong + unsupported, exact, second_pass, unsupported, wrong, both_ok + both_fail + strict + lenient + differ, both_fail, both_ok, strict, lenient, differ))
+    print("%d synthetic frames (%s): %d exact (%d of them in the second pass over frames of many blocks), %d not taken (status >= 64), %d wrong | %d damaged frames: both reject %d, both accept with equal bytes %d, GPU stricter %d, GPU more lenient %d, different bytes %d" % (
+        exact + wrong + unsupported, "hand-written shapes" if args.shapes else "a third of them from ZSTD_compress2 with random advanced parameters", exact, second_pass, unsupported, wrong, both_ok + both_fail + strict + lenient + differ, both_fail, both_ok, strict, lenient, differ))
     return 1 if wrong or lenient or differ else 0
 
 

@@ -306,6 +306,132 @@ def test_zstd_decode_is_byte_exact_on_a_slice_of_the_fuzzer(hip):
     assert both_ok + both_bad + strict == 900 and both_bad > 300
 
 
+# ----------------------------------------------------------------------------- Zstandard: frames no compressor writes
+# Everything above came out of libzstd's compressor, so it has the forms, lengths and distances that compressor chooses.  The
+# frames below are written by tests/zstd_frame_writer.py from a description (tests/test_zstd_writer_host.py holds that writer
+# against libzstd on the CPU): every form of the format, and exact numbers on the execution kernel's own boundaries.  The
+# contract is strict: status 0 and libzstd's bytes, which are the writer's; no "not taken" code, these forms are not on the
+# list of exceptions in flagstat_zstd_kernels.h.
+def run_written(hip, frames, what, batch=48):
+    """frames: (name, frame, decoded bytes) from the test-only writer"""
+    for at in range(0, len(frames), batch):
+        part = frames[at:at + batch]
+        names = [name for name, _, _ in part]
+        try:
+            wants = run_and_compare(hip, "zstd", [(f, len(w)) for _, f, w in part], what, popcnt_every=3)
+        except AssertionError as e:
+            i = next((a for a in e.args[0] if isinstance(a, int)), None) if e.args and isinstance(e.args[0], tuple) else None
+            raise AssertionError("%s (frames of this launch: %s)%s" % (e, names, "" if i is None else " -- frame: " + names[i]))
+        for name, want, (_, _, own) in zip(names, wants, part):
+            assert want == own, (name, "libzstd's bytes are not the writer's")
+
+
+@pytest.mark.parametrize("family", ["header", "literals", "huffman", "sequences", "tables", "repeats", "mixed"])
+def test_zstd_decode_is_byte_exact_on_hand_written_forms(hip, family):
+    """header forms; literals raw / RLE / Huffman / treeless in every size format, one stream and four; Huffman trees of depth 1..11
+    as direct and as FSE-compressed weights; sequence counts in one, two and three bytes; predefined, RLE, FSE (every accuracy
+    log) and repeat mode for each table; the six repeat-offset cases from a known and from a carried history; frames of twelve
+    blocks that mix them"""
+    import zstd_frame_writer as fw
+    assert list(fw.FAMILIES) == ["header", "literals", "huffman", "sequences", "tables", "repeats", "mixed"]
+    run_written(hip, fw.FAMILIES[family](), ("hand-written", family))
+
+
+@pytest.mark.parametrize("family", ["runs", "near", "far", "huge", "seams", "boundaries", "dense", "literal_use"])
+def test_zstd_decode_is_byte_exact_on_the_kernels_own_boundaries(hip, family):
+    """literal runs and matches of k * 16383 + {-1, 0, 1}, 65535, 65536 and a whole block; offsets 1..8 round the ring; offsets at
+    the ring's reach (32 KiB), its size (36 KiB), 64 KiB, 128 KiB, 256 KiB; 3 MiB reaching back to the first byte; sources that end at,
+    before and behind the start of the record that copies them; matches and literal runs across blocks; the densest bit
+    streams the format has; all literals used and none.  (Blocks of 63..65, 127..129 and 0x7EFF..0x7F01 sequences: "sequences" above.)"""
+    import zstd_frame_writer as fw
+    assert list(fw.GEOMETRY) == ["runs", "near", "far", "huge", "seams", "boundaries", "dense", "literal_use"]
+    run_written(hip, fw.GEOMETRY[family](), ("geometry", family), batch=24)
+
+
+def test_zstd_decode_declines_valid_frames_beyond_its_limits_by_name(hip):
+    """Valid Zstandard that flagstat_zstd_kernels.h says the decoder does not take -- a content checksum, a dictionary ID field,
+    a skippable frame in front, a second frame behind, more than 64 MiB: libzstd decodes each, the decoder answers with the code
+    for it.  Where two limits apply (64 MiB + 2 bytes in 513 RLE blocks: too large, and too many blocks) either code is right.
+    Never status 0 with other bytes, never a damage code (1..63)."""
+    import zstd_frame_writer as fw
+    seen = set()
+    for name, frame, want, codes in fw.limit_frames():
+        assert du.ref_zstd(frame, len(want)) == want, name
+        with du.DeviceDecode(hip, "zstd", [frame], [len(want)]) as dd:
+            st = int(dd.status[0])
+            print("%s: status %d" % (name, st))
+            if st == 0:
+                du.check_decoded(dd, 0, want, name)
+            assert st in codes, (name, st, "allowed", codes)
+            seen.add(st)
+    assert {64, 65, 66, 68} <= seen and seen & {67, 69}
+
+
+def test_zstd_decode_takes_a_hand_written_frame_of_many_blocks_in_the_second_pass(hip):
+    """60 small blocks of every kind, trees, tables and offset history carried from block to block: the first-pass entry may answer
+    "too many blocks" (12 slots for a frame this small), never wrong bytes; with a slot per block it decodes them byte for byte"""
+    import zstd_frame_writer as fw
+    rng = random.Random(5)
+    abc = bytes(rng.sample(range(129), 30))
+    w = fw.FrameWriter().raw(rng.randbytes(500))
+    w.compressed(bytes(rng.choices(abc, k=400)), [(3, 9, 100), (0, 4, 7)], lit="huf", streams=4, tree=fw.tree_for(abc, 7, rng), describe="fse",
+                 modes=("fse", "fse", "fse"), logs=(9, 8, 9), low=fw.EVERY_CODE)
+    for k in range(58):
+        if k % 7 == 3:
+            w.raw(rng.randbytes(k))
+        elif k % 7 == 5:
+            w.rle(k, 100 * k)
+        else:
+            seqs = [(rng.randrange(1, 4), rng.randrange(3, 30), rng.choice([-1, -2, -3, rng.randrange(1, 500)])) for _ in range(1 + k % 5 * 20)]
+            w.compressed(bytes(rng.choices(abc, k=sum(s[0] for s in seqs) + 8)), seqs, lit=("treeless", "huf")[k % 11 == 0], tree=fw.tree_for(abc, 5 + k % 6, rng),
+                         describe=("direct", "fse")[k % 2], streams=(1, 4)[k % 2], modes=(("repeat",) * 3, ("repeat", "predef", "fse"))[k % 4 == 0], low=fw.EVERY_CODE)
+    frame, want = w.finish()
+    assert len(w.body) == 60 and du.ref_zstd(frame, len(want)) == want
+    with du.DeviceDecode(hip, "zstd", [frame], [len(want)]) as dd:
+        if dd.status[0] == 0:
+            du.check_decoded(dd, 0, want, "60 blocks")
+        else:
+            assert dd.status[0] == 67, int(dd.status[0])
+    with du.DeviceDecode(hip, "zstd", [frame], [len(want)], min_blocks=64) as dd:
+        du.check_decoded(dd, 0, want, "60 blocks, second pass")
+        assert np.array_equal(dd.pospopcnt(0), du.pospopcnt_ref(want))
+
+
+def zstd_shape_fuzz_slice(hip, first, count, batch=50):
+    """zstd_frame_writer.random_frame over a seed range: every frame exact (no "not taken": at most 12 blocks each), two damaged
+    variants per frame under the rule of zstd_fuzz_slice; returns (exact, both accept, both reject, GPU stricter)"""
+    import zstd_frame_writer as fw
+    from zstd_fuzz_gen import damage
+    exact = both_ok = both_bad = strict = 0
+    for s0 in range(first, first + count, batch):
+        frames, damaged = [], []
+        for seed in range(s0, min(s0 + batch, first + count)):
+            rng = random.Random(seed)
+            frame, want = fw.random_frame(rng)
+            frames.append(("shape fuzz seed %d" % seed, frame, want))
+            damaged += [(damage(rng, frame), len(want)) for _ in range(2)]
+        run_written(hip, frames, ("shape fuzz seeds from", s0), batch=batch)
+        exact += len(frames)
+        with du.DeviceDecode(hip, "zstd", [p for p, _ in damaged], [n for _, n in damaged]) as dd:
+            for i, (p, n) in enumerate(damaged):
+                want = du.ref_zstd(p, n)
+                if dd.status[i] == 0:
+                    assert want is not None, ("seed", s0 + i // 2, "libzstd rejects, the GPU decoder accepts")
+                    du.check_decoded(dd, i, want, ("damaged, seed", s0 + i // 2))
+                    both_ok += 1
+                elif want is None:
+                    both_bad += 1
+                else:
+                    strict += 1
+    return exact, both_ok, both_bad, strict
+
+
+def test_zstd_decode_is_byte_exact_on_a_slice_of_the_shape_fuzzer(hip):
+    exact, both_ok, both_bad, strict = zstd_shape_fuzz_slice(hip, 0, 300)
+    print("shape fuzz: %d exact; damaged: both accept %d, both reject %d, GPU stricter %d" % (exact, both_ok, both_bad, strict))
+    assert exact == 300 and both_ok + both_bad + strict == 600
+
+
 def test_decoders_write_nothing_outside_their_blocks(hip):
     """Blocks of every length mod 16 packed back to back in 16-byte slots: each slot's slack (and an odd last byte) still
     holds the fill pattern after the launch -- a decoder that stores a vector too far would hit its neighbour."""

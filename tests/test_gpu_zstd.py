@@ -439,6 +439,60 @@ def test_a_frame_the_gpu_decoder_does_not_take_in_a_later_segment_sends_the_whol
         assert hip.FLAGSTATS_hip_set(b"zstd_gpu_min_bytes", 64 << 20) == 0
 
 
+def _limit_cases():
+    import zstd_frame_writer as fw
+    return fw.limit_frames()
+
+
+@pytest.mark.parametrize("which", range(10))
+def test_valid_frames_beyond_the_gpu_decoders_limits_go_to_libzstd(hip, which):
+    """A frame the GPU decoder declares it does not take (content checksum, dictionary ID field, skippable frame in front, second
+    frame behind, more than 64 MiB: tests/zstd_frame_writer.limit_frames, each decoded by libzstd) among ordinary frames in one
+    block image: with the decoder chosen by size the file goes to libzstd and the counters are the oracle's; forced onto the GPU
+    the call fails with a message and leaves the caller's counters untouched.
+    (The host pipeline gives a block a chunk of its own up to the knob "chunk_flags", 64 MiB as shipped -- the very size the GPU
+    decoder stops at; for the frame above it the knob is raised to 80 MiB, as a caller with such blocks has to.)"""
+    import oracle
+    from libflagstats_amd import blockfile
+    cases = _limit_cases()
+    assert len(cases) == 10
+    name, frame, want, codes = cases[which]
+    plain = [oracle.generate(oracle.GEN_NA12878, 120 + i, 1, 0, 150000).tobytes() for i in range(2)]
+    img = image_of(plain[:1], 1) + struct.pack("<ii", len(want), len(frame)) + frame + image_of(plain[1:], 3)
+    expected = expect_blocks([plain[0], want, plain[1]])
+    assert hip.FLAGSTATS_hip_get(b"zstd_decoder") == 2
+    assert hip.FLAGSTATS_hip_set(b"zstd_gpu_min_bytes", 1) == 0
+    old_chunk = hip.FLAGSTATS_hip_get(b"chunk_flags")
+    try:
+        if len(want) > 2 * old_chunk:
+            assert hip.FLAGSTATS_hip_set(b"chunk_flags", 40 << 20) == 0
+        got, st = blockfile.flagstat_zstd_image(img, 2)
+        assert st["gpu_decode"] == 0 and np.array_equal(got, expected), name
+        assert hip.FLAGSTATS_hip_set(b"zstd_decoder", 1) == 0
+        out = np.full(32, 7, dtype=np.uint64)
+        buf = (ctypes.c_char * len(img)).from_buffer_copy(img)
+        rc = hip.FLAGSTATS_hip_blockimage_zstd(buf, len(img), 2, out.ctypes.data, None)
+        assert rc != 0 and b"Zstandard" in hip.FLAGSTATS_hip_last_error(), name
+        assert (out == 7).all(), name
+    finally:
+        assert hip.FLAGSTATS_hip_set(b"chunk_flags", old_chunk) == 0
+        assert hip.FLAGSTATS_hip_set(b"zstd_decoder", 2) == 0
+        assert hip.FLAGSTATS_hip_set(b"zstd_gpu_min_bytes", 64 << 20) == 0
+
+
+def test_gpu_zstd_decoder_on_hand_written_frames(zgpu):
+    """One block image of every hand-written frame (tests/zstd_frame_writer.py: the format's forms, the execution kernel's
+    boundaries) through the orchestration with the GPU decoder forced: the counters of the writer's own expected bytes."""
+    import zstd_frame_writer as fw
+    from libflagstats_amd import blockfile
+    frames = fw.form_corpus() + fw.geometry_corpus()
+    assert len(frames) > 500
+    img = b"".join(struct.pack("<ii", len(want), len(frame)) + frame for _, frame, want in frames)
+    got, st = blockfile.flagstat_zstd_image(img, 2)
+    assert st["gpu_decode"] == 1 and st["n_blocks"] == len(frames)
+    assert np.array_equal(got, expect_blocks([want for _, _, want in frames]))
+
+
 def test_zstd_scratch_that_does_not_fit_makes_smaller_pieces(zgpu, monkeypatch):
     """the scratch between the kernels (8.5 MB per frame in flight and decode stream) is what a busy device runs out
     of first; a failed scratch allocation halves the frames per launch instead of giving the file up.  Forced here with a

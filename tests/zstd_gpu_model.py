@@ -99,9 +99,23 @@ def entropy_stage(frame, dst_len):
         raise Fail(BAD_HEADER)
     if fcs_bytes:
         content = int.from_bytes(frame[p:p + fcs_bytes], "little") + (256 if fcs_bytes == 2 else 0)
-        if content != dst_len:
-            raise Fail(BAD_HEADER)
         p += fcs_bytes
+        if content != dst_len:
+            # smaller than the declared size, with bytes behind its last block: the first of several frames in one payload
+            # (valid, not taken); anything else is damage.  Only the block headers are walked.
+            whole, fin, q = content < dst_len, False, p
+            while whole and not fin:
+                if q + 3 > n:
+                    whole = False
+                    break
+                bh = int.from_bytes(frame[q:q + 3], "little")
+                fin, btype, size = bool(bh & 1), (bh >> 1) & 3, bh >> 3
+                span = 1 if btype == 1 else size
+                if btype == 3 or size > zm.BLOCK_MAX or q + 3 + span > n:
+                    whole = False
+                else:
+                    q += 3 + span
+            raise Fail(TRAILING if whole and q < n else BAD_HEADER)
     recs = [0] * lay["rec_stride"]
     ck = [[0, 0, 0] for _ in range(lay["ck_stride"])]
     lits = bytearray(lay["lit_stride"])
