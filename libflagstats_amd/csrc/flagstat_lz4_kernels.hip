@@ -104,6 +104,12 @@ __device__ void lz4wg_walk(WgLds& L, const uint8_t* __restrict__ src, const uint
                            const uint32_t lane, unsigned long long* __restrict__ tally)
 {
     uint32_t ip = 0, ip_r = 0, in_hi = 0, in_hi_r = 0, err = 0, nrec = 0, tail_seen = 0, op = 0;
+    // liblz4's end-of-block rules (LZ4_decompress_safe refuses anything else, and so does the host decoder): the block ends
+    // with a literals-only sequence; behind a match that run has at least 5 bytes; the last match starts at least 12 bytes
+    // before the end.  Where the last match starts is known when the literals-only sequence comes: the scalar code notes it
+    // for its own sequences, and a tile that ends within 12 input bytes of the block's end notes its last member's.
+    uint32_t m_start = 0xFFFFFFFFu;  // output position of the last match noted (none yet)
+    bool ended = false;              // the literals-only sequence has been seen
     unsigned long long t_wait = 0, n_win = 0, n_seq = 0, n_tile = 0, t_dp = 0, t_chain = 0, t_reach = 0, t_push = 0, t_mark = 0;
     auto tock = [&](unsigned long long& acc) {
         if (PROF) {
@@ -165,6 +171,7 @@ __device__ void lz4wg_walk(WgLds& L, const uint8_t* __restrict__ src, const uint
         ++n_seq;
         cover(96u);
         const uint32_t token = inb();
+        const bool first = ip == 0u;
         advance(1u);
         uint32_t ll = token >> 4;
         if (ll == 15u) {
@@ -180,6 +187,10 @@ __device__ void lz4wg_walk(WgLds& L, const uint8_t* __restrict__ src, const uint
             } while (e == 255u);
         }
         if (ll > iend - ip || ll > oend - op) { err = 2; return; }
+        if (ll == iend - ip) {  // the literals-only sequence: the end rules
+            ended = true;
+            if (!first && (ll < 5u || (m_start != 0xFFFFFFFFu && op + ll - m_start < 12u))) { err = 11; return; }
+        }
         while (ll > 64u) {
             cover(96u);
             if (!push(REC_SEQ, op, ip_r | (64u << 24), 0u, 0u)) { err = 8; return; }
@@ -220,6 +231,7 @@ __device__ void lz4wg_walk(WgLds& L, const uint8_t* __restrict__ src, const uint
         }
         ml += 4u;
         if (ll + ml > oend - op) { err = 5; return; }
+        m_start = op + ll;
         if (!push(REC_SEQ, op, lit_at | (ll << 24), off, ml)) err = 8;
         op += ll + ml;
     };
@@ -405,12 +417,23 @@ __device__ void lz4wg_walk(WgLds& L, const uint8_t* __restrict__ src, const uint
         }
         if (PROF) n_win += nw;
         op += tile_out;
+        if (iend - (ip + adv) <= 12u) {
+            // the tile's last member may hold the block's last match (a final run of 11 literals or fewer is all that can
+            // follow): where it starts, for the end rules.  Its output ends where the tile's does.  Once per block.
+            const uint32_t i = members ? 31u - static_cast<uint32_t>(__builtin_clz(members)) : 0u;
+            const uint32_t tk = L.inw[base + i];
+            const uint32_t mlc = tk & 15u;
+            const uint32_t ml = mlc == 15u ? 19u + static_cast<uint32_t>(L.inw[base + i + 3u + (tk >> 4)]) : mlc + 4u;  // (inside the mirror, as above)
+            const uint64_t hasm = __builtin_amdgcn_ballot_w64(members != 0u);
+            if (hasm) m_start = op - __builtin_amdgcn_readlane(ml, 63u - static_cast<uint32_t>(__builtin_clzll(hasm)));
+        }
         tock(t_push);
         advance(adv);
         if (slow) slow_sequence();
     }
     while (!err && ip < iend) slow_sequence();
     if (!err && (ip != iend || op != oend)) err = 6;
+    if (!err && !ended) err = 11;  // (the block ends in a match)
     if (err) wg_st(&L.err, err);
     if (!err)
         for (uint32_t i = 0; i < kWgEmit; ++i) (void)push(REC_END, op, 0u, 0u, 0u);  // one for each emitter
@@ -659,6 +682,9 @@ __global__ __launch_bounds__(64) void lz4_decode_wave(const uint8_t* __restrict_
     const uint32_t lane = threadIdx.x;
     uint32_t ip = 0, op = 0, in_base = 0, in_valid = 0, flushed = 0;
     uint32_t err = 0, nseq = 0, nfar = 0;
+    // liblz4's end-of-block rules, as in lz4_decode_wg: where the last match starts, and whether the literals-only sequence came
+    uint32_t m_start = 0xFFFFFFFFu;
+    bool ended = false;
     // PROF: wave cycles per phase (s_memtime), summed over all waves into tally[2..]
     unsigned long long n_pass = 0, n_single = 0, t_lit = 0, n_lit = 0, t_copy = 0, t_far = 0, t_slow = 0, t_flush = 0, t_cover = 0, t_parse = 0, n_batch = 0, n_slow = 0, t_mark = 0;
     auto tick = [&]() { if (PROF) t_mark = __builtin_readcyclecounter(); };
@@ -802,7 +828,10 @@ __global__ __launch_bounds__(64) void lz4_decode_wave(const uint8_t* __restrict_
                 lds[wa] = static_cast<uint8_t>(d);
                 k0 = k1;
             }
-            if (nb) op = __builtin_amdgcn_readlane(endk, nb - 1u);
+            if (nb) {
+                op = __builtin_amdgcn_readlane(endk, nb - 1u);
+                m_start = __builtin_amdgcn_readlane(opk, nb - 1u);
+            }
             tock(t_copy);
             ip += 3u * nb;
             nseq += nb;
@@ -822,6 +851,7 @@ __global__ __launch_bounds__(64) void lz4_decode_wave(const uint8_t* __restrict_
             if (lane < ll) ring[(op + lane) & kRingMask] = static_cast<uint8_t>(lb);
             op += ll;
             if (offq == 0u || offq > op) { err = 5; break; }
+            m_start = op;
             if (offq <= RING - 64u) {
                 uint32_t m = __builtin_amdgcn_readlane(magic, offq & 63u);
                 if (offq >= 64u) m = 0;
@@ -861,6 +891,10 @@ __global__ __launch_bounds__(64) void lz4_decode_wave(const uint8_t* __restrict_
             if (err) break;
         }
         if (ll > iend - ip || ll > oend - op) { err = 2; break; }
+        if (ll == iend - ip) {  // the literals-only sequence: at least 5 behind a match, which starts 12 or more before the end
+            ended = true;
+            if (m_start != 0xFFFFFFFFu && (ll < 5u || op + ll - m_start < 12u)) { err = 11; break; }
+        }
         const bool bare = ll == 0;
         while (ll) {
             const uint32_t n = ll < 64 ? ll : 64;
@@ -897,6 +931,7 @@ __global__ __launch_bounds__(64) void lz4_decode_wave(const uint8_t* __restrict_
         }
         ml += 4;
         if (off == 0 || off > op || ml > oend - op) { err = 5; break; }
+        m_start = op;
         const bool near = off <= RING - 64;
         nfar += near ? 0u : 1u;
         while (ml) {
@@ -918,6 +953,7 @@ __global__ __launch_bounds__(64) void lz4_decode_wave(const uint8_t* __restrict_
         tock(t_slow);
     }
     if (!err && op != oend) err = 6;
+    if (!err && !ended) err = 11;  // (the block ends in a match, or holds no sequence at all)
     // tail of the ring.  An odd trailing byte of a block is dropped like the reference's N = size >> 1
     // (benchmark/flagstats.cpp:323): it stays zero in the padded slot, so the counting kernel sees no stray flag.
     if (!err) {

@@ -258,11 +258,13 @@ inline int64_t lz4_block_decode(const uint8_t* src, size_t n, uint8_t* dst, size
         }
         ip += lit;
         op += lit;
-        if (ip == iend) {  // last sequence carries literals only
+        if (ip == iend) {  // last sequence carries literals only; behind a match it has at least 5 (liblz4: LASTLITERALS)
+            if (lit < 5 && ip - lit - 1 != src) return -1;
             s.op = op;
             break;
         }
         if (iend - ip < 2) return -1;
+        if (static_cast<size_t>(oend - op) < 12) return -1;  // a match starts at least 12 bytes before the end (liblz4: MFLIMIT)
         const size_t off = static_cast<size_t>(ip[0]) | (static_cast<size_t>(ip[1]) << 8);
         ip += 2;
         if (off == 0 || off > static_cast<size_t>(op - dst)) return -1;
@@ -276,7 +278,7 @@ inline int64_t lz4_block_decode(const uint8_t* src, size_t n, uint8_t* dst, size
             } while (b == 255);
         }
         ml += 4;
-        if (ml > static_cast<size_t>(oend - op)) return -1;
+        if (ml + 5 > static_cast<size_t>(oend - op)) return -1;  // (... and ends at least 5 before it)
         const uint8_t* m = op - off;
         if (off >= 16 && static_cast<size_t>(oend - op) >= ml + 16) {
             // non-overlapping at 16-byte granularity: wild copy in 16-byte steps

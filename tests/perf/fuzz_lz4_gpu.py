@@ -22,10 +22,22 @@ from libflagstats_amd import _lib, blockfile  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seeds", type=int, default=150)
+    ap.add_argument("--shapes", action="store_true", help="blocks from tests/lz4_block_writer.random_block (tokens, matches and literal "
+                    "runs on the kernels' boundaries) instead: both kernels, byte for byte against liblz4, two damaged variants a block")
     args = ap.parse_args()
     import oracle
     lib = _lib.lib()
     _lib.check(lib.FLAGSTATS_hip_init(0), "init")
+    if args.shapes:
+        for kernel, name in ((0, "workgroup kernel"), (1, "wave-per-block kernel")):
+            tot = [0, 0, 0, 0]
+            for s0 in range(0, args.seeds, 50):
+                r = tdb.lz4_shape_fuzz_slice(lib, kernel, s0, min(50, args.seeds - s0))
+                tot = [a + b for a, b in zip(tot, r)]
+                print("%s: seeds to %d done" % (name, s0 + 50), flush=True)
+            print("shapes, %s: %d placed blocks byte-exact against liblz4; damaged: %d decode to liblz4's bytes, %d rejected by both, %d refused "
+                  "by the GPU decoder only, none accepted that liblz4 rejects" % (name, tot[0], tot[1], tot[2], tot[3]))
+        return
     _lib.check(lib.FLAGSTATS_hip_set(b"lz4_decoder", 1), "set")
     blocks = damaged_ok = damaged_rejected = 0
     bytes_level = [[0, 0, 0, 0], [0, 0, 0, 0]]   # per kernel: blocks byte-exact, damaged: both accept / both reject / GPU stricter than liblz4

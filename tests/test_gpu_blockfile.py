@@ -402,6 +402,40 @@ def test_gpu_decoder_on_synthetic_edge_streams(gpu_decoder, style, seed):
     assert st["gpu_decode"] == 0 and np.array_equal(got_host, want)
 
 
+def test_block_images_of_hand_placed_blocks_count_the_same_on_the_gpu_and_on_host_threads(gpu_decoder):
+    """one block of every family of tests/lz4_block_writer.py in one image: the GPU decoder and the host threads give the oracle's
+    counters; with one block that breaks an end-of-block rule of liblz4 (the reference fails on such a file) both fail loudly"""
+    import struct
+
+    import lz4_block_writer as bw
+    import oracle
+    from libflagstats_amd import _lib, blockfile
+    hip = gpu_decoder
+    picked = [cases[len(cases) // 2] for cases in (fam() for fam in bw.FAMILIES.values())] + [bw.FAMILIES["literals"]()[-1]]
+    img, want, n = bytearray(), np.zeros(32, dtype=np.uint64), 0
+    for name, comp, dec, _, _ in picked:
+        img += struct.pack("<ii", len(dec), len(comp)) + comp
+        want += oracle.flagstat_hist(np.frombuffer(dec[:len(dec) & ~1], dtype=np.uint16))
+        n += len(dec) >> 1
+    got, st = blockfile.flagstat_lz4_image(bytes(img), 2)
+    assert st["gpu_decode"] == 1 and st["n_flags"] == n and np.array_equal(got, want)
+    assert hip.FLAGSTATS_hip_set(b"lz4_decoder", 0) == 0
+    try:
+        got_host, st = blockfile.flagstat_lz4_image(bytes(img), 2)
+        assert st["gpu_decode"] == 0 and np.array_equal(got_host, want)
+        for name, comp, usize in bw.end_defects()[::7]:
+            assert bt.decompress_block_ref(comp, usize) is None, name
+            bad = bytes(img) + struct.pack("<ii", usize, len(comp)) + comp
+            for decoder in (1, 0):
+                assert hip.FLAGSTATS_hip_set(b"lz4_decoder", decoder) == 0
+                with pytest.raises(_lib.FlagstatsHipError):
+                    blockfile.flagstat_lz4_image(bad, 2)
+    finally:
+        assert hip.FLAGSTATS_hip_set(b"lz4_decoder", 1) == 0
+    got, st = blockfile.flagstat_lz4_image(bytes(img), 2)
+    assert st["gpu_decode"] == 1 and np.array_equal(got, want)
+
+
 def test_gpu_decoder_goes_through_large_files_in_segments(gpu_decoder, tmp_path, monkeypatch):
     """A file whose compressed + decoded bytes do not fit the device together is decoded in segments, one after the
     other; forced here with a 3 MiB segment on 10 blocks (image, file, superset), and a segment smaller than a block."""

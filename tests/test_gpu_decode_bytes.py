@@ -176,6 +176,106 @@ def test_lz4_decode_is_byte_exact_on_a_slice_of_the_fuzzer(hip, kernel):
     assert strict <= 30, strict
 
 
+# ------------------------------------------------------------------------------------- LZ4: blocks no compressor writes
+# Everything above came out of liblz4's compressors or out of a generator that draws sequences at random.  The blocks below are
+# written by tests/lz4_block_writer.py from a description (tests/test_lz4_writer_host.py holds that writer against liblz4 on the
+# CPU and proves every placement): tokens, matches and literal runs ON the workgroup kernel's boundaries -- segment positions, tile
+# ends, the input ring's end, the 384-byte span, 256-byte chunks, the 67,584-byte ring -- and on the wave kernel's.  The contract is
+# strict: status 0, liblz4's bytes, which are the writer's, nothing behind the even length, pospopcnt of the decoded buffer.
+LZ4_FAMILIES = ["segments", "stops", "literals", "span", "chunks", "tails", "ends", "wave"]
+
+
+def run_placed(hip, kernel, cases, what, batch=64):
+    """cases: (name, compressed, decoded, ...) from the test-only writer; a failing launch names its blocks"""
+    for at in range(0, len(cases), batch):
+        part = cases[at:at + batch]
+        names = [c[0] for c in part]
+        try:
+            wants = run_and_compare(hip, "lz4", [(c[1], len(c[2])) for c in part], what, kernel)
+        except AssertionError as e:
+            i = next((a for a in e.args[0] if isinstance(a, int)), None) if e.args and isinstance(e.args[0], tuple) else None
+            raise AssertionError("%s (blocks of this launch: %s)%s" % (e, names, "" if i is None else " -- block: " + names[i]))
+        for name, want, c in zip(names, wants, part):
+            assert want == c[2], (name, "liblz4's bytes are not the writer's")
+
+
+@pytest.mark.parametrize("kernel", LZ4_KERNELS)
+@pytest.mark.parametrize("family", LZ4_FAMILIES)
+def test_lz4_decode_is_byte_exact_on_hand_placed_blocks(hip, kernel, family):
+    """window-form sequences of every input length at every position of a segment, across tile ends and the input ring's end; every
+    kind of token the walker hands to the scalar code; literal runs of every form, on ring byte 67,583; windows of 383..385 and of
+    4,368 output bytes; matches on chunk borders, periods 1..7 over many chunks, chains inside a chunk, offsets 65,535 round the ring;
+    sizes round every flush; the tightest endings liblz4 accepts; the wave kernel's own numbers.  Both kernels take every family."""
+    import lz4_block_writer as bw
+    assert list(bw.FAMILIES) == LZ4_FAMILIES
+    run_placed(hip, kernel, bw.FAMILIES[family](), ("hand-placed", family))
+
+
+@pytest.mark.parametrize("kernel", LZ4_KERNELS)
+def test_lz4_decode_refuses_hand_damaged_blocks(hip, kernel):
+    """one defect each -- offset 0, an offset one beyond the output, length bytes past the input, a run or a match past the declared
+    size, a size one off, a cut at each of the last 20 bytes, and the three endings liblz4 refuses (a block that ends in a match,
+    fewer than 5 last literals behind a match, a last match within 12 bytes of the end): a status that is not 0 for each (which
+    one is not asserted: where several waves fail, the last code stands), and the valid neighbours of the same launch are exact"""
+    import lz4_block_writer as bw
+    bad = bw.rejected()
+    good = [c for c in bw.FAMILIES["tails"]() if len(c[2]) < 70000][:len(bad) + 1]
+    good = (good * (len(bad) // len(good) + 2))[:len(bad) + 1]
+    payloads, sizes = [good[0][1]], [len(good[0][2])]
+    for (name, comp, usize), g in zip(bad, good[1:]):
+        payloads += [comp, g[1]]
+        sizes += [usize, len(g[2])]
+    accepted = []
+    with du.DeviceDecode(hip, "lz4", payloads, sizes, kernel) as dd:
+        for i, (name, comp, usize) in enumerate(bad):
+            st = int(dd.status[2 * i + 1])
+            print("kernel %d: status %2d  %s" % (kernel, st, name))
+            if st == 0:
+                accepted.append(name)
+        for i, g in enumerate(good):
+            du.check_decoded(dd, 2 * i, g[2], ("the valid neighbour", g[0], "before", bad[i][0] if i < len(bad) else None))
+    assert not accepted, ("damaged blocks the GPU decoder accepts", accepted)
+
+
+def lz4_shape_fuzz_slice(hip, kernel, first, count, batch=50):
+    """lz4_block_writer.random_block over a seed range: every block exact, two damaged variants per block under the rule of
+    lz4_fuzz_slice; returns (exact, both accept, both reject, GPU stricter)"""
+    import lz4_block_writer as bw
+    exact = both_ok = both_bad = strict = 0
+    for s0 in range(first, first + count, batch):
+        cases, damaged = [], []
+        for seed in range(s0, min(s0 + batch, first + count)):
+            rng = random.Random(seed)
+            comp, dec, layout = bw.random_block(rng)
+            cases.append(("shape fuzz seed %d" % seed, comp, dec))
+            for _ in range(2):
+                bad = bytearray(comp)
+                for _ in range(rng.randint(1, 5)):
+                    bad[rng.randrange(len(bad))] ^= rng.randint(1, 255)
+                damaged.append((bytes(bad) if rng.random() < 0.8 else bytes(bad[:rng.randrange(1, len(bad) + 1)]), len(dec)))
+        run_placed(hip, kernel, cases, ("shape fuzz seeds from", s0), batch=batch)
+        exact += len(cases)
+        with du.DeviceDecode(hip, "lz4", [p for p, _ in damaged], [n for _, n in damaged], kernel) as dd:
+            for i, (p, n) in enumerate(damaged):
+                want = du.ref_lz4(p, n)
+                if dd.status[i] == 0:
+                    assert want is not None, ("seed", s0 + i // 2, "liblz4 rejects, the GPU decoder accepts")
+                    du.check_decoded(dd, i, want, ("damaged, seed", s0 + i // 2))
+                    both_ok += 1
+                elif want is None:
+                    both_bad += 1
+                else:
+                    strict += 1
+    return exact, both_ok, both_bad, strict
+
+
+@pytest.mark.parametrize("kernel", LZ4_KERNELS)
+def test_lz4_decode_is_byte_exact_on_a_slice_of_the_placed_fuzzer(hip, kernel):
+    exact, both_ok, both_bad, strict = lz4_shape_fuzz_slice(hip, kernel, 0, 300)
+    print("placed fuzz, kernel %d: %d exact; damaged: both accept %d, both reject %d, GPU stricter %d" % (kernel, exact, both_ok, both_bad, strict))
+    assert exact == 300 and both_ok + both_bad + strict == 600
+
+
 # ------------------------------------------------------------------------------------------------------------ Zstandard
 def _zstd_parts(raws, level):
     return [(bt.compress_block(raw, "zstd", level), len(raw)) for raw in raws]

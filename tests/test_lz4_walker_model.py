@@ -7,6 +7,7 @@ per segment; (3) forward again, the positions reachable from each segment's entr
 in further bytes (or whose match-length byte is 255) stop the tile.  This file pins that restatement -- the tables' sizes,
 the stop rules, the tile-end arithmetic, and (r05) that the prefix SCAN over the exit tables gives what the serial walk gives -- on LZ4-fast and LZ4-HC streams of flag data and on streams full of long matches
 and literal runs; the HIP code itself is checked on the GPU (tests/test_gpu_blockfile.py)."""
+import bisect
 import os
 import sys
 
@@ -19,6 +20,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import blockfile_tool as bt  # noqa: E402
 
 SEG, SEGS, TAB = 32, 64, 12
+TAIL = 50     # a tile's last position, were it the token of a sequence of 19 input bytes, has that sequence inside the block
 
 
 def true_chain(comp):
@@ -55,15 +57,63 @@ def true_chain(comp):
     return pos, simple
 
 
+def _exit_tables(buf, lanes):
+    """pass (1) of walk_tile for all lanes at once (what its loop does per segment, on numpy columns): the tables as integers"""
+    B = np.frombuffer(buf, dtype=np.uint8)[:SEG * lanes].reshape(lanes, SEG).astype(np.int64)
+    win = np.zeros((lanes, 19), dtype=np.int64)          # (column 18 stays zero: d - 1 = 18 only under ll = 15, which is overridden)
+    tab = [0] * lanes
+    rows = np.arange(lanes)
+    for i in range(SEG - 1, -1, -1):
+        tok = B[:, i]
+        ll = tok >> 4
+        d = 3 + ll + ((tok & 15) == 15)
+        ex = win[rows, d - 1]
+        ex = np.where(d >= SEG - i, i + d - SEG, ex)
+        ex = np.where(ll == 15, 31, ex)
+        win[:, 1:18] = win[:, 0:17].copy()
+        win[:, 0] = ex
+        if i < TAB:
+            for s, e in enumerate(ex.tolist()):
+                tab[s] |= e << (5 * i)
+    return tab
+
+
+def _members(buf, ip, ent, nvalid, e_next):
+    """pass (3) of walk_tile for all lanes at once (what its loop does per segment, on numpy columns), and its result"""
+    W = np.lib.stride_tricks.as_strided(np.frombuffer(buf, dtype=np.uint8), shape=(nvalid, 2 * SEG), strides=(SEG, 1)).astype(np.int64)
+    rows = np.arange(nvalid)
+    reach = np.left_shift(1, np.array(ent[:nvalid], dtype=np.int64))
+    stop = np.full(nvalid, SEG, dtype=np.int64)
+    for i in range(SEG):
+        tok = W[:, i]
+        ll, mlc = tok >> 4, tok & 15
+        on = ((reach >> i) & 1) == 1
+        halt = on & ((ll == 15) | ((mlc == 15) & (W[rows, np.minimum(i + 3 + ll, 2 * SEG - 1)] == 255)))
+        stop = np.where(halt, np.minimum(stop, i), stop)
+        reach |= np.where(on & ~halt, np.left_shift(1, i + 3 + ll + (mlc == 15)), 0)
+    members = []
+    for s, (r, st) in enumerate(zip(reach.tolist(), stop.tolist())):
+        members += [ip + SEG * s + i for i in range(min(st, SEG)) if (r >> i) & 1]
+        if st < SEG:
+            return members, SEG * s + st, True
+    assert e_next < 18, "the chain saw a token for the scalar code that the members pass did not"
+    return members, SEG * nvalid + e_next, False
+
+
 def walk_tile(comp, ip):
     """one tile at input position ip, as the kernel does it: (members found, positions advanced, stopped at a token for the scalar code)"""
     iend = len(comp)
-    nseg = min(SEGS, (iend - ip - 50) // SEG + 1) if iend >= ip + 50 else 0
+    nseg = min(SEGS, (iend - ip - TAIL) // SEG + 1) if iend >= ip + TAIL else 0
     if nseg == 0:
         return None
-    byte = lambda x: comp[x] if x < iend else 0  # noqa: E731
-    tabs = []
-    for s in range(SEGS):
+    # (the kernel computes all 64 lanes; what lanes behind the tile's last segment hold reaches nothing: the chain runs left to
+    # right and is read eight segments at a time, so the model stops at the next multiple of eight)
+    lanes = min(SEGS, (nseg + 7) // 8 * 8)
+    buf = bytes(comp[ip:ip + SEG * lanes + 64])
+    buf += bytes(SEG * lanes + 64 - len(buf))        # (what lies behind the block reads as zero)
+    byte = lambda x: buf[x - ip]  # noqa: E731
+    tabs = _exit_tables(buf, lanes) if lanes > 16 else []
+    for s in range(0 if tabs else lanes):
         win, tab = [0] * 18, 0
         for i in range(SEG - 1, -1, -1):
             tok = byte(ip + SEG * s + i)
@@ -79,7 +129,7 @@ def walk_tile(comp, ip):
                 tab |= ex << (5 * i)
         tabs.append(tab)
     ent, e, nvalid, e_next = [0] * SEGS, 0, nseg, 0
-    for sg in range(SEGS):
+    for sg in range(lanes):
         if sg % 8 == 0 and sg >= nvalid:
             break
         ent[sg] = e
@@ -94,24 +144,24 @@ def walk_tile(comp, ip):
     # doubling rounds (a lane composes its table with the one 1, 2, 4 ... lanes to its left; an exit of 12 or more stays what it
     # is), F(s)(0) is segment s's exit, the first exit of 12 or more (or the last segment) ends the tile.  Same entries, same end.
     ident = sum(e << (5 * e) for e in range(TAB))
-    F = list(tabs)
+    F = np.array(tabs, dtype=np.uint64)              # (the lanes at once, as the kernel has them)
+    u = np.uint64
     d = 1
-    while d < SEGS:
-        G = [F[s - d] if s >= d else ident for s in range(SEGS)]
-        nF = []
-        for s in range(SEGS):
-            n = 0
-            for en in range(TAB):
-                v = (G[s] >> (5 * en)) & 31
-                t = (F[s] >> ((5 * v) & 63)) & 31
-                n |= (v if v >= TAB else t) << (5 * en)
-            nF.append(n)
-        F, d = nF, d * 2
-    exits = [f & 31 for f in F]
-    last_seg = min(s for s in range(SEGS) if exits[s] >= TAB or s + 1 >= nseg)
+    while d < SEGS and d < lanes:                    # (a round whose left neighbours are all the identity changes nothing)
+        G = np.concatenate([np.full(min(d, lanes), ident, dtype=np.uint64), F[:max(lanes - d, 0)]])
+        n = np.zeros(lanes, dtype=np.uint64)
+        for en in range(TAB):
+            v = (G >> u(5 * en)) & u(31)
+            t = (F >> ((u(5) * v) & u(63))) & u(31)
+            n |= np.where(v >= u(TAB), v, t) << u(5 * en)
+        F, d = n, d * 2
+    exits = [int(f) & 31 for f in F]
+    last_seg = min(s for s in range(lanes) if exits[s] >= TAB or s + 1 >= nseg)
     assert last_seg + 1 == nvalid and exits[last_seg] == e_next, ("scan", ip, last_seg, nvalid, exits[last_seg], e_next)
     assert [0] + exits[:last_seg] == ent[:nvalid], ("scan entries", ip)
     members = []
+    if lanes > 16:
+        return _members(buf, ip, ent, nvalid, e_next)
     for s in range(nvalid):
         reach, stop = 1 << ent[s], SEG
         for i in range(SEG):
@@ -134,10 +184,15 @@ def walk_tile(comp, ip):
 def check_block(raw, mode, level):
     comp = bt.compress_block(raw, mode, level)
     assert bt.decompress_block_ref(comp, len(raw)) == raw
+    return len(check_stream(comp, mode, level))
+
+
+def check_stream(comp, mode="written", level=0):
+    """the walker's tiles over one valid block, whoever wrote it: [(tile's input position, members, positions advanced, stopped)]"""
     pos, simple = true_chain(comp)
     nxt = {p: (pos[k + 1] if k + 1 < len(pos) else len(comp)) for k, p in enumerate(pos)}
     chain = set(pos)
-    ip, tiles = 0, 0
+    ip, tiles = 0, []
     while True:
         t = walk_tile(comp, ip)
         if t is None:
@@ -145,14 +200,18 @@ def check_block(raw, mode, level):
         members, adv, stopped = t
         end = ip + adv
         assert end in chain, (mode, level, "tile ends off the chain", ip, end)
-        assert members == [p for p in pos if ip <= p < end], (mode, level, "members", ip)
+        assert members == pos[bisect.bisect_left(pos, ip):bisect.bisect_left(pos, end)], (mode, level, "members", ip)
         assert all(simple[p] for p in members), (mode, level, "a member the window form does not cover", ip)
         if stopped:
             assert not simple[end], (mode, level, "stopped at a token the window form covers", end)
             end = nxt[end]                 # the scalar code takes that sequence
         else:
             assert adv > 0
-        ip, tiles = end, tiles + 1
+        # what the tail rule is for: a sequence of 19 input bytes from the tile's last position would still lie inside the block
+        nseg = min(SEGS, (len(comp) - ip - TAIL) // SEG + 1)
+        assert ip + SEG * nseg - 1 + 19 <= len(comp), (mode, level, "the tile's last position is too close to the block's end", ip)
+        tiles.append((ip, members, adv, stopped))
+        ip = end
         if ip >= len(comp):
             break
     return tiles
