@@ -58,7 +58,13 @@ int FLAGSTATS_u16_x64(const uint16_t* array, uint64_t n, uint64_t* out);
 /* DEVICE-resident array (any 2-byte alignment), DEVICE counters: d_out[32] (uint64, device memory) += counters,
  * asynchronously on `stream` (a hipStream_t passed as void*; NULL = HIP's null stream).  One kernel launch; the adds are
  * atomic, so launches on several streams may share d_out.  d_array may also be page-locked host memory: it is then read in
- * place over PCIe, with no staging copy. */
+ * place over PCIe, with no staging copy.
+ * Streams and HIP graphs: every entry that takes a `stream` (this one, _store, _superset, device_pospopcnt_u16, the
+ * all-reduce forms) keeps one small workspace per caller stream -- the 64 most recently used streams of a device have one; a
+ * 65th stream takes the least recently used one's (after a device-wide wait), and raising the knob "blocks_per_cu" replaces a
+ * stream's workspace at its next call.  Plain launches never notice.  A launch CAPTURED into a graph holds its stream's
+ * workspace pointer: the graph stays valid while its stream stays among the 64 most recently used and "blocks_per_cu" is not
+ * raised; after either, replaying it touches freed memory -- capture it again instead. */
 int FLAGSTATS_hip_device_u16(const uint16_t* d_array, uint64_t n, uint64_t* d_out, void* stream);
 /* same, but d_out[32] = counters (all 32 slots written, never-written slots as 0): one query per call with no zeroing
  * launch in front; used by the multi-GPU step before its all-reduce. */

@@ -132,7 +132,10 @@ int FLAGSTATS_hip_blockimage_lz4_gpu(const void* image, uint64_t bytes, uint64_t
  *                    1 = r03's one wave per block (kept as the yardstick)
  * Read-only keys of FLAGSTATS_hip_get: "grid" (K1 workgroups), "numa_node" (of the default device),
  * "host_chunks" / "host_overlapped" (last multi-chunk host-pointer call on the default engine: chunks
- * submitted / chunks handed over while the previous chunk's copy + kernel were still in flight).
+ * submitted / chunks handed over while the previous chunk's copy + kernel were still in flight),
+ * "staged_calls" (host-pointer calls the "staged_min_flags" rule has sent through the chunk pipeline; the explicit
+ * FLAGSTATS_hip_host_staged_u16 does not count), "user_workspaces" (caller-stream workspaces the default device's engine
+ * holds for the stream-taking device entries: one per stream, at most 64, the least recently used one goes first).
  * Returns 0 on success. */
 
 #ifdef __cplusplus

@@ -284,6 +284,13 @@ uint64_t FLAGSTATS_hip_get(const char* key)
         for (uint64_t c : e->zstd_scratch_cap) held += c;
         return held;
     }
+    if (!std::strcmp(key, "user_workspaces")) {
+        if (fsint::default_device() < 0) return 0;
+        Engine* e = fsint::default_engine();
+        if (!e) return 0;
+        std::lock_guard<std::mutex> lk(e->user_mu);
+        return e->user_ws.size();
+    }
     if (!std::strcmp(key, "fence_free_events")) return static_cast<uint64_t>(k.fence_free_events.load());
     if (!std::strcmp(key, "grid")) {
         if (fsint::default_device() < 0) return 0;

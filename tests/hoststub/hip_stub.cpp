@@ -188,6 +188,7 @@ hipError_t hipMalloc(void** p, size_t bytes)
 {
     *p = std::aligned_alloc(256, (bytes + 255) & ~static_cast<size_t>(255));
     if (!*p) return hipErrorInvalidValue;
+    std::memset(*p, 0xA5, bytes);  // like the real thing: a fresh allocation holds whatever was there, never promised zeros
     remember(*p, bytes, hipMemoryTypeDevice);
     return hipSuccess;
 }
@@ -414,7 +415,12 @@ extern "C" {
 void fsk_warm(void) {}
 size_t fsk_partials_bytes(uint32_t grid) { return static_cast<size_t>(grid) * fsk::kInternal * sizeof(uint64_t) + 8192; }
 
-hipError_t fsk_launch(const uint16_t* d_array, uint64_t n, uint32_t grid, int variant, uint64_t* d_partials, uint32_t*,
+// launches that met a workspace whose 8 KiB block behind the partials was not zero (fsk_launch's invariant: zero before the
+// first launch -- ensure_ws zeroes a fresh workspace on the launching stream -- and left zero by every launch)
+static std::atomic<int> g_dirty_blocks{0};
+int hip_stub_dirty_blocks(void) { return g_dirty_blocks.load(); }
+
+hipError_t fsk_launch(const uint16_t* d_array, uint64_t n, uint32_t grid, int variant, uint64_t* d_partials, uint32_t* d_block,
                       uint64_t* d_out32, hipStream_t stream, uint64_t* signal_word, uint64_t signal_value)
 {
     if (n == 0) return hipSuccess;
@@ -424,6 +430,12 @@ hipError_t fsk_launch(const uint16_t* d_array, uint64_t n, uint32_t grid, int va
     enqueue(stream, [=] {
         uint64_t c[32];
         std::memset(c, 0, sizeof c);
+        if (d_block) {
+            const unsigned char* b = reinterpret_cast<const unsigned char*>(d_block);
+            bool dirty = false;
+            for (size_t i = 0; i < 8192 && !dirty; ++i) dirty = b[i] != 0;
+            if (dirty && g_dirty_blocks.fetch_add(1) == 0) std::fprintf(stderr, "hip_stub: a launch met a workspace block that is not zero\n");
+        }
         oracle_flagstat_u16(d_array, n, c);
         if (superset) {
             for (uint64_t i = 0; i < n; ++i) {

@@ -5,14 +5,18 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 #include <unistd.h>
 
+#include <hip/hip_runtime.h>   // (the stand-in's: the caller-stream scenario makes its own streams)
+
 #include "../../include/libflagstats_hip_probe.h"
 extern "C" {
 #include "../../oracle/flagstat_oracle.h"
+int hip_stub_dirty_blocks(void);   // hip_stub.cpp: launches that met a workspace block that was not zero
 }
 
 static int g_fail = 0;
@@ -313,6 +317,118 @@ static void multi(const std::vector<uint16_t>& flags, const uint64_t* want)
     FLAGSTATS_hip_ctx_destroy(c1);
 }
 
+// what the superset forms add to the plain counters: slots 0 / 16 = primary paired reads by QC class, slot 9 = pass-QC reads
+static void scalar_count(const uint16_t* a, size_t n, bool superset, uint64_t* c)
+{
+    oracle_flagstat_u16(a, n, c);
+    if (!superset) return;
+    for (size_t i = 0; i < n; ++i) {
+        const uint16_t x = a[i];
+        const bool fail = x & 0x200;
+        if ((x & 1) && !(x & 0x100) && !(x & 0x800)) ++c[fail ? 16 : 0];
+        if (!fail) ++c[9];
+    }
+}
+
+// The per-stream workspace cache of the device entries (count_on_user_stream: one Workspace per caller stream, most recently
+// used first, at most 64): 70 caller streams and the NULL stream visited in the same order round after round, so that from the
+// 65th call on EVERY call evicts the least recently used stream's workspace and every stream comes back after having been
+// evicted; "blocks_per_cu" raised and lowered between the calls (a raised grid frees and re-makes the workspace of the stream
+// that calls next); the K2 forms (which write the workspace) as well as the atomic one; then two threads on streams of their
+// own.  No wait between the calls.  Counters against the scalar rule; "device" memory is the heap, so a workspace that is used
+// after its release, or released twice, is an AddressSanitizer report; the stand-in refuses a workspace block that is not zero.
+static void user_streams(const std::vector<uint16_t>& flags)
+{
+    constexpr int kStreams = 70, kSlots = kStreams + 1;   // slot 70: the NULL stream
+    const size_t sizes[4] = {70001, 16383, 1, 7};
+    const size_t nd = 70001 + 8;
+    uint16_t* d = static_cast<uint16_t*>(FLAGSTATS_hip_device_alloc(nd * 2));
+    uint64_t* d_out = static_cast<uint64_t*>(FLAGSTATS_hip_device_alloc(kSlots * 48 * sizeof(uint64_t)));   // 32 counters + 16 bit counts each
+    CHECK(d && d_out, "device_alloc: %s", FLAGSTATS_hip_last_error());
+    if (!d || !d_out) return;
+    std::vector<uint64_t> want(kSlots * 48, 0), got(kSlots * 48, 0);
+    CHECK(FLAGSTATS_hip_memcpy_h2d(d, flags.data(), nd * 2) == 0 && FLAGSTATS_hip_memcpy_h2d(d_out, want.data(), want.size() * 8) == 0, "h2d");
+    hipStream_t st[kSlots];
+    for (int i = 0; i < kStreams; ++i) CHECK(hipStreamCreateWithFlags(&st[i], hipStreamNonBlocking) == hipSuccess, "stream %d", i);
+    st[kStreams] = nullptr;
+    const uint64_t before = FLAGSTATS_hip_get("user_workspaces");
+    CHECK(before <= 64, "%llu caller-stream workspaces before the scenario", static_cast<unsigned long long>(before));
+    uint64_t most = before;
+    int calls = 0;
+    auto one = [&](int i, int form, size_t off, size_t m) {   // form 0 accumulate, 1 store, 2 superset accumulate, 3 pospopcnt
+        uint64_t* o = d_out + i * 48;
+        uint64_t c[32] = {0};
+        int rc = 0;
+        if (form == 3) {
+            rc = FLAGSTATS_hip_device_pospopcnt_u16(d + off, m, o + 32, st[i]);
+            oracle_pospopcnt_u16(flags.data() + off, m, c);
+            for (int k = 0; k < 16; ++k) want[i * 48 + 32 + k] += c[k];
+        } else {
+            rc = form == 1 ? FLAGSTATS_hip_device_u16_store(d + off, m, o, st[i])
+                           : form == 2 ? FLAGSTATS_hip_device_u16_superset(d + off, m, o, st[i]) : FLAGSTATS_hip_device_u16(d + off, m, o, st[i]);
+            scalar_count(flags.data() + off, m, form == 2, c);
+            for (int k = 0; k < 32; ++k) want[i * 48 + k] = (form == 1 ? 0 : want[i * 48 + k]) + c[k];
+        }
+        CHECK(rc == 0, "call %d on stream %d (form %d): %s", calls, i, form, FLAGSTATS_hip_last_error());
+        const uint64_t held = FLAGSTATS_hip_get("user_workspaces");
+        CHECK(held <= 64, "%llu caller-stream workspaces held", static_cast<unsigned long long>(held));
+        if (held > most) most = held;
+        ++calls;
+    };
+    const uint64_t grids[4] = {2, 5, 1, 3};
+    for (int round = 0; round < 3; ++round) {
+        FLAGSTATS_hip_set("epilogue", round == 1 ? 0 : 1);   // round 1: partials + K2, which writes the workspace
+        for (int i = 0; i < kSlots; ++i) {
+            if (calls % 9 == 4) FLAGSTATS_hip_set("blocks_per_cu", grids[(calls / 9) % 4]);
+            const size_t m = sizes[(i + round) % 4], off = static_cast<size_t>(i + round) % 8;
+            one(i, round < 2 ? 0 : (i & 1) ? 2 : 1, off, m);
+            if (i % 5 == round) one(i, 3, off, m);   // (a second call on the stream at the front: no splice, no eviction)
+        }
+        CHECK(FLAGSTATS_hip_get("user_workspaces") == 64, "round %d: %llu workspaces held, not 64", round,
+              static_cast<unsigned long long>(FLAGSTATS_hip_get("user_workspaces")));
+    }
+    FLAGSTATS_hip_set("epilogue", 1);
+    // two caller threads, 35 streams each, two more rounds: the list is spliced and evicted from under one lock by both
+    {
+        std::mutex wm;   // (`one` updates want / calls / most)
+        auto th = [&](int t) {
+            for (int round = 0; round < 2; ++round)
+                for (int i = t * 35; i < t * 35 + 35; ++i) {
+                    if (t == 0 && i % 7 == 3) FLAGSTATS_hip_set("blocks_per_cu", grids[(i / 7 + round) % 4]);
+                    std::lock_guard<std::mutex> lk(wm);
+                    one(i, i % 3 == 0 ? 2 : 0, static_cast<size_t>(i) % 8, sizes[(i + round) % 4]);
+                }
+        };
+        // the bookkeeping is serialised by `wm`; the LIBRARY calls of the second pair of threads below are not
+        std::thread a(th, 0), b(th, 1);
+        a.join();
+        b.join();
+        auto free_running = [&](int t) {   // same streams, the calls themselves concurrent: every thread adds to ITS streams' counters only
+            for (int i = t * 35; i < t * 35 + 35; ++i) {
+                const size_t m = sizes[i % 4], off = static_cast<size_t>(i) % 8;
+                CHECK(FLAGSTATS_hip_device_u16(d + off, m, d_out + i * 48, st[i]) == 0, "concurrent call on stream %d", i);
+                CHECK(FLAGSTATS_hip_get("user_workspaces") <= 64, "more than 64 workspaces held");
+                uint64_t c[32] = {0};
+                oracle_flagstat_u16(flags.data() + off, m, c);
+                for (int k = 0; k < 32; ++k) want[i * 48 + k] += c[k];   // (disjoint rows per thread)
+            }
+        };
+        std::thread c(free_running, 0), e(free_running, 1);
+        c.join();
+        e.join();
+    }
+    FLAGSTATS_hip_set("blocks_per_cu", 1);
+    CHECK(hipDeviceSynchronize() == hipSuccess, "device sync");
+    CHECK(FLAGSTATS_hip_memcpy_d2h(got.data(), d_out, got.size() * 8) == 0, "d2h");
+    for (int i = 0; i < kSlots; ++i)
+        CHECK(std::memcmp(&got[i * 48], &want[i * 48], 48 * 8) == 0, "caller stream %d: counters differ from the scalar rule", i);
+    CHECK(most == 64 && FLAGSTATS_hip_get("user_workspaces") == 64, "the cache never filled: at most %llu workspaces", static_cast<unsigned long long>(most));
+    CHECK(hip_stub_dirty_blocks() == 0, "%d launches met a workspace block that was not zero", hip_stub_dirty_blocks());
+    for (int i = 0; i < kStreams; ++i) CHECK(hipStreamDestroy(st[i]) == hipSuccess, "stream destroy");
+    FLAGSTATS_hip_device_free(d);
+    FLAGSTATS_hip_device_free(d_out);
+}
+
 int main(int argc, char** argv)
 {
     const size_t n = 3000017;
@@ -328,6 +444,7 @@ int main(int argc, char** argv)
         sessions(flags, want);
         callers(flags);
         multi(flags, want);
+        user_streams(flags);
         FLAGSTATS_hip_shutdown();  // second round: everything is created again
     }
     std::printf(g_fail ? "tsan_driver: %d FAILED checks\n" : "tsan_driver: all checks passed\n", g_fail);
