@@ -105,6 +105,37 @@ int FLAGSTATS_hip_device_u16_segments_sync(const uint16_t* d_array, uint64_t n, 
 int FLAGSTATS_hip_u16_x64_segments(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint64_t nseg,
                                    uint64_t* out, int flags);
 
+/* ================= wide input: a FLAG column held as 4-byte or 8-byte integers, counted in place =================
+ * numpy's default integer, a pandas / CSV column and torch's natural integer tensors are int64 or int32, Arrow / Parquet FLAG
+ * columns int32.  These entries read such an array as it is (little-endian elements of `elem_bytes` = 4 or 8 bytes, signed or
+ * unsigned alike) instead of asking for a uint16 copy: the LOW 16 BITS of every element are counted exactly as the entries above
+ * count a uint16 -- the same 32 slots, the same scalar-exact rule -- and, in the same pass over the array,
+ *   high = OR over all elements of (element & ~0xFFFF), taken as unsigned
+ * is reported: high == 0 means every element was a valid 16-bit FLAG; a negative element sets bit 31 (elem_bytes 4) or bit 63
+ * (elem_bytes 8); any other bit names a value of 65,536 or more (a wrong column, a parse error).  The mask is exact and
+ * deterministic.  The counters are always those of the truncated values (as FLAGSTATS_text_to_u16 documents for text input); it is
+ * the caller who decides what a non-zero mask means.
+ * `flags`: bit 0 = store (out = counters, all 32 slots written; high = mask) instead of out += counters, high |= mask;
+ * bit 1 = superset (slots 0 / 16 and slot 9 = n minus slot 25, as the superset forms above).  `high` / `d_high` may be NULL:
+ * nothing is reported.  n == 0 succeeds and touches nothing (the store form writes zeros).
+ * Refused (non-zero, message in FLAGSTATS_hip_last_error, out and high untouched, nothing launched): elem_bytes other than 4 or
+ * 8 (2: use the u16 entries), an array pointer not aligned to elem_bytes, flag bits other than 0 and 1, a NULL array with
+ * n > 0; for the device form also a d_out or d_high that is not plain device memory, pointers on different devices, a stream
+ * of another device and an allocation shorter than n * elem_bytes (d_out: 256, d_high: 8) bytes from the pointer on. */
+/* DEVICE array, DEVICE d_out[32] and d_high[1] (uint64); asynchronous on `stream`: ONE kernel (the store form puts one memset
+ * per pointer in front of it; one in all when d_high == d_out + 32).  No per-stream workspace is kept, so a captured launch
+ * holds no pointer of the library's (the caveat of FLAGSTATS_hip_device_u16); capturing this entry into a graph is untested,
+ * though: it queries its pointers (hipPointerGetAttributes, hipMemGetAddressRange) and creates the device's engine on a first
+ * call, so make one plain call before capturing.  Adds and ORs are atomic: launches on several streams may share d_out and
+ * d_high in the += form. */
+int FLAGSTATS_hip_device_wide(const void* d_array, uint64_t n, int elem_bytes, uint64_t* d_out, uint64_t* d_high, int flags,
+                              void* stream);
+/* DEVICE array, HOST out[32] and high[1]; synchronous */
+int FLAGSTATS_hip_device_wide_sync(const void* d_array, uint64_t n, int elem_bytes, uint64_t* out, uint64_t* high, int flags);
+/* HOST array, HOST out[32] and high[1]; synchronous.  The array crosses the bus as it is (n * elem_bytes bytes) in the engine's
+ * chunks (knob "chunk_flags": chunk_flags * 2 bytes each); counters and mask are summed / ORed on the device. */
+int FLAGSTATS_hip_wide_x64(const void* array, uint64_t n, int elem_bytes, uint64_t* out, uint64_t* high, int flags);
+
 /* 64-bit positional popcount in this library's convention: out[16] += bit counts (host array / device array) */
 int FLAGSTATS_hip_pospopcnt_u16_x64(const uint16_t* array, uint64_t n, uint64_t* out);
 int FLAGSTATS_hip_device_pospopcnt_u16(const uint16_t* d_array, uint64_t n, uint64_t* d_out, void* stream);

@@ -9,6 +9,8 @@ Only what the path needs:
 * ``device``         device-resident arrays, on-device input makers, torch interop
 * ``segments``       per-segment counters (CSR offsets) in one launch: host arrays,
                      device pointers, torch tensors
+* ``wide``           the same counters for int32 / int64 (and 16-bit) arrays and tensors,
+                     with the mask of bits seen above bit 15
 * ``dist``           shard + single all-reduce for multi-GPU runs
 
 The hot path has no CPU fallback: importing the compute entry points without the
@@ -22,6 +24,8 @@ from .segments import (  # noqa: F401
     offsets_from_lengths,
     segment_dicts,
 )
+from .wide import count_device_ptr_ints, count_torch_ints, counters_ints, flagstats_ints  # noqa: F401
 
 __all__ = ["flagstats", "flagstats_x64", "SAM_FLAG_NAMES", "flagstats_segments", "offsets_from_lengths",
-           "count_segments_device_ptr", "count_segments_torch", "segment_dicts"]
+           "count_segments_device_ptr", "count_segments_torch", "segment_dicts", "counters_ints", "flagstats_ints",
+           "count_device_ptr_ints", "count_torch_ints"]

@@ -58,6 +58,12 @@ SIGNATURES = {
                                                               ctypes.c_void_p, ctypes.c_int]),
     "FLAGSTATS_hip_u16_x64_segments": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                                       ctypes.c_void_p, ctypes.c_int]),
+    "FLAGSTATS_hip_device_wide": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_int, ctypes.c_void_p]),
+    "FLAGSTATS_hip_device_wide_sync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_int]),
+    "FLAGSTATS_hip_wide_x64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_int]),
     "FLAGSTATS_hip_available": (ctypes.c_int, []),
     "FLAGSTATS_hip_device_count": (ctypes.c_int, []),
     "FLAGSTATS_hip_ctx_create": (ctypes.c_void_p, [ctypes.c_int]),
@@ -141,6 +147,14 @@ SIGNATURES = {
                                                  ctypes.POINTER(ctypes.c_float)]),
 }
 
+# internal launchers the tests and tests/perf drive directly (csrc/flagstat_wide.h); not part of the public headers, so kept apart
+# from SIGNATURES, which mirrors those
+INTERNAL_SIGNATURES = {
+    "fsk_launch_wide": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                       ctypes.c_uint32, ctypes.c_void_p]),
+    "fsk_wide_geometry": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, _U64P]),
+}
+
 _lib = None
 
 
@@ -190,7 +204,7 @@ def lib() -> ctypes.CDLL:
             "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C libflagstats_amd/csrc`). "
             "libflagstats_amd has no CPU fallback for the flagstat hot path.")
     handle = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items()):
         fn = getattr(handle, name)  # AttributeError here = header/library drift
         fn.restype = restype
         fn.argtypes = argtypes

@@ -17,6 +17,7 @@
 #include <sched.h>
 
 #include <atomic>
+#include <cstdio>
 #include <condition_variable>
 #include <functional>
 #include <list>
@@ -228,6 +229,33 @@ int select_default_device(int device);             // FLAGSTATS_hip_init
 int device_of_pointer(const void* p, const char* what, int* device, bool* plain_device_memory = nullptr);
 // a caller's stream must belong to `device` (NULL = that device's null stream)
 int check_stream_device(hipStream_t s, int device);
+#ifndef FLAGSTATS_HOST_STUB
+// a device pointer's allocation must hold `bytes` from it on (skipped where the runtime does not know the range); 0, or the
+// recorded error naming `what`.  (Entries of the product library only: the host-stub build has no address ranges.)
+inline int check_extent(const void* p, uint64_t bytes, const char* what)
+{
+    hipDeviceptr_t b = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&b, &size, const_cast<void*>(p)) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    const uintptr_t end = reinterpret_cast<uintptr_t>(b) + size, at = reinterpret_cast<uintptr_t>(p);
+    if (at < reinterpret_cast<uintptr_t>(b) || end - at < bytes) {
+        char buf[192];
+        std::snprintf(buf, sizeof buf, "%s (%p) is %llu bytes short of the %llu the call needs", what, p,
+                      static_cast<unsigned long long>(bytes - (end > at ? end - at : 0)), static_cast<unsigned long long>(bytes));
+        return fail_text(buf);
+    }
+    return 0;
+}
+#endif
+// a HIP call inside a C entry: on failure the error is recorded (fail_hip) and returned
+#define FS_HIP_TRY(expr)                                          \
+    do {                                                          \
+        hipError_t e_ = (expr);                                   \
+        if (e_ != hipSuccess) return fsint::fail_hip(#expr, e_);  \
+    } while (0)
 // `waiter` waits (on the device; the host does not) for everything queued on `on` so far.  Knob "fence_free_events":
 // the event carries no system-scope fence (a plain hipEventRecord costs the launch stream ~10 us of cache write-back
 // per record here); off by default.

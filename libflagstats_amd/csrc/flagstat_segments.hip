@@ -443,12 +443,6 @@ using fsint::fail_text;
 
 namespace {
 
-#define SEG_TRY(expr)                                      \
-    do {                                                   \
-        hipError_t e_ = (expr);                            \
-        if (e_ != hipSuccess) return fail_hip(#expr, e_);  \
-    } while (0)
-
 constexpr uint64_t kMaxSegments = (~0ull) / 256 - 1;  // nseg * 256 bytes of counters must be a size
 
 uint32_t seg_grid(const Engine& e) { return static_cast<uint32_t>(e.cus) * g_seg_blocks_per_cu.load(); }
@@ -468,25 +462,6 @@ int check_host_offsets(const uint64_t* offsets, uint64_t nseg, uint64_t n)
     if (offsets[nseg] > n) {
         std::snprintf(buf, sizeof buf, "offsets[nseg] = %llu exceeds the array's %llu flags",
                       static_cast<unsigned long long>(offsets[nseg]), static_cast<unsigned long long>(n));
-        return fail_text(buf);
-    }
-    return 0;
-}
-
-// a device pointer's allocation must hold `bytes` from it on (skipped where the runtime does not know the range)
-int check_extent(const void* p, uint64_t bytes, const char* what)
-{
-    hipDeviceptr_t b = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&b, &size, const_cast<void*>(p)) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    const uintptr_t end = reinterpret_cast<uintptr_t>(b) + size, at = reinterpret_cast<uintptr_t>(p);
-    if (at < reinterpret_cast<uintptr_t>(b) || end - at < bytes) {
-        char buf[192];
-        std::snprintf(buf, sizeof buf, "%s (%p) is %llu bytes short of the %llu the call needs", what, p,
-                      static_cast<unsigned long long>(bytes - (end > at ? end - at : 0)), static_cast<unsigned long long>(bytes));
         return fail_text(buf);
     }
     return 0;
@@ -588,10 +563,10 @@ int FLAGSTATS_hip_device_u16_segments(const uint16_t* d_array, uint64_t n, const
     hipStream_t s = static_cast<hipStream_t>(stream);
     rc = fsint::check_stream_device(s, e->device);
     if (rc) return rc;
-    if ((rc = check_extent(d_out, nseg * 32 * sizeof(uint64_t), "d_out")) || (rc = check_extent(d_offsets, (nseg + 1) * sizeof(uint64_t), "d_offsets")))
+    if ((rc = fsint::check_extent(d_out, nseg * 32 * sizeof(uint64_t), "d_out")) || (rc = fsint::check_extent(d_offsets, (nseg + 1) * sizeof(uint64_t), "d_offsets")))
         return rc;
-    if (n && (rc = check_extent(d_array, n * sizeof(uint16_t), "d_array"))) return rc;
-    SEG_TRY(fsk_launch_segments(d_array, 0, n, d_offsets, nseg, d_out, flags & 3, seg_grid(*e), s));
+    if (n && (rc = fsint::check_extent(d_array, n * sizeof(uint16_t), "d_array"))) return rc;
+    FS_HIP_TRY(fsk_launch_segments(d_array, 0, n, d_offsets, nseg, d_out, flags & 3, seg_grid(*e), s));
     return 0;
 }
 
@@ -624,12 +599,12 @@ int FLAGSTATS_hip_device_u16_segments_sync(const uint16_t* d_array, uint64_t n, 
     HostRows got;
     if ((rc = buf.alloc(nseg)) || (rc = got.alloc(nseg))) return rc;
     if ((rc = check_host_offsets(offsets, nseg, n))) return rc;
-    if (n && (rc = check_extent(d_array, n * sizeof(uint16_t), "d_array"))) return rc;
+    if (n && (rc = fsint::check_extent(d_array, n * sizeof(uint16_t), "d_array"))) return rc;
     hipStream_t s = e.stream[0];
-    SEG_TRY(hipMemcpyAsync(buf.off, offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    SEG_TRY(fsk_launch_segments(d_array, 0, n, buf.off, nseg, buf.cnt, 1 | (flags & 2), seg_grid(e), s));
-    SEG_TRY(hipMemcpyAsync(got.p.get(), buf.cnt, got.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    SEG_TRY(hipStreamSynchronize(s));
+    FS_HIP_TRY(hipMemcpyAsync(buf.off, offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    FS_HIP_TRY(fsk_launch_segments(d_array, 0, n, buf.off, nseg, buf.cnt, 1 | (flags & 2), seg_grid(e), s));
+    FS_HIP_TRY(hipMemcpyAsync(got.p.get(), buf.cnt, got.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    FS_HIP_TRY(hipStreamSynchronize(s));
     apply(out, got, flags);
     return 0;
 }
@@ -664,8 +639,8 @@ int FLAGSTATS_hip_u16_x64_segments(const uint16_t* array, uint64_t n, const uint
     for (int i = 0; i < slots; ++i)
         if ((rc = fsint::stage_reserve(e, i, last - first < chunk ? (last - first ? last - first : 1) : chunk))) return rc;
     hipStream_t s0 = e.stream[0];
-    SEG_TRY(hipMemsetAsync(buf.cnt, 0, nseg * 32 * sizeof(uint64_t), s0));
-    SEG_TRY(hipMemcpyAsync(buf.off, offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s0));
+    FS_HIP_TRY(hipMemsetAsync(buf.cnt, 0, nseg * 32 * sizeof(uint64_t), s0));
+    FS_HIP_TRY(hipMemcpyAsync(buf.off, offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s0));
     if (slots == 2 && (rc = fsint::stream_wait_stream(e, e.stream[1], s0))) return rc;
     const uint32_t grid = seg_grid(e);
     const int mode = flags & 2;
@@ -673,13 +648,13 @@ int FLAGSTATS_hip_u16_x64_segments(const uint16_t* array, uint64_t n, const uint
     for (uint64_t pos = first; pos < last; pos += chunk, ++k) {
         const int sl = static_cast<int>(k % static_cast<uint64_t>(slots));
         const uint64_t c = last - pos < chunk ? last - pos : chunk;
-        SEG_TRY(hipMemcpyAsync(e.stage[sl], array + pos, c * sizeof(uint16_t), hipMemcpyHostToDevice, e.stream[sl]));
-        SEG_TRY(fsk_launch_segments(e.stage[sl], pos, c, buf.off, nseg, buf.cnt, mode, grid, e.stream[sl]));
+        FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], array + pos, c * sizeof(uint16_t), hipMemcpyHostToDevice, e.stream[sl]));
+        FS_HIP_TRY(fsk_launch_segments(e.stage[sl], pos, c, buf.off, nseg, buf.cnt, mode, grid, e.stream[sl]));
     }
     if (slots == 2 && (rc = fsint::stream_wait_stream(e, s0, e.stream[1]))) return rc;
-    SEG_TRY(hipMemcpyAsync(got.p.get(), buf.cnt, got.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s0));
-    SEG_TRY(hipStreamSynchronize(s0));
-    if (slots == 2) SEG_TRY(hipStreamSynchronize(e.stream[1]));
+    FS_HIP_TRY(hipMemcpyAsync(got.p.get(), buf.cnt, got.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s0));
+    FS_HIP_TRY(hipStreamSynchronize(s0));
+    if (slots == 2) FS_HIP_TRY(hipStreamSynchronize(e.stream[1]));
     apply(out, got, flags);
     return 0;
 }

@@ -1,0 +1,504 @@
+// flagstat_wide.hip -- flagstat of a FLAG array held as 4-byte or 8-byte little-endian integers (int32 / int64 columns), read in
+// place: the low 16 bits of every element are counted exactly as K1 counts a uint16, and every bit above bit 15 that any
+// element carries is ORed into one uint64 mask, in the same pass.
+//
+// Geometry.  K1's, in bytes: the array is addressed on the 16-byte grid of its aligned-down base and cut into steps of 32 KiB
+// (256 lanes x 8 vectors of 16 B: 8,192 elements at W = 4, 4,096 at W = 8); workgroup b takes the head edge step (b == 0), the
+// tail edge step, then the fully covered steps b, b + G, ...; each wave owns a contiguous 8 KiB of a step.  Edge steps go through
+// a guarded, zero-filling loader (a zero element counts nothing and sets no mask bit); fast steps through K1's rolling load
+// schedule (schedule 71: a vector's registers are re-issued for the vector six places on as soon as it has been read out),
+// restated below from flagstat_kernels.hip.  tests/steps_oracle.StepSplit(addr % 16, n * W / 2, grid) is the step split.
+//
+// Narrowing.  front4 (flagstat_count_core.h) wants 4 flags as a dword L of their low bytes and a dword H of their high bytes.
+// One v_perm_b32 takes two flag-carrying dwords a, b to P = [a.b0, b.b0, a.b1, b.b1]; a second pair of perms takes two P to L
+// and H.  At W = 4 every loaded vector (4 elements) gives one (L, H); at W = 8 the even dwords of two vectors do, and the odd
+// dwords are all high bits and feed only the mask.  A step thus has 8 (W = 4) or 4 (W = 8) inputs where K1 has 16: they go
+// through the first three (two) levels of K1's carry-save tree and the carry is walked up the remaining planes alone, so a step
+// still ends in ONE weight-16 push into the lane's chain -- epochs of 255 steps, the flush and the wave stagger are K1's.
+//
+// Mask.  Each lane ORs its loaded dwords together (v_or3_b32: one per two dwords), even and -- at W = 8 -- odd dwords apart;
+// at the end the even stream is cut to its bits 16-31, the wave ORs over its lanes (DPP), the workgroup over its waves (LDS),
+// and a workgroup whose value is non-zero does one relaxed agent-scope atomic OR on the caller's word.
+//
+// Epilogue.  K1's direct one: every workgroup maps its 21 totals to the 32 slots and adds them to out[32] with relaxed
+// agent-scope atomics.  No workspace, no second kernel; the store form zeroes counters and mask in front (one memset).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cstdio>
+#include <mutex>
+
+#include "../../include/libflagstats_hip.h"
+#include "flagstat_count_core.h"
+#include "flagstat_engine.h"
+#include "flagstat_wide.h"
+
+namespace fsk {
+
+constexpr int kWideDepth = 8;        // chain depth as K1: epochs of 255 steps
+constexpr int kWideStepBytes = kVecPerStep * 16;   // 32 KiB
+
+// Read a just-loaded vector out of its registers AT THIS POINT of the instruction stream (they are re-targeted by the load of
+// a later vector right after, as in K1's split_out): the flag-carrying dwords pairwise to P = [a.b0, b.b0, a.b1, b.b1], every
+// dword into the mask accumulators.  W = 4: two P (elements 0,1 and 2,3).  W = 8: one P (the even dwords), p1 untouched.
+template <int W>
+__device__ __forceinline__ void narrow_out(const uint4& o, uint32_t& p0, uint32_t& p1, uint32_t& or_even, uint32_t& or_odd)
+{
+    const uint32_t sel = 0x05010400u;
+    if constexpr (W == 4) {
+        asm volatile("v_perm_b32 %0, %4, %3, %7\n\tv_perm_b32 %1, %6, %5, %7\n\tv_or3_b32 %2, %2, %3, %4\n\tv_or3_b32 %2, %2, %5, %6"
+                     : "=&v"(p0), "=&v"(p1), "+v"(or_even)
+                     : "v"(o.x), "v"(o.y), "v"(o.z), "v"(o.w), "s"(sel));
+    } else {
+        asm volatile("v_perm_b32 %0, %5, %3, %7\n\tv_or3_b32 %1, %1, %3, %5\n\tv_or3_b32 %2, %2, %4, %6"
+                     : "=&v"(p0), "+v"(or_even), "+v"(or_odd)
+                     : "v"(o.x), "v"(o.y), "v"(o.z), "v"(o.w), "s"(sel));
+    }
+}
+
+// one level of K1's carry-save tree on CNT inputs of the plane's weight (CNT == 1: the lone carry walks up)
+template <int CNT, int N>
+__device__ __forceinline__ void wide_level(uint32_t (&x)[N], uint32_t& plane)
+{
+    if constexpr (CNT >= 2) {
+#pragma unroll
+        for (int i = 0; i < CNT / 2; ++i) csa(x[i], plane, plane, x[2 * i], x[2 * i + 1]);
+    } else {
+        csa(x[0], plane, plane, x[0], 0u);
+    }
+}
+
+// N inputs of weight 1 through the planes of weight 1, 2, 4, 8: the weight-16 carry
+template <int N>
+__device__ __forceinline__ uint32_t wide_tree(uint32_t (&x)[N], uint32_t& p1, uint32_t& p2, uint32_t& p4, uint32_t& p8)
+{
+    static_assert(N == 4 || N == 8, "a 32 KiB step holds 8 (W = 4) or 4 (W = 8) inputs per lane");
+    wide_level<N>(x, p1);
+    wide_level<N / 2>(x, p2);
+    wide_level<N / 4>(x, p4);
+    wide_level<(N >= 8 ? N / 8 : 1)>(x, p8);
+    return x[0];
+}
+
+// One step: 8 vectors of 16 B per lane = 32 / W inputs of 4 flags each.
+// ROLL 0: the vectors are in v[].  ROLL 1, 2: K1's schedule 71 -- vector u's registers are re-issued for vector u + 6 of the same
+// step (`cur`) or, ROLL 1 only, u - 2 of the next one (`next`): 6 loads = 24 KiB per CU in flight.
+template <int W, int ROLL>
+__device__ __forceinline__ void wide_step(Lane<kWideDepth>& s, uint4 (&v)[kUnroll], uint32_t blk, uint32_t& or_even, uint32_t& or_odd,
+                                          const uint4* __restrict__ cur, const uint4* __restrict__ next)
+{
+    constexpr int NIN = 32 / W;
+    constexpr int RD = 6;
+    constexpr int US = 64;   // each wave a contiguous 8 KiB of the step
+    uint32_t T[NIN], F[NIN], S[NIN];
+    uint32_t held = 0;       // W = 8: the even vector's P until the odd one's arrives
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+        uint32_t p0, p1 = 0;
+        __builtin_amdgcn_sched_barrier(0);
+        narrow_out<W>(v[u], p0, p1, or_even, or_odd);
+        if constexpr (ROLL != 0) {
+            if (u + RD < kUnroll)
+                v[u + RD] = load_vec<true>(cur + (u + RD) * US);
+            else if constexpr (ROLL == 1)
+                v[u + RD - kUnroll] = load_vec<true>(next + (u + RD - kUnroll) * US);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (W == 8 && (u & 1) == 0) {
+            held = p0;
+            continue;
+        }
+        const uint32_t a = W == 4 ? p0 : held, b = W == 4 ? p1 : p0;   // flags 0,1 and 2,3
+        const uint32_t L = perm(b, a, 0x05040100u), H = perm(b, a, 0x07060302u);
+        const int i = W == 4 ? u : u / 2;
+        uint32_t q, k;
+        front4(L, H, T[i], q, k);
+        F[i] = T[i] & perm(0u, 0xFF00FF00u, q);
+        S[i] = perm(0u, 0x84428140u, q) & (k | 0x3F3F3F3Fu);
+    }
+    const uint32_t ct = wide_tree(T, s.t1, s.t2, s.t4, s.t8);
+    const uint32_t cf = wide_tree(F, s.f1, s.f2, s.f4, s.f8);
+    const uint32_t cs = wide_tree(S, s.s1, s.s2, s.s4, s.s8);
+    chain_push<0, kWideDepth>(s, blk, ct, cf, cs);
+}
+
+template <int W, int ROLL>
+__device__ __forceinline__ void wide_step_and_count(Lane<kWideDepth>& s, uint4 (&v)[kUnroll], uint32_t& blk, uint32_t& or_even,
+                                                    uint32_t& or_odd, const uint4* __restrict__ cur = nullptr,
+                                                    const uint4* __restrict__ next = nullptr)
+{
+    blk = __builtin_amdgcn_readfirstlane(blk);
+    wide_step<W, ROLL>(s, v, blk, or_even, or_odd, cur, next);
+    ++blk;
+    if (blk == (1u << kWideDepth) - 1u) {
+        flush(s, (1u << kWideDepth) - 1u);
+        blk = 0;
+    }
+}
+
+// Vector j of the 16-byte grid holds element positions [j * 16 / W, (j + 1) * 16 / W); positions in [lo, hi) are the caller's
+// elements, everything else reads as zero.  Only dwords of elements inside [lo, hi) are ever read.
+template <int W>
+__device__ __forceinline__ uint4 load_guarded_wide(const uint4* __restrict__ a0, uint64_t j, uint64_t lo, uint64_t hi)
+{
+    constexpr int EPV = 16 / W, DPE = W / 4;
+    const uint64_t f0 = j * EPV;
+    if (f0 >= lo && f0 + EPV <= hi) return a0[j];
+    uint32_t w[4] = {0, 0, 0, 0};
+    if (f0 + EPV <= lo || f0 >= hi) return make_uint4(0, 0, 0, 0);
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(a0 + j);
+#pragma unroll
+    for (int e = 0; e < EPV; ++e) {
+        const uint64_t f = f0 + e;
+        if (f >= lo && f < hi) {
+#pragma unroll
+            for (int d = 0; d < DPE; ++d) w[e * DPE + d] = p[e * DPE + d];
+        }
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// OR of x over the 64 lanes of a wave, valid in lane 63 only (the DPP steps of wave_sum_lane63 with | for +; lanes a step does
+// not write read 0)
+__device__ __forceinline__ uint32_t wave_or_lane63(uint32_t x)
+{
+    x |= static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), 0xB1, 0xF, 0xF, false));
+    x |= static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), 0x4E, 0xF, 0xF, false));
+    x |= static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), 0x141, 0xF, 0xF, false));
+    x |= static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), 0x140, 0xF, 0xF, false));
+    x |= static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), 0x142, 0xA, 0xF, false));
+    x |= static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), 0x143, 0xC, 0xF, false));
+    return x;
+}
+
+// a0: 16-B aligned-down base; the caller's elements occupy positions [lo, hi) of its grid of W-byte elements.  mode: bit 1
+// superset (bit 0, the store form, is the launcher's memset).  high may be nullptr.
+template <int W>
+__global__ __launch_bounds__(kThreads) void flagstat_count_wide(const uint4* __restrict__ a0, uint64_t lo, uint64_t hi, uint64_t nsteps,
+                                                                uint64_t fast_begin, uint64_t fast_end, uint64_t* __restrict__ out,
+                                                                uint64_t* __restrict__ high, int mode)
+{
+    static_assert(W == 4 || W == 8, "4-byte or 8-byte elements");
+    Lane<kWideDepth> s;
+    lane_init(s);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = threadIdx.x >> 6;
+    constexpr int VPS = kVecPerStep;
+    constexpr int US = 64;
+    const uint64_t lane_off = static_cast<uint64_t>(wave) * (64 * kUnroll) + lane;
+    const uint64_t G = gridDim.x;
+    // wave w starts its first epoch at 64 * w, so at most one wave of a CU is flushing at any time (K1's mode bit 4)
+    uint32_t blk = (wave & 3u) * 64u;
+    uint32_t or_even = 0, or_odd = 0;
+
+    auto edge_step = [&](uint64_t st) {
+        uint4 v[kUnroll];
+        const uint64_t j0 = st * VPS + lane_off;
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) v[u] = load_guarded_wide<W>(a0, j0 + u * US, lo, hi);
+        wide_step_and_count<W, 0>(s, v, blk, or_even, or_odd);
+    };
+    // ragged edge steps (at most the first and the last of the whole array), outside the pipelined loop
+    if (fast_begin != 0 && blockIdx.x == 0) edge_step(0);
+    if (nsteps > fast_end && nsteps - 1 >= fast_begin && (nsteps - 1) % G == blockIdx.x) edge_step(nsteps - 1);
+    // first fully in-range step of this workgroup
+    uint64_t st = blockIdx.x;
+    if (st < fast_begin) st += G;  // fast_begin is 0 or 1
+    if (st < fast_end) {
+        constexpr int RD = 6;
+        uint4 v[kUnroll];
+        const uint4* p = a0 + st * VPS + lane_off;
+#pragma unroll
+        for (int u = 0; u < RD; ++u) {  // the first RD vectors; the rest is issued as they are consumed
+            v[u] = load_vec<true>(p + u * US);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        for (; st + G < fast_end; st += G) {
+            const uint4* pn = p + G * VPS;
+            wide_step_and_count<W, 1>(s, v, blk, or_even, or_odd, p, pn);
+            p = pn;
+        }
+        wide_step_and_count<W, 2>(s, v, blk, or_even, or_odd, p);
+    }
+    flush(s, blk);
+
+    // wave sums and ORs on the VALU (DPP), then the 4 waves through LDS
+    constexpr int kWaves = kThreads / 64;
+    __shared__ uint32_t red[kWaves][kInternal];
+    __shared__ uint32_t hred[kWaves][2];
+    __shared__ uint64_t wg_tot[32];
+    uint32_t wsum[kInternal];
+#pragma unroll
+    for (int c = 0; c < kInternal; ++c) wsum[c] = wave_sum_lane63(s.acc[c]);
+    const uint32_t we = wave_or_lane63(or_even & 0xFFFF0000u);   // the even-dword stream: bits 16-31 of every element
+    const uint32_t wo = wave_or_lane63(or_odd);                   // W = 8: bits 32-63
+    if (lane == 63) {
+#pragma unroll
+        for (int c = 0; c < kInternal; ++c) red[wave][c] = wsum[c];
+        hred[wave][0] = we;
+        hred[wave][1] = wo;
+    }
+    __syncthreads();
+    if (threadIdx.x < kInternal) {
+        uint64_t sum = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) sum += red[w][threadIdx.x];
+        wg_tot[threadIdx.x] = sum;
+    }
+    if (threadIdx.x == 64 && high != nullptr) {
+        uint32_t e = 0, o = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            e |= hred[w][0];
+            o |= hred[w][1];
+        }
+        const uint64_t m = (static_cast<uint64_t>(o) << 32) | e;
+        if (m) (void)__hip_atomic_fetch_or(high, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    // this workgroup's totals, mapped to the reference's slots, added to out[32]; n enters slot 9 (superset) in workgroup 0
+    finalize_slots<true>(wg_tot, out, mode, blockIdx.x == 0 ? hi - lo : 0);
+}
+
+}  // namespace fsk
+
+// ------------------------------------------------------------------ launcher
+// Host-side geometry: everything the kernel assumes is derived here from (address, n, W).
+extern "C" hipError_t fsk_wide_geometry(uint64_t address, uint64_t n, int elem_bytes, uint32_t grid, uint64_t* geo)
+{
+    if ((elem_bytes != 4 && elem_bytes != 8) || grid == 0 || geo == nullptr) return hipErrorInvalidValue;
+    const uint64_t W = static_cast<uint64_t>(elem_bytes);
+    const uint64_t addr = address;
+    if (addr & (W - 1)) return hipErrorInvalidValue;
+    for (int i = 0; i < 6; ++i) geo[i] = 0;
+    if (n == 0) return hipSuccess;
+    if (n > (~0ull - 64) / W) return hipErrorInvalidValue;  // n * W must be a size
+    const uint64_t base = addr & ~static_cast<uint64_t>(15);
+    const uint64_t epv = 16 / W;                            // elements per 16-byte vector
+    const uint64_t lo = (addr - base) / W, hi = lo + n;
+    const uint64_t nvec = (hi + epv - 1) / epv;
+    const uint64_t vps = fsk::kVecPerStep;
+    const uint64_t nsteps = (nvec + vps - 1) / vps;
+    // steps whose vectors are all fully inside [lo, hi)
+    uint64_t fast_begin = (lo == 0) ? 0 : 1;
+    uint64_t fast_end = (hi / epv) / vps;
+    if (fast_end < fast_begin) fast_end = fast_begin;
+    if (static_cast<uint64_t>(grid) > nsteps) grid = static_cast<uint32_t>(nsteps);
+    // a wave's totals are uint32: a workgroup pushes at most ceil(nsteps / grid) + 2 steps (its share and both edge steps), each
+    // wave a quarter of every step
+    const uint64_t wave_elems_per_step = fsk::kWideStepBytes / W / (fsk::kThreads / 64);
+    if (nsteps / grid + 3 >= (1ull << 32) / wave_elems_per_step) return hipErrorInvalidValue;
+    geo[0] = lo;
+    geo[1] = hi;
+    geo[2] = nsteps;
+    geo[3] = fast_begin;
+    geo[4] = fast_end;
+    geo[5] = grid;
+    return hipSuccess;
+}
+
+extern "C" hipError_t fsk_launch_wide(const void* d_array, uint64_t n, int elem_bytes, uint64_t* d_out32, uint64_t* d_high, int mode,
+                                      uint32_t grid, hipStream_t stream)
+{
+    if ((elem_bytes != 4 && elem_bytes != 8) || (mode & ~3) || grid == 0 || d_out32 == nullptr || (n && d_array == nullptr))
+        return hipErrorInvalidValue;
+    uint64_t geo[6];
+    hipError_t e = fsk_wide_geometry(reinterpret_cast<uintptr_t>(d_array), n, elem_bytes, grid, geo);
+    if (e != hipSuccess) return e;
+    if (mode & 1) {
+        // counters and mask word in one memset where they are one allocation's 33 words
+        const bool together = d_high == d_out32 + 32;
+        e = hipMemsetAsync(d_out32, 0, (together ? 33 : 32) * sizeof(uint64_t), stream);
+        if (e == hipSuccess && d_high && !together) e = hipMemsetAsync(d_high, 0, sizeof(uint64_t), stream);
+        if (e != hipSuccess) return e;
+    }
+    if (n == 0) return hipSuccess;
+    const uint4* a0 = reinterpret_cast<const uint4*>(reinterpret_cast<uintptr_t>(d_array) & ~static_cast<uintptr_t>(15));
+    const dim3 g(static_cast<uint32_t>(geo[5])), b(fsk::kThreads);
+    if (elem_bytes == 4)
+        hipLaunchKernelGGL(fsk::flagstat_count_wide<4>, g, b, 0, stream, a0, geo[0], geo[1], geo[2], geo[3], geo[4], d_out32, d_high, mode & 2);
+    else
+        hipLaunchKernelGGL(fsk::flagstat_count_wide<8>, g, b, 0, stream, a0, geo[0], geo[1], geo[2], geo[3], geo[4], d_out32, d_high, mode & 2);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ C entry points (include/libflagstats_hip.h)
+using fsint::DeviceGuard;
+using fsint::Engine;
+using fsint::fail_hip;
+using fsint::fail_text;
+
+namespace {
+
+// what every form refuses before it touches the GPU
+int wide_args(const void* array, uint64_t n, int elem_bytes, const void* out, int flags)
+{
+    if (elem_bytes == 2) return fail_text("elem_bytes 2: 16-bit arrays go to the u16 entries (FLAGSTATS_u16_x64, FLAGSTATS_hip_device_u16)");
+    if (elem_bytes != 4 && elem_bytes != 8) return fail_text("elem_bytes must be 4 or 8");
+    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
+    if (n && !array) return fail_text("NULL array with n > 0");
+    if (reinterpret_cast<uintptr_t>(array) & static_cast<uintptr_t>(elem_bytes - 1))
+        return fail_text(elem_bytes == 4 ? "array must be 4-byte aligned (elem_bytes 4)" : "array must be 8-byte aligned (elem_bytes 8)");
+    if (n > (~0ull - 64) / static_cast<uint64_t>(elem_bytes)) return fail_text("n * elem_bytes is not a size");
+    if (!out && (n || (flags & 1))) return fail_text("NULL counters");
+    return 0;
+}
+
+// device counters[32] + mask word of one synchronous call
+struct WideRow {
+    uint64_t* d = nullptr;
+    ~WideRow()
+    {
+        if (d) (void)hipFree(d);
+    }
+    int alloc()
+    {
+        const hipError_t e = hipMalloc(&d, 33 * sizeof(uint64_t));
+        if (e != hipSuccess) {
+            d = nullptr;
+            return fail_hip("hipMalloc(wide counters)", e);
+        }
+        return 0;
+    }
+};
+
+void wide_apply(uint64_t* out, uint64_t* high, const uint64_t (&got)[33], int flags)
+{
+    if (flags & 1) {
+        for (int i = 0; i < 32; ++i) out[i] = got[i];
+        if (high) *high = got[32];
+    } else {
+        for (int i = 0; i < 32; ++i) out[i] += got[i];
+        if (high) *high |= got[32];
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int FLAGSTATS_hip_device_wide(const void* d_array, uint64_t n, int elem_bytes, uint64_t* d_out, uint64_t* d_high, int flags, void* stream)
+{
+    FS_ENTRY();
+    int rc = wide_args(d_array, n, elem_bytes, d_out, flags);
+    if (rc) return rc;
+    if (n == 0 && !(flags & 1)) return 0;
+    int dev_out = -1, dev = -1;
+    bool plain = false;
+    rc = fsint::device_of_pointer(d_out, "d_out", &dev_out, &plain);
+    if (rc) return rc;
+    if (!plain) return fail_text("d_out must be device memory (the counters are added with device atomics)");
+    if (d_high) {
+        rc = fsint::device_of_pointer(d_high, "d_high", &dev, &plain);
+        if (rc) return rc;
+        if (!plain) return fail_text("d_high must be device memory (the mask is ORed with a device atomic)");
+        if (dev != dev_out) return fail_text("d_high and d_out live on different devices");
+    }
+    if (n) {
+        rc = fsint::device_of_pointer(d_array, "d_array", &dev);
+        if (rc) return rc;
+        if (dev != dev_out) return fail_text("d_array and d_out live on different devices");
+    }
+    Engine* e = fsint::engine_for_device(dev_out);
+    if (!e) return -1;
+    DeviceGuard guard(e->device);
+    if (!guard.ok()) return -1;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = fsint::check_stream_device(s, e->device);
+    if (rc) return rc;
+    if ((rc = fsint::check_extent(d_out, 32 * sizeof(uint64_t), "d_out"))) return rc;
+    if (d_high && (rc = fsint::check_extent(d_high, sizeof(uint64_t), "d_high"))) return rc;
+    if (n && (rc = fsint::check_extent(d_array, n * static_cast<uint64_t>(elem_bytes), "d_array"))) return rc;
+    FS_HIP_TRY(fsk_launch_wide(d_array, n, elem_bytes, d_out, d_high, flags & 3, fsint::grid_for(*e), s));
+    return 0;
+}
+
+int FLAGSTATS_hip_device_wide_sync(const void* d_array, uint64_t n, int elem_bytes, uint64_t* out, uint64_t* high, int flags)
+{
+    FS_ENTRY();
+    int rc = wide_args(d_array, n, elem_bytes, out, flags);
+    if (rc) return rc;
+    if (n == 0) {
+        if (flags & 1) {
+            for (int i = 0; i < 32; ++i) out[i] = 0;
+            if (high) *high = 0;
+        }
+        return 0;
+    }
+    int dev = -1;
+    rc = fsint::device_of_pointer(d_array, "d_array", &dev);
+    if (rc) return rc;
+    Engine* ep = fsint::engine_for_device(dev);
+    if (!ep) return -1;
+    Engine& e = *ep;
+    std::lock_guard<std::mutex> lk(e.mu);
+    if (fsint::engine_alive(e)) return -1;
+    DeviceGuard guard(e.device);
+    if (!guard.ok()) return -1;
+    if ((rc = fsint::check_extent(d_array, n * static_cast<uint64_t>(elem_bytes), "d_array"))) return rc;
+    WideRow row;
+    if ((rc = row.alloc())) return rc;
+    uint64_t got[33];
+    hipStream_t s = e.stream[0];
+    FS_HIP_TRY(fsk_launch_wide(d_array, n, elem_bytes, row.d, row.d + 32, 1 | (flags & 2), fsint::grid_for(e), s));
+    FS_HIP_TRY(hipMemcpyAsync(got, row.d, sizeof got, hipMemcpyDeviceToHost, s));
+    FS_HIP_TRY(hipStreamSynchronize(s));
+    wide_apply(out, high, got, flags);
+    return 0;
+}
+
+int FLAGSTATS_hip_wide_x64(const void* array, uint64_t n, int elem_bytes, uint64_t* out, uint64_t* high, int flags)
+{
+    FS_ENTRY();
+    int rc = wide_args(array, n, elem_bytes, out, flags);
+    if (rc) return rc;
+    if (n == 0) {
+        if (flags & 1) {
+            for (int i = 0; i < 32; ++i) out[i] = 0;
+            if (high) *high = 0;
+        }
+        return 0;
+    }
+    Engine* ep = fsint::default_engine();
+    if (!ep) return -1;
+    Engine& e = *ep;
+    std::lock_guard<std::mutex> lk(e.mu);
+    if (fsint::engine_alive(e)) return -1;
+    DeviceGuard guard(e.device);
+    if (!guard.ok()) return -1;
+    fsint::lz4_gpu_other_use(e);
+    WideRow row;
+    if ((rc = row.alloc())) return rc;
+    if ((rc = fsint::engine_second(e))) return rc;
+    // the array crosses the bus as it is, in chunks of "chunk_flags" * 2 bytes, alternating between the engine's two streams
+    // and staging buffers (the copy of chunk k + 1 overlaps the kernel on chunk k); every chunk's launch adds into the same
+    // device counters and ORs into the same mask word
+    const uint64_t W = static_cast<uint64_t>(elem_bytes);
+    const uint64_t chunk_flags = fsint::knobs().chunk_flags.load() < 8 ? 8 : fsint::knobs().chunk_flags.load();
+    const uint64_t chunk = chunk_flags * 2 / W;   // elements per chunk
+    const int slots = n > chunk ? 2 : 1;
+    for (int i = 0; i < slots; ++i)
+        if ((rc = fsint::stage_reserve(e, i, n < chunk ? (n * W + 1) / 2 : chunk_flags))) return rc;
+    hipStream_t s0 = e.stream[0];
+    FS_HIP_TRY(hipMemsetAsync(row.d, 0, 33 * sizeof(uint64_t), s0));
+    if (slots == 2 && (rc = fsint::stream_wait_stream(e, e.stream[1], s0))) return rc;
+    const uint32_t grid = fsint::grid_for(e);
+    const int mode = flags & 2;
+    const uint8_t* src = static_cast<const uint8_t*>(array);
+    uint64_t k = 0;
+    for (uint64_t pos = 0; pos < n; pos += chunk, ++k) {
+        const int sl = static_cast<int>(k % static_cast<uint64_t>(slots));
+        const uint64_t c = n - pos < chunk ? n - pos : chunk;
+        FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], src + pos * W, c * W, hipMemcpyHostToDevice, e.stream[sl]));
+        FS_HIP_TRY(fsk_launch_wide(e.stage[sl], c, elem_bytes, row.d, row.d + 32, mode, grid, e.stream[sl]));
+    }
+    if (slots == 2 && (rc = fsint::stream_wait_stream(e, s0, e.stream[1]))) return rc;
+    uint64_t got[33];
+    FS_HIP_TRY(hipMemcpyAsync(got, row.d, sizeof got, hipMemcpyDeviceToHost, s0));
+    FS_HIP_TRY(hipStreamSynchronize(s0));
+    if (slots == 2) FS_HIP_TRY(hipStreamSynchronize(e.stream[1]));
+    wide_apply(out, high, got, flags);
+    return 0;
+}
+
+}  // extern "C"
