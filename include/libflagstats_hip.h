@@ -136,6 +136,37 @@ int FLAGSTATS_hip_device_wide_sync(const void* d_array, uint64_t n, int elem_byt
  * chunks (knob "chunk_flags": chunk_flags * 2 bytes each); counters and mask are summed / ORed on the device. */
 int FLAGSTATS_hip_wide_x64(const void* array, uint64_t n, int elem_bytes, uint64_t* out, uint64_t* high, int flags);
 
+/* ================= selected elements: flagstat under a bitmap or a byte mask =================
+ * The table for the reads with MAPQ >= 30, for one read group or contig, for the non-null rows of an Arrow column: instead of
+ * compacting the column first (values[mask]: a pass over column and mask, a copy, a pass over the copy) these entries read the
+ * uint16 array and its selection once, in one kernel.  The 32 counters are FLAGSTAT_scalar's over the subsequence
+ * {array[i] : sel(i), 0 <= i < n}; `selected` is the number of i with sel(i).  Two encodings of sel, chosen by `sel_bits`:
+ *   sel_bits == 1: an LSB-first bitmap (Arrow's validity layout, numpy.packbits(m, bitorder="little")): element i is bit
+ *                  (sel_offset + i) & 7 of byte (sel_offset + i) >> 3 of `sel`; sel_offset is any uint64 (an Arrow slice's offset)
+ *   sel_bits == 8: one byte per element (numpy bool, torch.bool): element i is byte sel_offset + i, any non-zero byte selects
+ * Only bytes of `sel` that hold the bit or byte of an element are read.
+ * `flags`: bit 0 = store (out = counters, all 32 slots written; selected = count) instead of out += counters, selected += count;
+ * bit 1 = superset (slots 0 / 16 = primary paired reads among the selected, slot 9 = selected minus slot 25).  `selected` /
+ * `d_selected` may be NULL: nothing is reported.  n == 0 succeeds and touches nothing (the store form writes zeros); `sel` may
+ * be NULL then.
+ * Refused (non-zero, message in FLAGSTATS_hip_last_error, out and selected untouched, nothing launched): sel_bits other than 1
+ * or 8, an odd array pointer, flag bits other than 0 and 1, a NULL array or selection with n > 0, a sel_offset + n that is no
+ * index; for the device forms also a d_out or d_selected that is not plain device memory, pointers on different devices, a
+ * stream of another device and an allocation shorter than the call needs (d_array: n * 2 bytes, d_sel: the bytes that hold the
+ * n bits or bytes, d_out: 256, d_selected: 8). */
+/* DEVICE array and selection, DEVICE d_out[32] and d_selected[1] (uint64); asynchronous on `stream`: ONE kernel (the store form
+ * puts one memset per pointer in front of it; one in all when d_selected == d_out + 32), no workspace.  Adds are atomic: launches
+ * on several streams may share d_out and d_selected in the += form. */
+int FLAGSTATS_hip_device_u16_where(const uint16_t* d_array, uint64_t n, const void* d_sel, uint64_t sel_offset, int sel_bits,
+                                   uint64_t* d_out, uint64_t* d_selected, int flags, void* stream);
+/* DEVICE array and selection, HOST out[32] and selected[1]; synchronous */
+int FLAGSTATS_hip_device_u16_where_sync(const uint16_t* d_array, uint64_t n, const void* d_sel, uint64_t sel_offset, int sel_bits,
+                                        uint64_t* out, uint64_t* selected, int flags);
+/* HOST array and selection, HOST out[32] and selected[1]; synchronous.  Array and selection cross the bus in the engine's chunks
+ * (knob "chunk_flags"), each chunk's slice of the selection with its flags; the counters are summed on the device. */
+int FLAGSTATS_hip_u16_x64_where(const uint16_t* array, uint64_t n, const void* sel, uint64_t sel_offset, int sel_bits,
+                                uint64_t* out, uint64_t* selected, int flags);
+
 /* 64-bit positional popcount in this library's convention: out[16] += bit counts (host array / device array) */
 int FLAGSTATS_hip_pospopcnt_u16_x64(const uint16_t* array, uint64_t n, uint64_t* out);
 int FLAGSTATS_hip_device_pospopcnt_u16(const uint16_t* d_array, uint64_t n, uint64_t* d_out, void* stream);

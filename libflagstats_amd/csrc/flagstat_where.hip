@@ -1,0 +1,662 @@
+// flagstat_where.hip -- flagstat of the SELECTED elements of a uint16 FLAG array: the 32 counters of {array[i] : sel(i)} and the
+// number of selected elements, in one pass over the array and its selection.  The selection is an LSB-first bitmap (Arrow's
+// validity layout, np.packbits(bitorder="little")) that may start at any bit, or one byte per element (numpy / torch bool).
+//
+// Geometry.  K1's: the array is addressed on the 16-byte grid of its aligned-down base, the caller's flags occupy positions
+// [lo, hi) of it, and it is cut into steps of 32 KiB = 16,384 flags (256 lanes x 8 vectors of 16 B); workgroup b takes the head
+// edge step (b == 0), the tail edge step, then the fully covered steps b, b + G, ...; each wave owns a contiguous 8 KiB of a
+// step and lane l takes vectors u * 64 + l.  Edge steps go through guarded, zero-filling loaders; fast steps through K1's
+// rolling load schedule (schedule 71: a vector's registers are re-issued for the vector six places on as soon as it has been
+// read out), restated below from flagstat_kernels.hip.  tests/steps_oracle.StepSplit(addr % 16, n, grid) is the step split.
+//
+// Selection.  The selection is addressed on the array's grid as well: the launcher hands the kernel a base pointer `sel` such
+// that the 8 bits of grid vector j start at bit `sh` of sel[j] (bitmap: sh == 0 takes one byte per vector, otherwise two are
+// funnelled together), or such that its 8 bytes are sel[8 j .. 8 j + 8) (byte form, at any alignment).  A wave's 64 lanes thus
+// read 64 consecutive selection bytes (bitmap) or 512 (bytes) per vector.
+// A zero flag counts nothing in any slot, so selecting is zeroing the flags that are not selected, in front of front4:
+//   bitmap:  in the split itself.  split_out's four v_perm_b32 take their byte selectors from registers, and a selector byte
+//            of 0x0C writes 0x00: a 256-entry table in LDS (4 KiB, built by the workgroup's 256 threads) maps a selection
+//            byte to the four selectors with 0x0C for every flag that is not selected.  Per vector of 8 flags: v_lshlrev_b32
+//            (the table offset; v_bfe_u32 in front when the bits are funnelled), ds_read_b128, v_bcnt_u32_b32 for the number
+//            selected -- 1 to 1.5 VALU ops per 4 flags.  The selection byte of a vector is loaded one vector ahead of it, so
+//            the table read of vector u + 1 is in flight while vector u is counted.
+//   bytes:   on the byte planes L and H.  Per 4 flags v_and_b32, v_add_u32, v_bitop3_b32 (bit 7 of a byte = byte != 0),
+//            v_lshrrev_b32, v_perm_b32 (0x01 -> 0xFF), 2 x v_and_b32 (some fused by the compiler with front4's first ops),
+//            v_bcnt_u32_b32: 8 VALU ops.  This form moves 3 B per flag and runs at 0.955-0.962 of K1's byte rate
+//            (profiles/r10/where_sweep.log); whether these ops or its loads cost the 4 % has not been determined.
+// Only selection bytes that hold the bit or byte of an element in [0, n) are read: on fast steps every position of a vector
+// is an element; the edge loaders look at [lo, hi) for every byte.
+//
+// Epilogue.  K1's direct one: every workgroup maps its 21 totals to the 32 slots and adds them to out[32] with relaxed
+// agent-scope atomics; its number of selected elements goes to *selected the same way and is what the superset slot 9 takes for
+// the flag count (the per-workgroup partial sums wrap modulo 2^64: slot_value, flagstat_count_core.h).  No workspace, no second
+// kernel; the store form zeroes counters and `selected` in front (one memset).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cstdio>
+#include <mutex>
+
+#include "../../include/libflagstats_hip.h"
+#include "flagstat_count_core.h"
+#include "flagstat_engine.h"
+#include "flagstat_where.h"
+
+namespace fsk {
+
+constexpr int kWhereDepth = 8;        // chain depth as K1: epochs of 255 steps
+
+// what a lane holds of the selection per vector: the byte (two, funnelled) with its 8 bits, or its 8 bytes
+template <int SEL_BITS>
+struct SelWord {
+    typedef uint32_t type;
+};
+template <>
+struct SelWord<8> {
+    typedef uint2 type;
+};
+
+typedef uint16_t u16_any __attribute__((aligned(1)));
+typedef uint32_t u32x2_any __attribute__((ext_vector_type(2), aligned(1)));
+
+// the selection of one vector on a fast step (every position is an element)
+template <int SEL_BITS, bool FUNNEL>
+__device__ __forceinline__ typename SelWord<SEL_BITS>::type load_sel(const uint8_t* __restrict__ p)
+{
+    if constexpr (SEL_BITS == 1) {
+        if constexpr (FUNNEL)
+            return __builtin_nontemporal_load(reinterpret_cast<const u16_any*>(p));
+        else
+            return __builtin_nontemporal_load(p);
+    } else {
+        const u32x2_any t = __builtin_nontemporal_load(reinterpret_cast<const u32x2_any*>(p));
+        return make_uint2(t.x, t.y);
+    }
+}
+
+// the selection of vector j on an edge step: positions outside [lo, hi) read as not selected and their bytes are not touched.
+// Bitmap form: the 8 bits come back at bit 0 (the step then runs with sh == 0).
+template <int SEL_BITS>
+__device__ __forceinline__ typename SelWord<SEL_BITS>::type load_sel_guarded(const uint8_t* __restrict__ sel, uint32_t sh, uint64_t j,
+                                                                             uint64_t lo, uint64_t hi)
+{
+    const uint64_t f0 = j * 8;
+    if constexpr (SEL_BITS == 1) {
+        if (f0 + 8 <= lo || f0 >= hi) return 0u;
+        const uint32_t e0 = f0 >= lo ? 0u : static_cast<uint32_t>(lo - f0);            // first and last position that is an element
+        const uint32_t e1 = f0 + 8 <= hi ? 7u : static_cast<uint32_t>(hi - 1 - f0);
+        uint32_t w = 0;
+        if (e0 + sh < 8) w = sel[j];
+        if (e1 + sh >= 8) w |= static_cast<uint32_t>(sel[j + 1]) << 8;
+        return (w >> sh) & (0xFFu >> (7 - e1)) & (0xFFu << e0);
+    } else {
+        uint32_t w[2] = {0, 0};
+        if (f0 + 8 <= lo || f0 >= hi) return make_uint2(0, 0);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const uint64_t f = f0 + e;
+            if (f >= lo && f < hi) w[e >> 2] |= static_cast<uint32_t>(sel[f]) << (8 * (e & 3));
+        }
+        return make_uint2(w[0], w[1]);
+    }
+}
+
+// 4 selection bits (bit k = flag k) to 4 byte masks
+__device__ __forceinline__ uint32_t nibble_mask(uint32_t nib)
+{
+    // bit k lands on bits k, k + 7, k + 14, k + 21, all distinct for k < 4: bit 8 k is bit k
+    return perm(0u, 0x0000FF00u, __umul24(nib, 0x204081u) & 0x01010101u);
+}
+
+// 4 selection bytes to 4 byte masks (any non-zero byte selects); s = 0x01 per selected flag
+__device__ __forceinline__ uint32_t bytes_mask(uint32_t x, uint32_t& s)
+{
+    const uint32_t t = (x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;   // bit 7 of a byte: one of its bits 0-6 is set (no carry leaves a byte)
+    s = ((t | x) & 0x80808080u) >> 7;
+    return perm(0u, 0x0000FF00u, s);
+}
+
+// the byte masks of a vector's flags 0-3 and 4-7 in the byte form; the number selected is added to cnt
+__device__ __forceinline__ void bytes_masks(const uint2& w, uint32_t& M0, uint32_t& M1, uint32_t& cnt)
+{
+    uint32_t s0, s1;
+    M0 = bytes_mask(w.x, s0);
+    M1 = bytes_mask(w.y, s1);
+    cnt += __builtin_popcount(s0);
+    cnt += __builtin_popcount(s1);
+}
+
+// Bitmap form: the mask costs no VALU op of its own.  split_out's four v_perm_b32 take their byte selectors from registers
+// instead of constants, and a selector byte of 0x0C makes v_perm_b32 write 0x00: entry i of a 256-entry table in LDS holds, for
+// the selection byte i, the four selectors (low and high byte planes of flags 0-3 and of flags 4-7) in which every flag that is
+// not selected has 0x0C.  One ds_read_b128 per vector fetches them.
+constexpr uint32_t kSplitLo = 0x06040200u, kSplitHi = 0x07050301u;   // split_out's selectors
+
+__device__ __forceinline__ uint4 selector_entry(uint32_t i)
+{
+    const uint32_t M0 = nibble_mask(i & 15u), M1 = nibble_mask(i >> 4);
+    return make_uint4((kSplitLo & M0) | (0x0C0C0C0Cu & ~M0), (kSplitHi & M0) | (0x0C0C0C0Cu & ~M0), (kSplitLo & M1) | (0x0C0C0C0Cu & ~M1),
+                      (kSplitHi & M1) | (0x0C0C0C0Cu & ~M1));
+}
+
+// split_out (flagstat_count_core.h) under the selectors of a table entry: the planes of the selected flags, zero elsewhere
+__device__ __forceinline__ void split_out_selected(const uint4& o, const uint4& sel, uint32_t& L0, uint32_t& H0, uint32_t& L1, uint32_t& H1)
+{
+    asm volatile("v_perm_b32 %0, %5, %4, %8\n\tv_perm_b32 %1, %5, %4, %9\n\tv_perm_b32 %2, %7, %6, %10\n\tv_perm_b32 %3, %7, %6, %11"
+                 : "=&v"(L0), "=&v"(H0), "=&v"(L1), "=&v"(H1)
+                 : "v"(o.x), "v"(o.y), "v"(o.z), "v"(o.w), "v"(sel.x), "v"(sel.y), "v"(sel.z), "v"(sel.w));
+}
+
+// the table entry of the vector whose 8 selection bits start at bit sh of w; the number selected is added to cnt
+__device__ __forceinline__ uint4 lookup(const uint4* __restrict__ lut, uint32_t w, uint32_t sh, uint32_t& cnt)
+{
+    const uint32_t bits = __builtin_amdgcn_ubfe(w, sh, 8);
+    cnt += __builtin_popcount(bits);
+    return lut[bits];
+}
+
+// One step: 8 vectors of 16 B per lane = 64 flags -> 16 T, 16 F, 16 S inputs through K1's tree (flagstat_kernels.hip: step).
+// ROLL 0: the vectors are in v[], their selection in m[].  ROLL 1, 2: K1's schedule 71 -- vector u's registers are re-issued for
+// vector u + 6 of the same step (`cur`) or, ROLL 1 only, u - 2 of the next one (`next`): 6 loads = 24 KiB per CU in flight.
+// Byte form: the selection of a vector is loaded right in front of it and read out with it.  Bitmap form: the selection byte
+// of a vector is loaded in front of the vector BEFORE it, so that it has arrived when that one has; its table entry is
+// fetched while that one is being counted and handed on in `entry` (on entry: vector 0's; on exit, ROLL 1: the next step's
+// vector 0's).
+template <int SEL_BITS, bool FUNNEL, int ROLL>
+__device__ __forceinline__ void where_step(Lane<kWhereDepth>& s, uint4 (&v)[kUnroll], typename SelWord<SEL_BITS>::type (&m)[kUnroll],
+                                           uint4& entry, const uint4* __restrict__ lut, uint32_t blk, uint32_t sh, uint32_t& cnt,
+                                           const uint4* __restrict__ cur, const uint4* __restrict__ next, const uint8_t* __restrict__ scur,
+                                           const uint8_t* __restrict__ snext)
+{
+    constexpr int RD = 6;
+    constexpr int US = 64;                              // each wave a contiguous 8 KiB of the step
+    constexpr int SS = SEL_BITS == 1 ? US : US * 8;     // selection bytes between a lane's consecutive vectors
+    uint32_t t8a = 0, t8b = 0, f8a = 0, f8b = 0, s8a = 0, s8b = 0;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        uint32_t t4a = 0, t4b = 0, f4a = 0, f4b = 0, s4a = 0, s4b = 0;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            uint32_t T[4], F[4], S[4];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                uint32_t L0, H0, L1, H1;
+                const int uu = half * 4 + q * 2 + k;  // a constant after unrolling
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (SEL_BITS == 1) {
+                    split_out_selected(v[uu], entry, L0, H0, L1, H1);
+                    if (uu + 1 < kUnroll || ROLL == 1) entry = lookup(lut, m[(uu + 1) % kUnroll], sh, cnt);
+                    if constexpr (ROLL != 0) {
+                        if (uu + RD + 1 < kUnroll)
+                            m[uu + RD + 1] = load_sel<SEL_BITS, FUNNEL>(scur + (uu + RD + 1) * SS);
+                        else if constexpr (ROLL == 1)
+                            m[uu + RD + 1 - kUnroll] = load_sel<SEL_BITS, FUNNEL>(snext + (uu + RD + 1 - kUnroll) * SS);
+                    }
+                } else {
+                    split_out(v[uu], L0, H0, L1, H1);
+                    const uint2 w = m[uu];
+                    if constexpr (ROLL != 0) {
+                        if (uu + RD < kUnroll)
+                            m[uu + RD] = load_sel<SEL_BITS, FUNNEL>(scur + (uu + RD) * SS);
+                        else if constexpr (ROLL == 1)
+                            m[uu + RD - kUnroll] = load_sel<SEL_BITS, FUNNEL>(snext + (uu + RD - kUnroll) * SS);
+                    }
+                    uint32_t M0, M1;
+                    bytes_masks(w, M0, M1, cnt);
+                    L0 &= M0;
+                    H0 &= M0;
+                    L1 &= M1;
+                    H1 &= M1;
+                }
+                if constexpr (ROLL != 0) {
+                    if (uu + RD < kUnroll)
+                        v[uu + RD] = load_vec<true>(cur + (uu + RD) * US);
+                    else if constexpr (ROLL == 1)
+                        v[uu + RD - kUnroll] = load_vec<true>(next + (uu + RD - kUnroll) * US);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                uint32_t qa, qb, ka, kb;
+                front4(L0, H0, T[2 * k], qa, ka);
+                front4(L1, H1, T[2 * k + 1], qb, kb);
+                F[2 * k] = T[2 * k] & perm(0u, 0xFF00FF00u, qa);
+                F[2 * k + 1] = T[2 * k + 1] & perm(0u, 0xFF00FF00u, qb);
+                S[2 * k] = perm(0u, 0x84428140u, qa) & (ka | 0x3F3F3F3Fu);
+                S[2 * k + 1] = perm(0u, 0x84428140u, qb) & (kb | 0x3F3F3F3Fu);
+            }
+            uint32_t t2a, t2b, f2a, f2b, s2a, s2b;
+            csa(t2a, s.t1, s.t1, T[0], T[1]);
+            csa(t2b, s.t1, s.t1, T[2], T[3]);
+            csa(f2a, s.f1, s.f1, F[0], F[1]);
+            csa(f2b, s.f1, s.f1, F[2], F[3]);
+            csa(s2a, s.s1, s.s1, S[0], S[1]);
+            csa(s2b, s.s1, s.s1, S[2], S[3]);
+            csa(q ? t4b : t4a, s.t2, s.t2, t2a, t2b);
+            csa(q ? f4b : f4a, s.f2, s.f2, f2a, f2b);
+            csa(q ? s4b : s4a, s.s2, s.s2, s2a, s2b);
+        }
+        csa(half ? t8b : t8a, s.t4, s.t4, t4a, t4b);
+        csa(half ? f8b : f8a, s.f4, s.f4, f4a, f4b);
+        csa(half ? s8b : s8a, s.s4, s.s4, s4a, s4b);
+    }
+    uint32_t ct, cf, cs;
+    csa(ct, s.t8, s.t8, t8a, t8b);  // weight-16 carries
+    csa(cf, s.f8, s.f8, f8a, f8b);
+    csa(cs, s.s8, s.s8, s8a, s8b);
+    chain_push<0, kWhereDepth>(s, blk, ct, cf, cs);
+}
+
+template <int SEL_BITS, bool FUNNEL, int ROLL>
+__device__ __forceinline__ void where_step_and_count(Lane<kWhereDepth>& s, uint4 (&v)[kUnroll], typename SelWord<SEL_BITS>::type (&m)[kUnroll],
+                                                     uint4& entry, const uint4* __restrict__ lut, uint32_t& blk, uint32_t sh, uint32_t& cnt,
+                                                     const uint4* __restrict__ cur = nullptr, const uint4* __restrict__ next = nullptr,
+                                                     const uint8_t* __restrict__ scur = nullptr, const uint8_t* __restrict__ snext = nullptr)
+{
+    blk = __builtin_amdgcn_readfirstlane(blk);
+    where_step<SEL_BITS, FUNNEL, ROLL>(s, v, m, entry, lut, blk, sh, cnt, cur, next, scur, snext);
+    ++blk;
+    if (blk == (1u << kWhereDepth) - 1u) {
+        flush(s, (1u << kWhereDepth) - 1u);
+        blk = 0;
+    }
+}
+
+// a0: 16-B aligned-down base; the caller's flags occupy positions [lo, hi) of its grid.  sel, shift: the selection on the same
+// grid (see above; FUNNEL: shift != 0).  mode: bit 1 superset (bit 0, the store form, is the launcher's memset).  selected may
+// be nullptr.
+template <int SEL_BITS, bool FUNNEL = false>
+__global__ __launch_bounds__(kThreads) void flagstat_count_where(const uint4* __restrict__ a0, const uint8_t* __restrict__ sel, uint32_t shift,
+                                                                 uint64_t lo, uint64_t hi, uint64_t nsteps, uint64_t fast_begin,
+                                                                 uint64_t fast_end, uint64_t* __restrict__ out,
+                                                                 uint64_t* __restrict__ selected, int mode)
+{
+    static_assert(SEL_BITS == 1 || (SEL_BITS == 8 && !FUNNEL), "a bitmap (at a byte boundary of the grid or not) or bytes");
+    static_assert(kThreads == 256, "one thread per table entry");
+    typedef typename SelWord<SEL_BITS>::type sel_t;
+    __shared__ uint4 lut[SEL_BITS == 1 ? 256 : 1];
+    if constexpr (SEL_BITS == 1) {
+        lut[threadIdx.x] = selector_entry(threadIdx.x);
+        __syncthreads();
+    }
+    Lane<kWhereDepth> s;
+    lane_init(s);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = threadIdx.x >> 6;
+    constexpr int VPS = kVecPerStep;
+    constexpr int US = 64;
+    constexpr int SB = SEL_BITS == 1 ? 1 : 8;   // selection bytes per vector
+    const uint64_t lane_off = static_cast<uint64_t>(wave) * (64 * kUnroll) + lane;
+    const uint64_t G = gridDim.x;
+    // wave w starts its first epoch at 64 * w, so at most one wave of a CU is flushing at any time (K1's mode bit 4)
+    uint32_t blk = (wave & 3u) * 64u;
+    uint32_t cnt = 0;                           // selected elements of this lane
+    const uint32_t sh = FUNNEL ? __builtin_amdgcn_readfirstlane(shift) : 0u;
+    uint4 entry = make_uint4(0, 0, 0, 0);       // bitmap form: the table entry of the vector that is counted next
+
+    auto edge_step = [&](uint64_t st) {
+        uint4 v[kUnroll];
+        sel_t m[kUnroll];
+        const uint64_t j0 = st * VPS + lane_off;
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            v[u] = load_guarded(a0, j0 + u * US, lo, hi);
+            m[u] = load_sel_guarded<SEL_BITS>(sel, shift, j0 + u * US, lo, hi);
+        }
+        if constexpr (SEL_BITS == 1) entry = lookup(lut, m[0], 0u, cnt);
+        where_step_and_count<SEL_BITS, false, 0>(s, v, m, entry, lut, blk, 0u, cnt);
+    };
+    // ragged edge steps (at most the first and the last of the whole array), outside the pipelined loop
+    if (fast_begin != 0 && blockIdx.x == 0) edge_step(0);
+    if (nsteps > fast_end && nsteps - 1 >= fast_begin && (nsteps - 1) % G == blockIdx.x) edge_step(nsteps - 1);
+    // first fully in-range step of this workgroup
+    uint64_t st = blockIdx.x;
+    if (st < fast_begin) st += G;  // fast_begin is 0 or 1
+    if (st < fast_end) {
+        constexpr int RD = 6;
+        uint4 v[kUnroll];
+        sel_t m[kUnroll];
+        const uint4* p = a0 + st * VPS + lane_off;
+        const uint8_t* ps = sel + (st * VPS + lane_off) * SB;
+        // the first RD vectors; the rest is issued as they are consumed.  The bitmap's bytes run one vector ahead.
+        if constexpr (SEL_BITS == 1) m[0] = load_sel<SEL_BITS, FUNNEL>(ps);
+#pragma unroll
+        for (int u = 0; u < RD; ++u) {
+            if constexpr (SEL_BITS == 1)
+                m[u + 1] = load_sel<SEL_BITS, FUNNEL>(ps + (u + 1) * US * SB);
+            else
+                m[u] = load_sel<SEL_BITS, FUNNEL>(ps + u * US * SB);
+            v[u] = load_vec<true>(p + u * US);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (SEL_BITS == 1) entry = lookup(lut, m[0], sh, cnt);
+        for (; st + G < fast_end; st += G) {
+            const uint4* pn = p + G * VPS;
+            const uint8_t* psn = ps + G * VPS * SB;
+            where_step_and_count<SEL_BITS, FUNNEL, 1>(s, v, m, entry, lut, blk, sh, cnt, p, pn, ps, psn);
+            p = pn;
+            ps = psn;
+        }
+        where_step_and_count<SEL_BITS, FUNNEL, 2>(s, v, m, entry, lut, blk, sh, cnt, p, nullptr, ps, nullptr);
+    }
+    flush(s, blk);
+
+    // wave sums on the VALU (DPP), then the 4 waves through LDS; word kInternal is the number of selected elements
+    constexpr int kWaves = kThreads / 64;
+    __shared__ uint32_t red[kWaves][kInternal + 1];
+    __shared__ uint64_t wg_tot[32];
+    uint32_t wsum[kInternal + 1];
+#pragma unroll
+    for (int c = 0; c < kInternal; ++c) wsum[c] = wave_sum_lane63(s.acc[c]);
+    wsum[kInternal] = wave_sum_lane63(cnt);
+    if (lane == 63) {
+#pragma unroll
+        for (int c = 0; c <= kInternal; ++c) red[wave][c] = wsum[c];
+    }
+    __syncthreads();
+    if (threadIdx.x <= kInternal) {
+        uint64_t sum = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) sum += red[w][threadIdx.x];
+        wg_tot[threadIdx.x] = sum;
+    }
+    __syncthreads();
+    const uint64_t wg_selected = wg_tot[kInternal];
+    if (threadIdx.x == 64 && selected != nullptr && wg_selected)
+        (void)__hip_atomic_fetch_add(selected, wg_selected, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // this workgroup's totals, mapped to the reference's slots, added to out[32]; every workgroup enters its own number of
+    // selected elements into slot 9 (superset)
+    finalize_slots<true>(wg_tot, out, mode, wg_selected);
+}
+
+}  // namespace fsk
+
+// ------------------------------------------------------------------ launcher
+// Host-side geometry: everything the kernel assumes is derived here from (address, n, sel_offset, sel_bits).
+extern "C" hipError_t fsk_where_geometry(uint64_t address, uint64_t n, uint64_t sel_offset, int sel_bits, uint32_t grid, uint64_t* geo)
+{
+    if ((sel_bits != 1 && sel_bits != 8) || grid == 0 || geo == nullptr) return hipErrorInvalidValue;
+    const uint64_t addr = address;
+    if (addr & 1u) return hipErrorInvalidValue;
+    for (int i = 0; i < 8; ++i) geo[i] = 0;
+    if (n == 0) return hipSuccess;
+    if (n > (~0ull - 64) / 2) return hipErrorInvalidValue;  // n * 2 must be a size
+    if (sel_offset > ~0ull - 64 - n) return hipErrorInvalidValue;  // sel_offset + n must be an index
+    const uint64_t base = addr & ~static_cast<uint64_t>(15);
+    const uint64_t lo = (addr - base) / 2, hi = lo + n;
+    const uint64_t nvec = (hi + 7) / 8;
+    const uint64_t vps = fsk::kVecPerStep;
+    const uint64_t nsteps = (nvec + vps - 1) / vps;
+    // steps whose vectors are all fully inside [lo, hi)
+    uint64_t fast_begin = (lo == 0) ? 0 : 1;
+    uint64_t fast_end = (hi / 8) / vps;
+    if (fast_end < fast_begin) fast_end = fast_begin;
+    if (static_cast<uint64_t>(grid) > nsteps) grid = static_cast<uint32_t>(nsteps);
+    // a wave's totals are uint32: a workgroup pushes at most ceil(nsteps / grid) + 2 steps (its share and both edge steps), each
+    // wave a quarter of every step
+    const uint64_t wave_elems_per_step = fsk::kVecPerStep * 8 / (fsk::kThreads / 64);
+    if (nsteps / grid + 3 >= (1ull << 32) / wave_elems_per_step) return hipErrorInvalidValue;
+    geo[0] = lo;
+    geo[1] = hi;
+    geo[2] = nsteps;
+    geo[3] = fast_begin;
+    geo[4] = fast_end;
+    geo[5] = grid;
+    // the selection bytes that hold the bit or byte of an element
+    geo[6] = sel_bits == 1 ? sel_offset >> 3 : sel_offset;
+    geo[7] = sel_bits == 1 ? ((sel_offset + n - 1) >> 3) + 1 : sel_offset + n;
+    return hipSuccess;
+}
+
+extern "C" hipError_t fsk_launch_where(const uint16_t* d_array, uint64_t n, const void* d_sel, uint64_t sel_offset, int sel_bits,
+                                       uint64_t* d_out32, uint64_t* d_selected, int mode, uint32_t grid, hipStream_t stream)
+{
+    if ((sel_bits != 1 && sel_bits != 8) || (mode & ~3) || grid == 0 || d_out32 == nullptr || (n && (d_array == nullptr || d_sel == nullptr)))
+        return hipErrorInvalidValue;
+    uint64_t geo[8];
+    hipError_t e = fsk_where_geometry(reinterpret_cast<uintptr_t>(d_array), n, sel_offset, sel_bits, grid, geo);
+    if (e != hipSuccess) return e;
+    if (mode & 1) {
+        // counters and the selected count in one memset where they are one allocation's 33 words
+        const bool together = d_selected == d_out32 + 32;
+        e = hipMemsetAsync(d_out32, 0, (together ? 33 : 32) * sizeof(uint64_t), stream);
+        if (e == hipSuccess && d_selected && !together) e = hipMemsetAsync(d_selected, 0, sizeof(uint64_t), stream);
+        if (e != hipSuccess) return e;
+    }
+    if (n == 0) return hipSuccess;
+    const uint4* a0 = reinterpret_cast<const uint4*>(reinterpret_cast<uintptr_t>(d_array) & ~static_cast<uintptr_t>(15));
+    const dim3 g(static_cast<uint32_t>(geo[5])), b(fsk::kThreads);
+    const uintptr_t sel0 = reinterpret_cast<uintptr_t>(d_sel);
+    const uint64_t lo = geo[0];
+    if (sel_bits == 8) {
+        // grid position q is element q - lo: its byte is d_sel[sel_offset + q - lo]
+        const uint8_t* sel = reinterpret_cast<const uint8_t*>(sel0 + sel_offset - lo);
+        hipLaunchKernelGGL((fsk::flagstat_count_where<8>), g, b, 0, stream, a0, sel, 0u, geo[0], geo[1], geo[2], geo[3], geo[4], d_out32,
+                           d_selected, mode & 2);
+        return hipGetLastError();
+    }
+    // grid position q is element q - lo: its bit is bit sel_offset + q - lo = q + (bit0 - 8), where bit0 >= 1
+    const uint64_t bit0 = sel_offset + 8 - lo;
+    const uint8_t* sel = reinterpret_cast<const uint8_t*>(sel0 + (bit0 >> 3) - 1);
+    const uint32_t shift = static_cast<uint32_t>(bit0 & 7);
+    if (shift == 0)
+        hipLaunchKernelGGL((fsk::flagstat_count_where<1, false>), g, b, 0, stream, a0, sel, 0u, geo[0], geo[1], geo[2], geo[3], geo[4],
+                           d_out32, d_selected, mode & 2);
+    else
+        hipLaunchKernelGGL((fsk::flagstat_count_where<1, true>), g, b, 0, stream, a0, sel, shift, geo[0], geo[1], geo[2], geo[3], geo[4],
+                           d_out32, d_selected, mode & 2);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ C entry points (include/libflagstats_hip.h)
+using fsint::DeviceGuard;
+using fsint::Engine;
+using fsint::fail_hip;
+using fsint::fail_text;
+
+namespace {
+
+// what every form refuses before it touches the GPU
+int where_args(const uint16_t* array, uint64_t n, const void* sel, uint64_t sel_offset, int sel_bits, const void* out, int flags)
+{
+    if (sel_bits != 1 && sel_bits != 8) return fail_text("sel_bits must be 1 (an LSB-first bitmap) or 8 (one byte per element)");
+    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
+    if (n && !array) return fail_text("NULL array with n > 0");
+    if (n && !sel) return fail_text("NULL selection with n > 0");
+    if (reinterpret_cast<uintptr_t>(array) & 1u) return fail_text("array must be 2-byte aligned");
+    if (n > (~0ull - 64) / 2) return fail_text("n * 2 is not a size");
+    if (sel_offset > ~0ull - 64 - n) return fail_text("sel_offset + n is not an index");
+    if (!out && (n || (flags & 1))) return fail_text("NULL counters");
+    return 0;
+}
+
+// the bytes of the selection that hold an element's bit or byte: [first, first + bytes) from `sel` on (n > 0).  The device
+// entries check the allocation from `sel` itself up to first + bytes: only `sel` is known to be device memory, and an offset at
+// or past the allocation's end would otherwise name an address the runtime cannot vouch for
+void where_extent(uint64_t n, uint64_t sel_offset, int sel_bits, uint64_t* first, uint64_t* bytes)
+{
+    *first = sel_bits == 1 ? sel_offset >> 3 : sel_offset;
+    *bytes = (sel_bits == 1 ? ((sel_offset + n - 1) >> 3) + 1 : sel_offset + n) - *first;
+}
+
+// device counters[32] + selected count of one synchronous call
+struct WhereRow {
+    uint64_t* d = nullptr;
+    ~WhereRow()
+    {
+        if (d) (void)hipFree(d);
+    }
+    int alloc()
+    {
+        const hipError_t e = hipMalloc(&d, 33 * sizeof(uint64_t));
+        if (e != hipSuccess) {
+            d = nullptr;
+            return fail_hip("hipMalloc(where counters)", e);
+        }
+        return 0;
+    }
+};
+
+void where_apply(uint64_t* out, uint64_t* selected, const uint64_t (&got)[33], int flags)
+{
+    if (flags & 1) {
+        for (int i = 0; i < 32; ++i) out[i] = got[i];
+        if (selected) *selected = got[32];
+    } else {
+        for (int i = 0; i < 32; ++i) out[i] += got[i];
+        if (selected) *selected += got[32];
+    }
+}
+
+void where_nothing(uint64_t* out, uint64_t* selected, int flags)
+{
+    if (flags & 1) {
+        for (int i = 0; i < 32; ++i) out[i] = 0;
+        if (selected) *selected = 0;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int FLAGSTATS_hip_device_u16_where(const uint16_t* d_array, uint64_t n, const void* d_sel, uint64_t sel_offset, int sel_bits,
+                                   uint64_t* d_out, uint64_t* d_selected, int flags, void* stream)
+{
+    FS_ENTRY();
+    int rc = where_args(d_array, n, d_sel, sel_offset, sel_bits, d_out, flags);
+    if (rc) return rc;
+    if (n == 0 && !(flags & 1)) return 0;
+    int dev_out = -1, dev = -1;
+    bool plain = false;
+    rc = fsint::device_of_pointer(d_out, "d_out", &dev_out, &plain);
+    if (rc) return rc;
+    if (!plain) return fail_text("d_out must be device memory (the counters are added with device atomics)");
+    if (d_selected) {
+        rc = fsint::device_of_pointer(d_selected, "d_selected", &dev, &plain);
+        if (rc) return rc;
+        if (!plain) return fail_text("d_selected must be device memory (the count is added with a device atomic)");
+        if (dev != dev_out) return fail_text("d_selected and d_out live on different devices");
+    }
+    if (n) {
+        rc = fsint::device_of_pointer(d_array, "d_array", &dev);
+        if (rc) return rc;
+        if (dev != dev_out) return fail_text("d_array and d_out live on different devices");
+        rc = fsint::device_of_pointer(d_sel, "d_sel", &dev);
+        if (rc) return rc;
+        if (dev != dev_out) return fail_text("d_sel and d_out live on different devices");
+    }
+    Engine* e = fsint::engine_for_device(dev_out);
+    if (!e) return -1;
+    DeviceGuard guard(e->device);
+    if (!guard.ok()) return -1;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = fsint::check_stream_device(s, e->device);
+    if (rc) return rc;
+    if ((rc = fsint::check_extent(d_out, 32 * sizeof(uint64_t), "d_out"))) return rc;
+    if (d_selected && (rc = fsint::check_extent(d_selected, sizeof(uint64_t), "d_selected"))) return rc;
+    if (n) {
+        if ((rc = fsint::check_extent(d_array, n * 2, "d_array"))) return rc;
+        uint64_t first, bytes;
+        where_extent(n, sel_offset, sel_bits, &first, &bytes);
+        if ((rc = fsint::check_extent(d_sel, first + bytes, "d_sel"))) return rc;
+    }
+    FS_HIP_TRY(fsk_launch_where(d_array, n, d_sel, sel_offset, sel_bits, d_out, d_selected, flags & 3, fsint::grid_for(*e), s));
+    return 0;
+}
+
+int FLAGSTATS_hip_device_u16_where_sync(const uint16_t* d_array, uint64_t n, const void* d_sel, uint64_t sel_offset, int sel_bits,
+                                        uint64_t* out, uint64_t* selected, int flags)
+{
+    FS_ENTRY();
+    int rc = where_args(d_array, n, d_sel, sel_offset, sel_bits, out, flags);
+    if (rc) return rc;
+    if (n == 0) {
+        where_nothing(out, selected, flags);
+        return 0;
+    }
+    int dev = -1, dev_sel = -1;
+    rc = fsint::device_of_pointer(d_array, "d_array", &dev);
+    if (rc) return rc;
+    rc = fsint::device_of_pointer(d_sel, "d_sel", &dev_sel);
+    if (rc) return rc;
+    if (dev_sel != dev) return fail_text("d_sel and d_array live on different devices");
+    Engine* ep = fsint::engine_for_device(dev);
+    if (!ep) return -1;
+    Engine& e = *ep;
+    std::lock_guard<std::mutex> lk(e.mu);
+    if (fsint::engine_alive(e)) return -1;
+    DeviceGuard guard(e.device);
+    if (!guard.ok()) return -1;
+    if ((rc = fsint::check_extent(d_array, n * 2, "d_array"))) return rc;
+    uint64_t first, bytes;
+    where_extent(n, sel_offset, sel_bits, &first, &bytes);
+    if ((rc = fsint::check_extent(d_sel, first + bytes, "d_sel"))) return rc;
+    WhereRow row;
+    if ((rc = row.alloc())) return rc;
+    uint64_t got[33];
+    hipStream_t s = e.stream[0];
+    FS_HIP_TRY(fsk_launch_where(d_array, n, d_sel, sel_offset, sel_bits, row.d, row.d + 32, 1 | (flags & 2), fsint::grid_for(e), s));
+    FS_HIP_TRY(hipMemcpyAsync(got, row.d, sizeof got, hipMemcpyDeviceToHost, s));
+    FS_HIP_TRY(hipStreamSynchronize(s));
+    where_apply(out, selected, got, flags);
+    return 0;
+}
+
+int FLAGSTATS_hip_u16_x64_where(const uint16_t* array, uint64_t n, const void* sel, uint64_t sel_offset, int sel_bits, uint64_t* out,
+                                uint64_t* selected, int flags)
+{
+    FS_ENTRY();
+    int rc = where_args(array, n, sel, sel_offset, sel_bits, out, flags);
+    if (rc) return rc;
+    if (n == 0) {
+        where_nothing(out, selected, flags);
+        return 0;
+    }
+    Engine* ep = fsint::default_engine();
+    if (!ep) return -1;
+    Engine& e = *ep;
+    std::lock_guard<std::mutex> lk(e.mu);
+    if (fsint::engine_alive(e)) return -1;
+    DeviceGuard guard(e.device);
+    if (!guard.ok()) return -1;
+    fsint::lz4_gpu_other_use(e);
+    WhereRow row;
+    if ((rc = row.alloc())) return rc;
+    if ((rc = fsint::engine_second(e))) return rc;
+    // the array crosses the bus in chunks of "chunk_flags" flags, alternating between the engine's two streams and staging
+    // buffers (the copy of chunk k + 1 overlaps the kernel on chunk k); a chunk's slice of the selection rides in the same
+    // staging buffer, behind the flags: a bitmap slice from the byte that holds the chunk's first bit (the launch then starts
+    // (sel_offset + pos) & 7 bits into it).  Every chunk's launch adds into the same device counters.
+    const uint64_t chunk = fsint::knobs().chunk_flags.load() < 8 ? 8 : fsint::knobs().chunk_flags.load();
+    const uint64_t cap = n < chunk ? n : chunk;                         // flags of the largest chunk
+    const uint64_t sel_cap = sel_bits == 1 ? (cap + 7) / 8 + 1 : cap;   // bytes of its slice
+    const int slots = n > chunk ? 2 : 1;
+    for (int i = 0; i < slots; ++i)
+        if ((rc = fsint::stage_reserve(e, i, cap + (sel_cap + 1) / 2))) return rc;
+    hipStream_t s0 = e.stream[0];
+    FS_HIP_TRY(hipMemsetAsync(row.d, 0, 33 * sizeof(uint64_t), s0));
+    if (slots == 2 && (rc = fsint::stream_wait_stream(e, e.stream[1], s0))) return rc;
+    const uint32_t grid = fsint::grid_for(e);
+    const int mode = flags & 2;
+    const uint8_t* sel_src = static_cast<const uint8_t*>(sel);
+    uint64_t k = 0;
+    for (uint64_t pos = 0; pos < n; pos += chunk, ++k) {
+        const int sl = static_cast<int>(k % static_cast<uint64_t>(slots));
+        const uint64_t c = n - pos < chunk ? n - pos : chunk;
+        uint64_t first, bytes;
+        where_extent(c, sel_offset + pos, sel_bits, &first, &bytes);
+        uint8_t* d_sel = reinterpret_cast<uint8_t*>(e.stage[sl] + cap);
+        FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], array + pos, c * 2, hipMemcpyHostToDevice, e.stream[sl]));
+        FS_HIP_TRY(hipMemcpyAsync(d_sel, sel_src + first, bytes, hipMemcpyHostToDevice, e.stream[sl]));
+        FS_HIP_TRY(fsk_launch_where(e.stage[sl], c, d_sel, sel_bits == 1 ? (sel_offset + pos) & 7 : 0, sel_bits, row.d, row.d + 32, mode,
+                                    grid, e.stream[sl]));
+    }
+    if (slots == 2 && (rc = fsint::stream_wait_stream(e, s0, e.stream[1]))) return rc;
+    uint64_t got[33];
+    FS_HIP_TRY(hipMemcpyAsync(got, row.d, sizeof got, hipMemcpyDeviceToHost, s0));
+    FS_HIP_TRY(hipStreamSynchronize(s0));
+    if (slots == 2) FS_HIP_TRY(hipStreamSynchronize(e.stream[1]));
+    where_apply(out, selected, got, flags);
+    return 0;
+}
+
+}  // extern "C"
