@@ -167,6 +167,34 @@ int FLAGSTATS_hip_device_u16_where_sync(const uint16_t* d_array, uint64_t n, con
 int FLAGSTATS_hip_u16_x64_where(const uint16_t* array, uint64_t n, const void* sel, uint64_t sel_offset, int sel_bits,
                                 uint64_t* out, uint64_t* selected, int flags);
 
+/* ================= filtered: flagstat under samtools' view filter -f / -F / -q =================
+ * `samtools view -f require -F exclude -q min_mapq | samtools flagstat` without the mask array that the `where` entries would
+ * need: the predicate is a function of the FLAG value and of one uint8 column next to it, and is applied inside the count.
+ *   pass(i) = (array[i] & require) == require && (array[i] & exclude) == 0 && (min_mapq == 0 || mapq[i] >= min_mapq)
+ * The 32 counters are FLAGSTAT_scalar's over {array[i] : pass(i), 0 <= i < n}; `selected` is the number of i with pass(i).
+ * require & exclude != 0 is legal, as in samtools, and passes nothing (nothing is launched).  min_mapq == 0 reads no byte of
+ * `mapq`, which may then be NULL; require == exclude == 0 with min_mapq == 0 is the plain count, selected == n.
+ * `flags`: as for the `where` entries -- bit 0 = store (out = counters, all 32 slots written; selected = count) instead of +=;
+ * bit 1 = superset (slots 0 / 16 = primary paired reads among those that pass, slot 9 = selected minus slot 25).  `selected` /
+ * `d_selected` may be NULL: nothing is reported.  n == 0 succeeds and touches nothing (the store form writes zeros).
+ * Refused (non-zero, message in FLAGSTATS_hip_last_error, out and selected untouched, nothing launched): require or exclude above
+ * 0xFFFF, min_mapq above 255, a NULL mapq with min_mapq > 0 and n > 0, a NULL array with n > 0, an odd array pointer, flag bits
+ * other than 0 and 1, NULL counters, an n with n * 2 not a size or too large for a wave's uint32 totals; for the device forms also
+ * a d_out or d_selected that is not plain device memory, pointers on different devices, a stream of another device and an
+ * allocation shorter than the call needs (d_array: n * 2 bytes, d_mapq: n bytes when min_mapq > 0, d_out: 256, d_selected: 8). */
+/* DEVICE array and MAPQ column, DEVICE d_out[32] and d_selected[1] (uint64); asynchronous on `stream`: ONE kernel (the store form
+ * puts one memset per pointer in front of it; one in all when d_selected == d_out + 32), no workspace.  Adds are atomic: launches
+ * on several streams may share d_out and d_selected in the += form. */
+int FLAGSTATS_hip_device_u16_filter(const uint16_t* d_array, uint64_t n, uint32_t require, uint32_t exclude, const uint8_t* d_mapq,
+                                    uint32_t min_mapq, uint64_t* d_out, uint64_t* d_selected, int flags, void* stream);
+/* DEVICE array and MAPQ column, HOST out[32] and selected[1]; synchronous */
+int FLAGSTATS_hip_device_u16_filter_sync(const uint16_t* d_array, uint64_t n, uint32_t require, uint32_t exclude, const uint8_t* d_mapq,
+                                         uint32_t min_mapq, uint64_t* out, uint64_t* selected, int flags);
+/* HOST array and MAPQ column, HOST out[32] and selected[1]; synchronous.  Array and column cross the bus in the engine's chunks
+ * (knob "chunk_flags"), each chunk's slice of the column behind its flags; the counters are summed on the device. */
+int FLAGSTATS_hip_u16_x64_filter(const uint16_t* array, uint64_t n, uint32_t require, uint32_t exclude, const uint8_t* mapq,
+                                 uint32_t min_mapq, uint64_t* out, uint64_t* selected, int flags);
+
 /* 64-bit positional popcount in this library's convention: out[16] += bit counts (host array / device array) */
 int FLAGSTATS_hip_pospopcnt_u16_x64(const uint16_t* array, uint64_t n, uint64_t* out);
 int FLAGSTATS_hip_device_pospopcnt_u16(const uint16_t* d_array, uint64_t n, uint64_t* d_out, void* stream);

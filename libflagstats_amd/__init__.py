@@ -13,6 +13,8 @@ Only what the path needs:
                      with the mask of bits seen above bit 15
 * ``where``          the same counters for the elements a boolean mask or an LSB-first
                      bitmap selects, with the number selected, in one pass
+* ``filter``         the same counters for the reads that pass samtools' ``-f`` / ``-F`` / ``-q``
+                     (FLAG bits required and excluded, a MAPQ threshold), with no mask array
 * ``dist``           shard + single all-reduce for multi-GPU runs
 
 The hot path has no CPU fallback: importing the compute entry points without the
@@ -26,10 +28,11 @@ from .segments import (  # noqa: F401
     offsets_from_lengths,
     segment_dicts,
 )
+from .filter import count_device_ptr_filter, count_torch_filter, counters_filter, flagstats_filter  # noqa: F401
 from .where import count_device_ptr_where, count_torch_where, counters_where, flagstats_where  # noqa: F401
 from .wide import count_device_ptr_ints, count_torch_ints, counters_ints, flagstats_ints  # noqa: F401
 
 __all__ = ["flagstats", "flagstats_x64", "SAM_FLAG_NAMES", "flagstats_segments", "offsets_from_lengths",
            "count_segments_device_ptr", "count_segments_torch", "segment_dicts", "counters_ints", "flagstats_ints",
            "count_device_ptr_ints", "count_torch_ints", "counters_where", "flagstats_where", "count_device_ptr_where",
-           "count_torch_where"]
+           "count_torch_where", "counters_filter", "flagstats_filter", "count_device_ptr_filter", "count_torch_filter"]

@@ -1,0 +1,587 @@
+// flagstat_filter.hip -- flagstat of the elements of a uint16 FLAG array that pass samtools' view filter: the 32 counters of
+// {flag[i] : pass(i)} and the number of i that pass, where
+//   pass(i) = (flag[i] & require) == require && (flag[i] & exclude) == 0 && (min_mapq == 0 || mapq[i] >= min_mapq)
+// (-f require, -F exclude, -q min_mapq; mapq is one uint8 per element).  One pass over the array (and the MAPQ column when
+// min_mapq > 0), one kernel, no selection array in memory.
+//
+// Geometry.  K1's and the selected-elements kernel's (flagstat_where.hip): the array is addressed on the 16-byte grid of its
+// aligned-down base, the caller's flags occupy positions [lo, hi) of it, steps of 32 KiB = 16,384 flags; workgroup b takes the
+// head edge step (b == 0), the tail edge step, then the fully covered steps b, b + G, ...; each wave owns a contiguous 8 KiB of a
+// step and lane l takes vectors u * 64 + l.  Edge steps go through guarded, zero-filling loaders; fast steps through K1's rolling
+// load schedule 71, restated below as flagstat_where.hip restates it.  The step split is fsk_where_geometry's
+// (tests/steps_oracle.StepSplit).
+//
+// MAPQ.  Addressed like the byte form of `where`: the launcher hands the kernel `mq` such that the 8 bytes of grid vector j are
+// mq[8 j .. 8 j + 8), at any alignment; one unaligned dwordx2 per vector, loaded with the vector on fast steps.  Edge steps read
+// only bytes of elements in [0, n).  The kernel is a template on whether the column is read at all (min_mapq == 0: it is not,
+// and the pointer may be NULL).
+//
+// Predicate.  A zero flag counts nothing in any slot, so filtering is zeroing the flags that fail, in front of front4, on the
+// byte planes L (FLAG bits 0-7 of 4 flags) and H (bits 8-15) that split_out produces.  With r = require, e = exclude, m = r | e
+// and r & e == 0 (the launcher answers an overlapping pair itself: it selects nothing), a flag passes iff ((flag ^ r) & m) == 0.
+// r, e and min_mapq are launch arguments, uniform over the grid; their byte-replicated forms live in registers.  Per 4 flags:
+//   x1 = (L ^ rL) & mL                      v_bitop3_b32
+//   x2 = (H ^ rH) & mH                      v_bitop3_b32
+//   a  = (x1 | x2) & 0x7F..                 v_bitop3_b32
+//   t  = a + 0x7F..                         v_add_u32       bit 7 of a byte: one of bits 0-6 of x1 | x2 is set (no carry leaves)
+//   q  = t | x1 | x2                        v_bitop3_b32    bit 7 of a byte: the flag fails
+//   p  = ~q & 0x80..                        v_bitop3_b32    0x80 per passing flag        [with MAPQ: ~q & g & 0x80.., see below]
+//   M  = v_perm_b32(0, 0, p)                v_perm_b32      a selector byte of 0x80 writes 0xFF, one of 0x00 a source byte (0x00)
+//   L &= M, H &= M                          2 x v_and_b32
+//   cnt += popcount(p)                      v_bcnt_u32_b32
+// = 10 VALU ops.  MAPQ adds 3: the byte-wise unsigned w >= y (gfx950 has no packed u8 compare) is SWAR across bit 7:
+//   u  = w | 0x80..                         v_or_b32
+//   t2 = u - (y & 0x7F) * 0x01..            v_sub_u32       every byte of u is >= 0x80 > y & 0x7F: no borrow leaves a byte;
+//                                                           bit 7 of a byte: (w & 0x7F) >= (y & 0x7F)
+//   g  = majority(w, t2, y < 128 ? 0x80.. : 0)              v_bitop3_b32    bit 7: y < 128: w7 | t2_7; y >= 128: w7 & t2_7
+// Edge steps additionally clear p for positions outside [lo, hi) (a zero-filled position passes every predicate without
+// `require` bits and would be counted in `selected`).
+//
+// Epilogue.  K1's direct one, as in flagstat_where.hip: finalize_slots<true> and one relaxed agent-scope atomic for `selected`,
+// which is also what the superset slot 9 takes for the flag count.  No workspace, no second kernel.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cstdio>
+#include <mutex>
+
+#include "../../include/libflagstats_hip.h"
+#include "flagstat_count_core.h"
+#include "flagstat_engine.h"
+#include "flagstat_filter.h"
+#include "flagstat_where.h"
+
+namespace fsk {
+
+constexpr int kFilterDepth = 8;       // chain depth as K1: epochs of 255 steps
+
+typedef uint32_t mq_u32x2_any __attribute__((ext_vector_type(2), aligned(1)));
+
+// the predicate of a launch, byte-replicated: wave-uniform
+struct FilterArgs {
+    uint32_t rL, mL, rH, mH;   // require and require | exclude, low and high byte plane
+    uint32_t y7;               // (min_mapq & 0x7F) in every byte
+    uint32_t k;                // 0x80808080 when min_mapq < 128, else 0
+};
+
+// the MAPQ bytes of one vector on a fast step (every position is an element)
+__device__ __forceinline__ uint2 load_mapq(const uint8_t* __restrict__ p)
+{
+    const mq_u32x2_any t = __builtin_nontemporal_load(reinterpret_cast<const mq_u32x2_any*>(p));
+    return make_uint2(t.x, t.y);
+}
+
+// the MAPQ bytes of vector j on an edge step: bytes of positions outside [lo, hi) are not touched and read as 0
+__device__ __forceinline__ uint2 load_mapq_guarded(const uint8_t* __restrict__ mq, uint64_t j, uint64_t lo, uint64_t hi)
+{
+    const uint64_t f0 = j * 8;
+    uint32_t w[2] = {0, 0};
+    if (f0 + 8 <= lo || f0 >= hi) return make_uint2(0, 0);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const uint64_t f = f0 + e;
+        if (f >= lo && f < hi) w[e >> 2] |= static_cast<uint32_t>(mq[f]) << (8 * (e & 3));
+    }
+    return make_uint2(w[0], w[1]);
+}
+
+// bit e of the result: position 8 j + e is an element
+__device__ __forceinline__ uint32_t valid_bits(uint64_t j, uint64_t lo, uint64_t hi)
+{
+    const uint64_t f0 = j * 8;
+    if (f0 + 8 <= lo || f0 >= hi) return 0u;
+    const uint32_t e0 = f0 >= lo ? 0u : static_cast<uint32_t>(lo - f0);
+    const uint32_t e1 = f0 + 8 <= hi ? 7u : static_cast<uint32_t>(hi - 1 - f0);
+    return (0xFFu >> (7 - e1)) & (0xFFu << e0);
+}
+
+// 4 bits (bit k = flag k) to 0x80 per set bit: bit k lands on bits k, k + 7, k + 14, k + 21, all distinct for k < 4
+__device__ __forceinline__ uint32_t nibble_to_bit7(uint32_t nib)
+{
+    return (__umul24(nib, 0x204081u) & 0x01010101u) << 7;
+}
+
+// v_bitop3_b32 truth tables, written as the expression over a = 0xF0, b = 0xCC, c = 0xAA
+constexpr uint32_t kTtXorAnd = (0xF0 ^ 0xCC) & 0xAA;                          // (a ^ b) & c
+constexpr uint32_t kTtOrAnd = (0xF0 | 0xCC) & 0xAA;                           // (a | b) & c
+constexpr uint32_t kTtOr3 = 0xF0 | 0xCC | 0xAA;                               // a | b | c
+constexpr uint32_t kTtNotAnd = (~0xF0 & 0xCC) & 0xFF;                         // ~a & b
+constexpr uint32_t kTtNotAndAnd = (~0xF0 & 0xCC & 0xAA) & 0xFF;               // ~a & b & c
+constexpr uint32_t kTtMajority = (0xF0 & 0xCC) | ((0xF0 | 0xCC) & 0xAA);      // (a & b) | ((a | b) & c)
+
+// 0x80 per flag of the planes L, H that passes; w: the MAPQ bytes of the same 4 flags
+template <bool MAPQ>
+__device__ __forceinline__ uint32_t pass4(const FilterArgs& f, uint32_t L, uint32_t H, uint32_t w)
+{
+    const uint32_t x1 = __builtin_amdgcn_bitop3_b32(L, f.rL, f.mL, kTtXorAnd);
+    const uint32_t x2 = __builtin_amdgcn_bitop3_b32(H, f.rH, f.mH, kTtXorAnd);
+    const uint32_t t = __builtin_amdgcn_bitop3_b32(x1, x2, 0x7F7F7F7Fu, kTtOrAnd) + 0x7F7F7F7Fu;
+    const uint32_t q = __builtin_amdgcn_bitop3_b32(t, x1, x2, kTtOr3);
+    if constexpr (MAPQ) {
+        const uint32_t t2 = (w | 0x80808080u) - f.y7;
+        const uint32_t g = __builtin_amdgcn_bitop3_b32(w, t2, f.k, kTtMajority);
+        return __builtin_amdgcn_bitop3_b32(q, g, 0x80808080u, kTtNotAndAnd);
+    } else {
+        return __builtin_amdgcn_bitop3_b32(q, 0x80808080u, 0u, kTtNotAnd);
+    }
+}
+
+// One step: 8 vectors of 16 B per lane = 64 flags -> 16 T, 16 F, 16 S inputs through K1's tree (flagstat_kernels.hip: step).
+// ROLL 0 (edge steps): the vectors are in v[], their MAPQ bytes in m[], the bits of their positions that are elements in vb[].
+// ROLL 1, 2: K1's schedule 71 -- vector u's registers are re-issued for vector u + 6 of the same step (`cur`) or, ROLL 1 only,
+// u - 2 of the next one (`next`): 6 loads = 24 KiB per CU in flight; the MAPQ bytes of a vector are loaded right in front of
+// it and read out with it.
+template <bool MAPQ, int ROLL>
+__device__ __forceinline__ void filter_step(Lane<kFilterDepth>& s, const FilterArgs& f, uint4 (&v)[kUnroll], uint2 (&m)[kUnroll],
+                                            const uint32_t (&vb)[kUnroll], uint32_t blk, uint32_t& cnt, const uint4* __restrict__ cur,
+                                            const uint4* __restrict__ next, const uint8_t* __restrict__ mcur,
+                                            const uint8_t* __restrict__ mnext)
+{
+    constexpr int RD = 6;
+    constexpr int US = 64;           // each wave a contiguous 8 KiB of the step
+    constexpr int MS = US * 8;       // MAPQ bytes between a lane's consecutive vectors
+    uint32_t t8a = 0, t8b = 0, f8a = 0, f8b = 0, s8a = 0, s8b = 0;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        uint32_t t4a = 0, t4b = 0, f4a = 0, f4b = 0, s4a = 0, s4b = 0;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            uint32_t T[4], F[4], S[4];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                uint32_t L0, H0, L1, H1;
+                const int uu = half * 4 + q * 2 + k;  // a constant after unrolling
+                __builtin_amdgcn_sched_barrier(0);
+                split_out(v[uu], L0, H0, L1, H1);
+                uint2 w = make_uint2(0, 0);
+                if constexpr (MAPQ) {
+                    w = m[uu];
+                    if constexpr (ROLL != 0) {
+                        if (uu + RD < kUnroll)
+                            m[uu + RD] = load_mapq(mcur + (uu + RD) * MS);
+                        else if constexpr (ROLL == 1)
+                            m[uu + RD - kUnroll] = load_mapq(mnext + (uu + RD - kUnroll) * MS);
+                    }
+                }
+                if constexpr (ROLL != 0) {
+                    if (uu + RD < kUnroll)
+                        v[uu + RD] = load_vec<true>(cur + (uu + RD) * US);
+                    else if constexpr (ROLL == 1)
+                        v[uu + RD - kUnroll] = load_vec<true>(next + (uu + RD - kUnroll) * US);
+                }
+                uint32_t p0 = pass4<MAPQ>(f, L0, H0, w.x);
+                uint32_t p1 = pass4<MAPQ>(f, L1, H1, w.y);
+                if constexpr (ROLL == 0) {
+                    p0 &= nibble_to_bit7(vb[uu] & 15u);
+                    p1 &= nibble_to_bit7(vb[uu] >> 4);
+                }
+                cnt += __builtin_popcount(p0);
+                cnt += __builtin_popcount(p1);
+                const uint32_t M0 = perm(0u, 0u, p0), M1 = perm(0u, 0u, p1);   // selector 0x80 -> 0xFF, 0x00 -> source byte 0 = 0x00
+                L0 &= M0;
+                H0 &= M0;
+                L1 &= M1;
+                H1 &= M1;
+                __builtin_amdgcn_sched_barrier(0);
+                uint32_t qa, qb, ka, kb;
+                front4(L0, H0, T[2 * k], qa, ka);
+                front4(L1, H1, T[2 * k + 1], qb, kb);
+                F[2 * k] = T[2 * k] & perm(0u, 0xFF00FF00u, qa);
+                F[2 * k + 1] = T[2 * k + 1] & perm(0u, 0xFF00FF00u, qb);
+                S[2 * k] = perm(0u, 0x84428140u, qa) & (ka | 0x3F3F3F3Fu);
+                S[2 * k + 1] = perm(0u, 0x84428140u, qb) & (kb | 0x3F3F3F3Fu);
+            }
+            uint32_t t2a, t2b, f2a, f2b, s2a, s2b;
+            csa(t2a, s.t1, s.t1, T[0], T[1]);
+            csa(t2b, s.t1, s.t1, T[2], T[3]);
+            csa(f2a, s.f1, s.f1, F[0], F[1]);
+            csa(f2b, s.f1, s.f1, F[2], F[3]);
+            csa(s2a, s.s1, s.s1, S[0], S[1]);
+            csa(s2b, s.s1, s.s1, S[2], S[3]);
+            csa(q ? t4b : t4a, s.t2, s.t2, t2a, t2b);
+            csa(q ? f4b : f4a, s.f2, s.f2, f2a, f2b);
+            csa(q ? s4b : s4a, s.s2, s.s2, s2a, s2b);
+        }
+        csa(half ? t8b : t8a, s.t4, s.t4, t4a, t4b);
+        csa(half ? f8b : f8a, s.f4, s.f4, f4a, f4b);
+        csa(half ? s8b : s8a, s.s4, s.s4, s4a, s4b);
+    }
+    uint32_t ct, cf, cs;
+    csa(ct, s.t8, s.t8, t8a, t8b);  // weight-16 carries
+    csa(cf, s.f8, s.f8, f8a, f8b);
+    csa(cs, s.s8, s.s8, s8a, s8b);
+    chain_push<0, kFilterDepth>(s, blk, ct, cf, cs);
+}
+
+template <bool MAPQ, int ROLL>
+__device__ __forceinline__ void filter_step_and_count(Lane<kFilterDepth>& s, const FilterArgs& f, uint4 (&v)[kUnroll], uint2 (&m)[kUnroll],
+                                                      const uint32_t (&vb)[kUnroll], uint32_t& blk, uint32_t& cnt,
+                                                      const uint4* __restrict__ cur = nullptr, const uint4* __restrict__ next = nullptr,
+                                                      const uint8_t* __restrict__ mcur = nullptr, const uint8_t* __restrict__ mnext = nullptr)
+{
+    blk = __builtin_amdgcn_readfirstlane(blk);
+    filter_step<MAPQ, ROLL>(s, f, v, m, vb, blk, cnt, cur, next, mcur, mnext);
+    ++blk;
+    if (blk == (1u << kFilterDepth) - 1u) {
+        flush(s, (1u << kFilterDepth) - 1u);
+        blk = 0;
+    }
+}
+
+// a0: 16-B aligned-down base; the caller's flags occupy positions [lo, hi) of its grid.  mq: the MAPQ column on the same grid
+// (the byte of position q is mq[q]; not read when !MAPQ).  require & exclude == 0 (the launcher's business), both below 2^16,
+// min_mapq in 1..255 when MAPQ.  mode: bit 1 superset (bit 0, the store form, is the launcher's memset).  selected may be nullptr.
+template <bool MAPQ>
+__global__ __launch_bounds__(kThreads) void flagstat_count_filter(const uint4* __restrict__ a0, const uint8_t* __restrict__ mq, uint32_t require,
+                                                                  uint32_t exclude, uint32_t min_mapq, uint64_t lo, uint64_t hi,
+                                                                  uint64_t nsteps, uint64_t fast_begin, uint64_t fast_end,
+                                                                  uint64_t* __restrict__ out, uint64_t* __restrict__ selected, int mode)
+{
+    Lane<kFilterDepth> s;
+    lane_init(s);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = threadIdx.x >> 6;
+    constexpr int VPS = kVecPerStep;
+    constexpr int US = 64;
+    const uint64_t lane_off = static_cast<uint64_t>(wave) * (64 * kUnroll) + lane;
+    const uint64_t G = gridDim.x;
+    FilterArgs f;
+    {
+        const uint32_t m = require | exclude;
+        f.rL = (require & 0xFFu) * 0x01010101u;
+        f.rH = ((require >> 8) & 0xFFu) * 0x01010101u;
+        f.mL = (m & 0xFFu) * 0x01010101u;
+        f.mH = ((m >> 8) & 0xFFu) * 0x01010101u;
+        f.y7 = (min_mapq & 0x7Fu) * 0x01010101u;
+        f.k = min_mapq < 128u ? 0x80808080u : 0u;
+    }
+    // wave w starts its first epoch at 64 * w, so at most one wave of a CU is flushing at any time (K1's mode bit 4)
+    uint32_t blk = (wave & 3u) * 64u;
+    uint32_t cnt = 0;                           // passing elements of this lane
+
+    auto edge_step = [&](uint64_t st) {
+        uint4 v[kUnroll];
+        uint2 m[kUnroll];
+        uint32_t vb[kUnroll];
+        const uint64_t j0 = st * VPS + lane_off;
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            v[u] = load_guarded(a0, j0 + u * US, lo, hi);
+            vb[u] = valid_bits(j0 + u * US, lo, hi);
+            if constexpr (MAPQ)
+                m[u] = load_mapq_guarded(mq, j0 + u * US, lo, hi);
+            else
+                m[u] = make_uint2(0, 0);
+        }
+        filter_step_and_count<MAPQ, 0>(s, f, v, m, vb, blk, cnt);
+    };
+    // ragged edge steps (at most the first and the last of the whole array), outside the pipelined loop
+    if (fast_begin != 0 && blockIdx.x == 0) edge_step(0);
+    if (nsteps > fast_end && nsteps - 1 >= fast_begin && (nsteps - 1) % G == blockIdx.x) edge_step(nsteps - 1);
+    // first fully in-range step of this workgroup
+    uint64_t st = blockIdx.x;
+    if (st < fast_begin) st += G;  // fast_begin is 0 or 1
+    if (st < fast_end) {
+        constexpr int RD = 6;
+        uint4 v[kUnroll];
+        uint2 m[kUnroll];
+        const uint32_t vb[kUnroll] = {};        // not looked at on fast steps
+        const uint4* p = a0 + st * VPS + lane_off;
+        const uint8_t* pm = mq + (st * VPS + lane_off) * 8;
+        // the first RD vectors; the rest is issued as they are consumed
+#pragma unroll
+        for (int u = 0; u < RD; ++u) {
+            if constexpr (MAPQ) m[u] = load_mapq(pm + u * US * 8);
+            v[u] = load_vec<true>(p + u * US);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        for (; st + G < fast_end; st += G) {
+            const uint4* pn = p + G * VPS;
+            const uint8_t* pmn = pm + G * VPS * 8;
+            filter_step_and_count<MAPQ, 1>(s, f, v, m, vb, blk, cnt, p, pn, pm, pmn);
+            p = pn;
+            pm = pmn;
+        }
+        filter_step_and_count<MAPQ, 2>(s, f, v, m, vb, blk, cnt, p, nullptr, pm, nullptr);
+    }
+    flush(s, blk);
+
+    // wave sums on the VALU (DPP), then the 4 waves through LDS; word kInternal is the number of passing elements
+    constexpr int kWaves = kThreads / 64;
+    __shared__ uint32_t red[kWaves][kInternal + 1];
+    __shared__ uint64_t wg_tot[32];
+    uint32_t wsum[kInternal + 1];
+#pragma unroll
+    for (int c = 0; c < kInternal; ++c) wsum[c] = wave_sum_lane63(s.acc[c]);
+    wsum[kInternal] = wave_sum_lane63(cnt);
+    if (lane == 63) {
+#pragma unroll
+        for (int c = 0; c <= kInternal; ++c) red[wave][c] = wsum[c];
+    }
+    __syncthreads();
+    if (threadIdx.x <= kInternal) {
+        uint64_t sum = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) sum += red[w][threadIdx.x];
+        wg_tot[threadIdx.x] = sum;
+    }
+    __syncthreads();
+    const uint64_t wg_selected = wg_tot[kInternal];
+    if (threadIdx.x == 64 && selected != nullptr && wg_selected)
+        (void)__hip_atomic_fetch_add(selected, wg_selected, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // this workgroup's totals, mapped to the reference's slots, added to out[32]; every workgroup enters its own number of
+    // passing elements into slot 9 (superset)
+    finalize_slots<true>(wg_tot, out, mode, wg_selected);
+}
+
+}  // namespace fsk
+
+// ------------------------------------------------------------------ launcher
+extern "C" hipError_t fsk_launch_filter(const uint16_t* d_array, uint64_t n, uint32_t require, uint32_t exclude, const uint8_t* d_mapq,
+                                        uint32_t min_mapq, uint64_t* d_out32, uint64_t* d_selected, int mode, uint32_t grid,
+                                        hipStream_t stream)
+{
+    if ((mode & ~3) || grid == 0 || d_out32 == nullptr || require > 0xFFFFu || exclude > 0xFFFFu || min_mapq > 255u ||
+        (n && (d_array == nullptr || (min_mapq && d_mapq == nullptr))))
+        return hipErrorInvalidValue;
+    // the step split is K1's and where's: one copy of that arithmetic (the selection arguments only fill geo[6], geo[7])
+    uint64_t geo[8];
+    hipError_t e = fsk_where_geometry(reinterpret_cast<uintptr_t>(d_array), n, 0, 8, grid, geo);
+    if (e != hipSuccess) return e;
+    if (mode & 1) {
+        // counters and the selected count in one memset where they are one allocation's 33 words
+        const bool together = d_selected == d_out32 + 32;
+        e = hipMemsetAsync(d_out32, 0, (together ? 33 : 32) * sizeof(uint64_t), stream);
+        if (e == hipSuccess && d_selected && !together) e = hipMemsetAsync(d_selected, 0, sizeof(uint64_t), stream);
+        if (e != hipSuccess) return e;
+    }
+    // a bit both required and excluded: no flag passes (samtools accepts the pair); the kernel's test assumes a disjoint pair
+    if (n == 0 || (require & exclude)) return hipSuccess;
+    const uint4* a0 = reinterpret_cast<const uint4*>(reinterpret_cast<uintptr_t>(d_array) & ~static_cast<uintptr_t>(15));
+    const dim3 g(static_cast<uint32_t>(geo[5])), b(fsk::kThreads);
+    if (min_mapq) {
+        // grid position q is element q - lo: its byte is d_mapq[q - lo]
+        const uint8_t* mq = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(d_mapq) - geo[0]);
+        hipLaunchKernelGGL((fsk::flagstat_count_filter<true>), g, b, 0, stream, a0, mq, require, exclude, min_mapq, geo[0], geo[1], geo[2],
+                           geo[3], geo[4], d_out32, d_selected, mode & 2);
+    } else {
+        hipLaunchKernelGGL((fsk::flagstat_count_filter<false>), g, b, 0, stream, a0, static_cast<const uint8_t*>(nullptr), require, exclude,
+                           0u, geo[0], geo[1], geo[2], geo[3], geo[4], d_out32, d_selected, mode & 2);
+    }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ C entry points (include/libflagstats_hip.h)
+using fsint::DeviceGuard;
+using fsint::Engine;
+using fsint::fail_hip;
+using fsint::fail_text;
+
+namespace {
+
+// what every form refuses before it touches the GPU
+int filter_args(const uint16_t* array, uint64_t n, uint32_t require, uint32_t exclude, const uint8_t* mapq, uint32_t min_mapq,
+                const void* out, int flags)
+{
+    if (require > 0xFFFFu) return fail_text("require must be a 16-bit FLAG mask (at most 0xFFFF)");
+    if (exclude > 0xFFFFu) return fail_text("exclude must be a 16-bit FLAG mask (at most 0xFFFF)");
+    if (min_mapq > 255u) return fail_text("min_mapq must be at most 255 (MAPQ is one byte)");
+    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
+    if (n && !array) return fail_text("NULL array with n > 0");
+    if (n && min_mapq && !mapq) return fail_text("NULL mapq with min_mapq > 0 and n > 0");
+    if (reinterpret_cast<uintptr_t>(array) & 1u) return fail_text("array must be 2-byte aligned");
+    if (n > (~0ull - 64) / 2) return fail_text("n * 2 is not a size");
+    if (!out && (n || (flags & 1))) return fail_text("NULL counters");
+    return 0;
+}
+
+// device counters[32] + selected count of one synchronous call
+struct FilterRow {
+    uint64_t* d = nullptr;
+    ~FilterRow()
+    {
+        if (d) (void)hipFree(d);
+    }
+    int alloc()
+    {
+        const hipError_t e = hipMalloc(&d, 33 * sizeof(uint64_t));
+        if (e != hipSuccess) {
+            d = nullptr;
+            return fail_hip("hipMalloc(filter counters)", e);
+        }
+        return 0;
+    }
+};
+
+void filter_apply(uint64_t* out, uint64_t* selected, const uint64_t (&got)[33], int flags)
+{
+    if (flags & 1) {
+        for (int i = 0; i < 32; ++i) out[i] = got[i];
+        if (selected) *selected = got[32];
+    } else {
+        for (int i = 0; i < 32; ++i) out[i] += got[i];
+        if (selected) *selected += got[32];
+    }
+}
+
+void filter_nothing(uint64_t* out, uint64_t* selected, int flags)
+{
+    if (flags & 1) {
+        for (int i = 0; i < 32; ++i) out[i] = 0;
+        if (selected) *selected = 0;
+    }
+}
+
+// a wave's totals are uint32: the one thing fsk_where_geometry still refuses once filter_args has passed (where's limit)
+int filter_fits(const uint16_t* array, uint64_t n, uint32_t grid)
+{
+    uint64_t geo[8];
+    if (fsk_where_geometry(reinterpret_cast<uintptr_t>(array), n, 0, 8, grid, geo) != hipSuccess)
+        return fail_text("n is too large for this grid: a wave's uint32 totals could overflow (split the array)");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int FLAGSTATS_hip_device_u16_filter(const uint16_t* d_array, uint64_t n, uint32_t require, uint32_t exclude, const uint8_t* d_mapq,
+                                    uint32_t min_mapq, uint64_t* d_out, uint64_t* d_selected, int flags, void* stream)
+{
+    FS_ENTRY();
+    int rc = filter_args(d_array, n, require, exclude, d_mapq, min_mapq, d_out, flags);
+    if (rc) return rc;
+    if (n == 0 && !(flags & 1)) return 0;
+    int dev_out = -1, dev = -1;
+    bool plain = false;
+    rc = fsint::device_of_pointer(d_out, "d_out", &dev_out, &plain);
+    if (rc) return rc;
+    if (!plain) return fail_text("d_out must be device memory (the counters are added with device atomics)");
+    if (d_selected) {
+        rc = fsint::device_of_pointer(d_selected, "d_selected", &dev, &plain);
+        if (rc) return rc;
+        if (!plain) return fail_text("d_selected must be device memory (the count is added with a device atomic)");
+        if (dev != dev_out) return fail_text("d_selected and d_out live on different devices");
+    }
+    if (n) {
+        rc = fsint::device_of_pointer(d_array, "d_array", &dev);
+        if (rc) return rc;
+        if (dev != dev_out) return fail_text("d_array and d_out live on different devices");
+        if (min_mapq) {
+            rc = fsint::device_of_pointer(d_mapq, "d_mapq", &dev);
+            if (rc) return rc;
+            if (dev != dev_out) return fail_text("d_mapq and d_out live on different devices");
+        }
+    }
+    Engine* e = fsint::engine_for_device(dev_out);
+    if (!e) return -1;
+    DeviceGuard guard(e->device);
+    if (!guard.ok()) return -1;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = fsint::check_stream_device(s, e->device);
+    if (rc) return rc;
+    if ((rc = filter_fits(d_array, n, fsint::grid_for(*e)))) return rc;
+    if ((rc = fsint::check_extent(d_out, 32 * sizeof(uint64_t), "d_out"))) return rc;
+    if (d_selected && (rc = fsint::check_extent(d_selected, sizeof(uint64_t), "d_selected"))) return rc;
+    if (n) {
+        if ((rc = fsint::check_extent(d_array, n * 2, "d_array"))) return rc;
+        if (min_mapq && (rc = fsint::check_extent(d_mapq, n, "d_mapq"))) return rc;
+    }
+    FS_HIP_TRY(fsk_launch_filter(d_array, n, require, exclude, d_mapq, min_mapq, d_out, d_selected, flags & 3, fsint::grid_for(*e), s));
+    return 0;
+}
+
+int FLAGSTATS_hip_device_u16_filter_sync(const uint16_t* d_array, uint64_t n, uint32_t require, uint32_t exclude, const uint8_t* d_mapq,
+                                         uint32_t min_mapq, uint64_t* out, uint64_t* selected, int flags)
+{
+    FS_ENTRY();
+    int rc = filter_args(d_array, n, require, exclude, d_mapq, min_mapq, out, flags);
+    if (rc) return rc;
+    if (n == 0) {
+        filter_nothing(out, selected, flags);
+        return 0;
+    }
+    int dev = -1, dev_mapq = -1;
+    rc = fsint::device_of_pointer(d_array, "d_array", &dev);
+    if (rc) return rc;
+    if (min_mapq) {
+        rc = fsint::device_of_pointer(d_mapq, "d_mapq", &dev_mapq);
+        if (rc) return rc;
+        if (dev_mapq != dev) return fail_text("d_mapq and d_array live on different devices");
+    }
+    Engine* ep = fsint::engine_for_device(dev);
+    if (!ep) return -1;
+    Engine& e = *ep;
+    std::lock_guard<std::mutex> lk(e.mu);
+    if (fsint::engine_alive(e)) return -1;
+    DeviceGuard guard(e.device);
+    if (!guard.ok()) return -1;
+    if ((rc = filter_fits(d_array, n, fsint::grid_for(e)))) return rc;
+    if ((rc = fsint::check_extent(d_array, n * 2, "d_array"))) return rc;
+    if (min_mapq && (rc = fsint::check_extent(d_mapq, n, "d_mapq"))) return rc;
+    FilterRow row;
+    if ((rc = row.alloc())) return rc;
+    uint64_t got[33];
+    hipStream_t s = e.stream[0];
+    FS_HIP_TRY(fsk_launch_filter(d_array, n, require, exclude, d_mapq, min_mapq, row.d, row.d + 32, 1 | (flags & 2), fsint::grid_for(e), s));
+    FS_HIP_TRY(hipMemcpyAsync(got, row.d, sizeof got, hipMemcpyDeviceToHost, s));
+    FS_HIP_TRY(hipStreamSynchronize(s));
+    filter_apply(out, selected, got, flags);
+    return 0;
+}
+
+int FLAGSTATS_hip_u16_x64_filter(const uint16_t* array, uint64_t n, uint32_t require, uint32_t exclude, const uint8_t* mapq, uint32_t min_mapq,
+                                 uint64_t* out, uint64_t* selected, int flags)
+{
+    FS_ENTRY();
+    int rc = filter_args(array, n, require, exclude, mapq, min_mapq, out, flags);
+    if (rc) return rc;
+    if (n == 0) {
+        filter_nothing(out, selected, flags);
+        return 0;
+    }
+    Engine* ep = fsint::default_engine();
+    if (!ep) return -1;
+    Engine& e = *ep;
+    std::lock_guard<std::mutex> lk(e.mu);
+    if (fsint::engine_alive(e)) return -1;
+    DeviceGuard guard(e.device);
+    if (!guard.ok()) return -1;
+    fsint::lz4_gpu_other_use(e);
+    FilterRow row;
+    if ((rc = row.alloc())) return rc;
+    if ((rc = fsint::engine_second(e))) return rc;
+    // the array crosses the bus in chunks of "chunk_flags" flags, alternating between the engine's two streams and staging
+    // buffers (the copy of chunk k + 1 overlaps the kernel on chunk k); a chunk's slice of the MAPQ column rides in the same
+    // staging buffer, behind the flags.  Every chunk's launch adds into the same device counters.
+    const uint64_t chunk = fsint::knobs().chunk_flags.load() < 8 ? 8 : fsint::knobs().chunk_flags.load();
+    const uint64_t cap = n < chunk ? n : chunk;                         // flags of the largest chunk
+    const uint64_t mapq_cap = min_mapq ? cap : 0;                       // bytes of its MAPQ slice
+    if ((rc = filter_fits(nullptr, cap, fsint::grid_for(e)))) return rc;
+    const int slots = n > chunk ? 2 : 1;
+    for (int i = 0; i < slots; ++i)
+        if ((rc = fsint::stage_reserve(e, i, cap + (mapq_cap + 1) / 2))) return rc;
+    hipStream_t s0 = e.stream[0];
+    FS_HIP_TRY(hipMemsetAsync(row.d, 0, 33 * sizeof(uint64_t), s0));
+    if (slots == 2 && (rc = fsint::stream_wait_stream(e, e.stream[1], s0))) return rc;
+    const uint32_t grid = fsint::grid_for(e);
+    const int mode = flags & 2;
+    uint64_t k = 0;
+    for (uint64_t pos = 0; pos < n; pos += chunk, ++k) {
+        const int sl = static_cast<int>(k % static_cast<uint64_t>(slots));
+        const uint64_t c = n - pos < chunk ? n - pos : chunk;
+        uint8_t* d_mapq = reinterpret_cast<uint8_t*>(e.stage[sl] + cap);
+        FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], array + pos, c * 2, hipMemcpyHostToDevice, e.stream[sl]));
+        if (min_mapq) FS_HIP_TRY(hipMemcpyAsync(d_mapq, mapq + pos, c, hipMemcpyHostToDevice, e.stream[sl]));
+        FS_HIP_TRY(fsk_launch_filter(e.stage[sl], c, require, exclude, d_mapq, min_mapq, row.d, row.d + 32, mode, grid, e.stream[sl]));
+    }
+    if (slots == 2 && (rc = fsint::stream_wait_stream(e, s0, e.stream[1]))) return rc;
+    uint64_t got[33];
+    FS_HIP_TRY(hipMemcpyAsync(got, row.d, sizeof got, hipMemcpyDeviceToHost, s0));
+    FS_HIP_TRY(hipStreamSynchronize(s0));
+    if (slots == 2) FS_HIP_TRY(hipStreamSynchronize(e.stream[1]));
+    filter_apply(out, selected, got, flags);
+    return 0;
+}
+
+}  // extern "C"

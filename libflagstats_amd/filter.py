@@ -1,0 +1,148 @@
+"""Flagstat of the reads that pass samtools' view filter: ``samtools view -f require -F exclude -q min_mapq | samtools
+flagstat`` in one pass, with no mask array in memory.
+
+An element passes when it has every bit of ``require``, no bit of ``exclude`` and -- with ``min_mapq > 0`` -- a MAPQ of at least
+``min_mapq`` in the ``uint8`` column ``mapq`` that has one element per value.  The 32 counters are those of the values that pass;
+next to them the caller gets ``selected``, their number.  ``require & exclude != 0`` is legal, as in samtools, and passes nothing.
+The predicate is applied inside the counting kernel: the array (and the column, when ``min_mapq > 0``) is read once.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from .pyflagstats import _as_dict
+
+STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
+
+
+def _check_predicate(require, exclude, min_mapq, has_mapq: bool):
+    for name, x in (("require", require), ("exclude", exclude)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+            raise ValueError("%s must be an int, not %s" % (name, type(x).__name__))
+        if not 0 <= x <= 0xFFFF:
+            raise ValueError("%s must be a 16-bit FLAG mask (0..65535), not %d" % (name, x))
+    if isinstance(min_mapq, bool) or not isinstance(min_mapq, (int, np.integer)):
+        raise ValueError("min_mapq must be an int, not %s" % type(min_mapq).__name__)
+    if not 0 <= min_mapq <= 255:
+        raise ValueError("min_mapq must be in 0..255 (MAPQ is one byte), not %d" % min_mapq)
+    if min_mapq > 0 and not has_mapq:
+        raise ValueError("min_mapq > 0 needs mapq (one uint8 per value)")
+    return int(require), int(exclude), int(min_mapq)
+
+
+def _check_numpy(values, mapq):
+    if not isinstance(values, np.ndarray):
+        raise ValueError("values must be a numpy.ndarray, not %s" % type(values).__name__)
+    if values.dtype != np.uint16:
+        raise ValueError("values must have dtype uint16, not %s" % values.dtype)
+    if values.ndim != 1:
+        raise ValueError("values must be 1-D, not %d-D" % values.ndim)
+    if mapq is not None:
+        if not isinstance(mapq, np.ndarray):
+            raise ValueError("mapq must be a numpy.ndarray, not %s" % type(mapq).__name__)
+        if mapq.dtype != np.uint8:
+            raise ValueError("mapq must have dtype uint8, not %s" % mapq.dtype)
+        if mapq.ndim != 1:
+            raise ValueError("mapq must be 1-D, not %d-D" % mapq.ndim)
+        if mapq.size != values.size:
+            raise ValueError("mapq must have one element per value (%d), not %d" % (values.size, mapq.size))
+        mapq = np.ascontiguousarray(mapq)
+    return np.ascontiguousarray(values), mapq
+
+
+def counters_filter(values, require: int = 0, exclude: int = 0, mapq=None, min_mapq: int = 0, superset: bool = False):
+    """``(uint64[32] counters, int selected)`` of the elements of the 1-D ``uint16`` host array ``values`` that have every bit
+    of ``require``, no bit of ``exclude`` and, with ``min_mapq > 0``, ``mapq[i] >= min_mapq`` (``mapq``: a ``uint8`` array of
+    the same length) (``FLAGSTATS_hip_u16_x64_filter``)."""
+    v, q = _check_numpy(values, mapq)
+    require, exclude, min_mapq = _check_predicate(require, exclude, min_mapq, q is not None)
+    out = np.zeros(32, dtype=np.uint64)
+    selected = ctypes.c_uint64(0)
+    _lib.check(_lib.lib().FLAGSTATS_hip_u16_x64_filter(v.ctypes.data if v.size else None, v.size, require, exclude,
+                                                       q.ctypes.data if q is not None and q.size else None, min_mapq,
+                                                       out.ctypes.data, ctypes.byref(selected),
+                                                       STORE | (SUPERSET if superset else 0)), "FLAGSTATS_hip_u16_x64_filter")
+    return out, int(selected.value)
+
+
+def flagstats_filter(values, require: int = 0, exclude: int = 0, mapq=None, min_mapq: int = 0) -> dict:
+    """The dict of ``pyflagstats.flagstats_x64`` over the values that pass: ``n_values`` is their number and ``mapped`` is
+    derived from it."""
+    counters, selected = counters_filter(values, require=require, exclude=exclude, mapq=mapq, min_mapq=min_mapq)
+    return _as_dict(counters, selected)
+
+
+def count_device_ptr_filter(ptr: int, n: int, require: int = 0, exclude: int = 0, mapq_ptr: int = 0, min_mapq: int = 0,
+                            superset: bool = False):
+    """``(uint64[32], int selected)`` of a device array of ``n`` ``uint16`` flags under the filter, array and MAPQ column
+    (``n`` bytes; ``mapq_ptr`` 0: none) given as raw pointers.  Synchronous (``FLAGSTATS_hip_device_u16_filter_sync``)."""
+    for name, x in (("ptr", ptr), ("n", n), ("mapq_ptr", mapq_ptr)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+            raise ValueError("%s must be an int, not %s" % (name, type(x).__name__))
+    if n < 0:
+        raise ValueError("n must not be negative")
+    for name, x in (("ptr", ptr), ("n", n), ("mapq_ptr", mapq_ptr)):
+        if not 0 <= x < 1 << 64:
+            raise ValueError("%s must fit an unsigned 64-bit integer, not %d" % (name, x))
+    require, exclude, min_mapq = _check_predicate(require, exclude, min_mapq, mapq_ptr != 0)
+    ptr, n, mapq_ptr = int(ptr), int(n), int(mapq_ptr)
+    out = np.zeros(32, dtype=np.uint64)
+    selected = ctypes.c_uint64(0)
+    _lib.check(_lib.lib().FLAGSTATS_hip_device_u16_filter_sync(ptr if n else None, n, require, exclude, mapq_ptr if n and mapq_ptr else None,
+                                                               min_mapq, out.ctypes.data, ctypes.byref(selected),
+                                                               STORE | (SUPERSET if superset else 0)), "FLAGSTATS_hip_device_u16_filter_sync")
+    return out, int(selected.value)
+
+
+def count_torch_filter(t, require: int = 0, exclude: int = 0, mapq=None, min_mapq: int = 0, out=None, selected=None, store: bool = False,
+                       superset: bool = False):
+    """Counters of the elements of the 1-D contiguous ``int16`` / ``uint16`` CUDA tensor ``t`` that pass the filter (``mapq``: a
+    1-D contiguous ``torch.uint8`` tensor of ``t.numel()`` elements on ``t``'s device, needed when ``min_mapq > 0``) -- on
+    torch's current stream, nothing synchronised.
+
+    Returns ``(out, selected)``: ``int64[32]`` and ``int64[1]`` CUDA tensors on ``t``'s device (made zeroed when not given).
+    ``store=False`` adds into both; ``store=True`` overwrites both."""
+    import torch
+
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("t must be a torch.Tensor, not %s" % type(t).__name__)
+    if t.dtype not in (torch.int16, torch.uint16):
+        raise ValueError("t must have dtype int16 or uint16, not %s" % t.dtype)
+    if t.dim() != 1 or not t.is_contiguous():
+        raise ValueError("t must be 1-D and contiguous")
+    if mapq is not None:
+        if not isinstance(mapq, torch.Tensor):
+            raise ValueError("mapq must be a torch.Tensor, not %s" % type(mapq).__name__)
+        if mapq.dtype != torch.uint8:
+            raise ValueError("mapq must have dtype torch.uint8, not %s" % mapq.dtype)
+        if mapq.dim() != 1 or not mapq.is_contiguous():
+            raise ValueError("mapq must be 1-D and contiguous")
+        if mapq.numel() != t.numel():
+            raise ValueError("mapq must have one element per value (%d), not %d" % (t.numel(), mapq.numel()))
+    require, exclude, min_mapq = _check_predicate(require, exclude, min_mapq, mapq is not None)
+    given = (("out", out, 32), ("selected", selected, 1))
+    for name, x, numel in given:
+        if x is not None and not (isinstance(x, torch.Tensor) and x.dtype == torch.int64 and x.numel() == numel and x.is_contiguous()):
+            raise ValueError("%s must be a contiguous int64 tensor of %d element%s" % (name, numel, "s" if numel > 1 else ""))
+    if not t.is_cuda:
+        raise ValueError("t must be a CUDA tensor")
+    for name, x in (("mapq", mapq), ("out", out), ("selected", selected)):
+        if x is not None and x.device != t.device:
+            raise ValueError("%s must live on t's device (%s), not on %s" % (name, t.device, x.device))
+    if out is None:
+        out = torch.zeros(32, dtype=torch.int64, device=t.device)
+    if selected is None:
+        selected = torch.zeros(1, dtype=torch.int64, device=t.device)
+    lib = _lib.lib()
+    with torch.cuda.device(t.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+        n = t.numel()
+        flags = (STORE if store else 0) | (SUPERSET if superset else 0)
+        _lib.check(lib.FLAGSTATS_hip_device_u16_filter(t.data_ptr() if n else None, n, require, exclude,
+                                                       mapq.data_ptr() if mapq is not None and n else None, min_mapq, out.data_ptr(),
+                                                       selected.data_ptr(), flags, stream),
+                   "FLAGSTATS_hip_device_u16_filter")
+    return out, selected
