@@ -2,7 +2,9 @@
 // lane's bit-sliced counters with their binary-counter chain, the epoch flush, the map from the 21 internal counters to the
 // reference's 32 slots and the two epilogue forms.  Device code only.  Shared by the product kernel and by the measurement
 // build's schedules (flagstat_kernels_tuning.hip, `make tuning`), which differ in HOW a step's vectors are loaded, not in what
-// is done with them.
+// is done with them (that unit keeps a step of its own: its XOR-only schedules cut into the tree).  The kernels derived from K1
+// -- flagstat_segments.hip, flagstat_wide.hip, flagstat_where.hip, flagstat_filter.hip -- call the same tree_step and end_step
+// and share, at the end of this file, schedule 71's constants and its re-issue of a vector's registers.
 #ifndef FLAGSTAT_COUNT_CORE_H_
 #define FLAGSTAT_COUNT_CORE_H_
 
@@ -113,6 +115,59 @@ __device__ __forceinline__ void chain_push(Lane<DEPTH>& s, uint32_t blk, uint32_
     }
 }
 
+// One step: 8 vectors of 16 B per lane = 64 flags -> 16 T, 16 F, 16 S inputs through a Harley-Seal tree; the weight-16 carries
+// enter the chain at `blk` (wave-uniform: the caller's readfirstlane stands in front of the step).  `planes(uu, L0, H0, L1, H1)`
+// is the caller's front for vector uu (a constant after unrolling): everything between the two sched_barriers of a rolling
+// schedule -- the split into byte planes, the re-issue of the vector's registers, any masking of flags -- in its own file.
+template <int DEPTH, typename Planes>
+__device__ __forceinline__ void tree_step(Lane<DEPTH>& s, uint32_t blk, Planes&& planes)
+{
+    uint32_t t8a = 0, t8b = 0, f8a = 0, f8b = 0, s8a = 0, s8b = 0;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        uint32_t t4a = 0, t4b = 0, f4a = 0, f4b = 0, s4a = 0, s4b = 0;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            // two vectors -> 4 T/F/S inputs
+            uint32_t T[4], F[4], S[4];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                uint32_t L0, H0, L1, H1;
+                planes(half * 4 + q * 2 + k, L0, H0, L1, H1);
+                uint32_t qa, qb, ka, kb;
+                front4(L0, H0, T[2 * k], qa, ka);
+                front4(L1, H1, T[2 * k + 1], qb, kb);
+                // fail-QC byte masks
+                F[2 * k] = T[2 * k] & perm(0u, 0xFF00FF00u, qa);
+                F[2 * k + 1] = T[2 * k + 1] & perm(0u, 0xFF00FF00u, qb);
+                // S byte: LUT over (qcfail, dup) = one-hot {QC only, DUP only, both} in bits 0-2 plus a
+                // QC-class template in bits 6 (pass) / 7 (fail), which survives only for primary paired
+                // reads (bits 6,7 of the keep-mask).  lut & (keep | 0x3f) is ONE v_bitop3_b32.
+                S[2 * k] = perm(0u, 0x84428140u, qa) & (ka | 0x3F3F3F3Fu);
+                S[2 * k + 1] = perm(0u, 0x84428140u, qb) & (kb | 0x3F3F3F3Fu);
+            }
+            uint32_t t2a, t2b, f2a, f2b, s2a, s2b;
+            csa(t2a, s.t1, s.t1, T[0], T[1]);
+            csa(t2b, s.t1, s.t1, T[2], T[3]);
+            csa(f2a, s.f1, s.f1, F[0], F[1]);
+            csa(f2b, s.f1, s.f1, F[2], F[3]);
+            csa(s2a, s.s1, s.s1, S[0], S[1]);
+            csa(s2b, s.s1, s.s1, S[2], S[3]);
+            csa(q ? t4b : t4a, s.t2, s.t2, t2a, t2b);
+            csa(q ? f4b : f4a, s.f2, s.f2, f2a, f2b);
+            csa(q ? s4b : s4a, s.s2, s.s2, s2a, s2b);
+        }
+        csa(half ? t8b : t8a, s.t4, s.t4, t4a, t4b);
+        csa(half ? f8b : f8a, s.f4, s.f4, f4a, f4b);
+        csa(half ? s8b : s8a, s.s4, s.s4, s4a, s4b);
+    }
+    uint32_t ct, cf, cs;
+    csa(ct, s.t8, s.t8, t8a, t8b);  // weight-16 carries
+    csa(cf, s.f8, s.f8, f8a, f8b);
+    csa(cs, s.s8, s.s8, s8a, s8b);
+    chain_push<0, DEPTH>(s, blk, ct, cf, cs);
+}
+
 // Flush: fold every plane into the 21 u32 lane counters and clear them.  `pushed` = steps pushed since the last
 // flush (wave-uniform): chain level j can hold something only after 2^j steps, so a short run (a mid-size array
 // leaves each workgroup a few dozen steps) skips the empty upper levels with scalar branches.  The flush is paid once
@@ -202,6 +257,17 @@ __device__ __forceinline__ void flush(Lane<DEPTH>& s, uint32_t pushed)
     s.t1 = s.t2 = s.t4 = s.t8 = 0;
     s.f1 = s.f2 = s.f4 = s.f8 = 0;
     s.s1 = s.s2 = s.s4 = s.s8 = 0;
+}
+
+// The tail of every step: one more step pushed; an epoch ends at 2^DEPTH - 1 of them with a flush.
+template <int DEPTH>
+__device__ __forceinline__ void end_step(Lane<DEPTH>& s, uint32_t& blk)
+{
+    ++blk;
+    if (blk == (1u << DEPTH) - 1u) {
+        flush(s, (1u << DEPTH) - 1u);
+        blk = 0;
+    }
 }
 
 // Map the 21 internal totals to the reference's 32 slots (index = FLAGSTAT_*_OFF,
@@ -317,6 +383,35 @@ __device__ __forceinline__ void load_step(uint4 (&v)[kUnroll], const uint4* __re
     } else {
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) v[u] = load_guarded(a0, j0 + u * USTRIDE, lo, hi);
+    }
+}
+
+// ------------------------------------------------------------------ schedule 71, as the kernels derived from K1 run it
+// (flagstat_segments.hip, flagstat_wide.hip, flagstat_where.hip, flagstat_filter.hip)
+constexpr int kRollDistance = 6;   // a vector's registers are re-issued for the vector six places on: 24 KiB in flight per CU
+constexpr int kWaveStride = 64;    // vectors between a lane's consecutive loads: each wave a contiguous 8 KiB of a step
+
+// Steps pushed in a wave's first epoch before it starts: wave w of a workgroup begins at 64 * w, so at any time at most one wave
+// of a CU is flushing while the other three keep their loads in flight (K1's mode bit 4; any start is arithmetically fine).
+__device__ __forceinline__ uint32_t stagger_start(uint32_t wave)
+{
+    return (wave & 3u) * 64u;
+}
+
+// Re-issue under ROLL what vector uu has just been read out of: v[] holds one item per vector of a step (the vector itself, or
+// a side column's bytes for it) and the item AHEAD places in front of uu was consumed.  ROLL 0: nothing (the step's items are
+// all in v[]).  ROLL 1: the target is a later vector of the same step (`cur`) or an early one of the lane's next (`next`).
+// ROLL 2 (the lane's last step): `cur` only.  `stride`: units of P between a lane's consecutive vectors.
+template <int ROLL, int AHEAD = 0, typename V, typename P, typename Load>
+__device__ __forceinline__ void reissue(int uu, V (&v)[kUnroll], const P* __restrict__ cur, const P* __restrict__ next, int stride,
+                                        Load&& load)
+{
+    if constexpr (ROLL != 0) {
+        const int t = uu + kRollDistance + AHEAD;
+        if (t < kUnroll)
+            v[t] = load(cur + t * stride);
+        else if constexpr (ROLL == 1)
+            v[t - kUnroll] = load(next + (t - kUnroll) * stride);
     }
 }
 

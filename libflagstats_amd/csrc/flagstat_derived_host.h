@@ -1,0 +1,275 @@
+// flagstat_derived_host.h -- internal: the host code that the kernels derived from K1 share (flagstat_wide.hip, flagstat_where.hip,
+// flagstat_filter.hip): the launcher's step split and store-form memset, the 33-word device row of a synchronous call, and the
+// bodies of the three entry forms -- on the caller's stream, synchronous over device memory, chunked over host memory.  What
+// differs between the kernels arrives as arguments and callables: the names of their pointers, the text of their refusals, how
+// a chunk's inputs are copied and launched.  A HIP call that a callable makes goes through FS_HIP_TRY there, so the text of its
+// failure names the caller's own expression.
+// (Product library only: the entries check allocation extents, which the host-stub build does not have.)
+#ifndef FLAGSTAT_DERIVED_HOST_H_
+#define FLAGSTAT_DERIVED_HOST_H_
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cstdio>
+#include <mutex>
+#include <optional>
+
+#include "flagstat_engine.h"
+#include "flagstat_kernels.h"
+
+namespace fsdrv {
+
+constexpr int kStepBytes = fsk::kVecPerStep * 16;   // 32 KiB
+
+// ------------------------------------------------------------------ launchers
+// Host-side geometry: everything a kernel assumes is derived here from (address, n, W), W = elem_bytes in {2, 4, 8}.  The array
+// is addressed on the 16-byte grid of its aligned-down base: geo[0..5] = lo, hi (the caller's elements occupy positions [lo, hi)
+// of the grid of W-byte elements), nsteps, fast_begin, fast_end (steps whose vectors are all fully inside [lo, hi)) and the
+// grid, at most one workgroup per step.  n == 0: all zero.  tests/steps_oracle.StepSplit(addr % 16, n * W / 2, grid) mirrors it.
+inline hipError_t step_split(uint64_t address, uint64_t n, int elem_bytes, uint32_t grid, uint64_t* geo)
+{
+    if ((elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) || grid == 0 || geo == nullptr) return hipErrorInvalidValue;
+    const uint64_t W = static_cast<uint64_t>(elem_bytes);
+    const uint64_t addr = address;
+    if (addr & (W - 1)) return hipErrorInvalidValue;
+    for (int i = 0; i < 6; ++i) geo[i] = 0;
+    if (n == 0) return hipSuccess;
+    if (n > (~0ull - 64) / W) return hipErrorInvalidValue;  // n * W must be a size
+    const uint64_t base = addr & ~static_cast<uint64_t>(15);
+    const uint64_t epv = 16 / W;                            // elements per 16-byte vector
+    const uint64_t lo = (addr - base) / W, hi = lo + n;
+    const uint64_t nvec = (hi + epv - 1) / epv;
+    const uint64_t vps = fsk::kVecPerStep;
+    const uint64_t nsteps = (nvec + vps - 1) / vps;
+    // steps whose vectors are all fully inside [lo, hi)
+    uint64_t fast_begin = (lo == 0) ? 0 : 1;
+    uint64_t fast_end = (hi / epv) / vps;
+    if (fast_end < fast_begin) fast_end = fast_begin;
+    if (static_cast<uint64_t>(grid) > nsteps) grid = static_cast<uint32_t>(nsteps);
+    // a wave's totals are uint32: a workgroup pushes at most ceil(nsteps / grid) + 2 steps (its share and both edge steps), each
+    // wave a quarter of every step
+    const uint64_t wave_elems_per_step = kStepBytes / W / (fsk::kThreads / 64);
+    if (nsteps / grid + 3 >= (1ull << 32) / wave_elems_per_step) return hipErrorInvalidValue;
+    geo[0] = lo;
+    geo[1] = hi;
+    geo[2] = nsteps;
+    geo[3] = fast_begin;
+    geo[4] = fast_end;
+    geo[5] = grid;
+    return hipSuccess;
+}
+
+// the store form's zeroes in front of a launch: the counters and the optional 33rd word (mask, selected count), in one memset
+// where they are one allocation's 33 words
+inline hipError_t zero_counters(uint64_t* d_out32, uint64_t* d_word, hipStream_t stream)
+{
+    const bool together = d_word == d_out32 + 32;
+    hipError_t e = hipMemsetAsync(d_out32, 0, (together ? 33 : 32) * sizeof(uint64_t), stream);
+    if (e == hipSuccess && d_word && !together) e = hipMemsetAsync(d_word, 0, sizeof(uint64_t), stream);
+    return e;
+}
+
+// ------------------------------------------------------------------ C entry points
+// device counters[32] + the 33rd word of one synchronous call; `what` names the allocation in the text of a failure
+struct Row {
+    uint64_t* d = nullptr;
+    ~Row()
+    {
+        if (d) (void)hipFree(d);
+    }
+    int alloc(const char* what)
+    {
+        const hipError_t e = hipMalloc(&d, 33 * sizeof(uint64_t));
+        if (e != hipSuccess) {
+            d = nullptr;
+            return fsint::fail_hip(what, e);
+        }
+        return 0;
+    }
+};
+
+// how the 33rd word of a result combines in the accumulate form: a count is added, a mask is ORed
+enum WordOp { kWordAdd, kWordOr };
+
+// a call's result into the caller's host words: stored (flags bit 0) or accumulated
+inline void apply(uint64_t* out, uint64_t* word, const uint64_t (&got)[33], int flags, WordOp op)
+{
+    if (flags & 1) {
+        for (int i = 0; i < 32; ++i) out[i] = got[i];
+        if (word) *word = got[32];
+    } else {
+        for (int i = 0; i < 32; ++i) out[i] += got[i];
+        if (word) *word = op == kWordOr ? (*word | got[32]) : *word + got[32];
+    }
+}
+
+// the result of a call over no elements
+inline void store_nothing(uint64_t* out, uint64_t* word, int flags)
+{
+    if (flags & 1) {
+        for (int i = 0; i < 32; ++i) out[i] = 0;
+        if (word) *word = 0;
+    }
+}
+
+// an input array of a call: its pointer, the name the refusals use for it, the bytes the call reads from it on
+struct Input {
+    const void* p;
+    const char* name;
+    uint64_t bytes;
+};
+
+// the optional 33rd word of a device entry: `why` completes "<name> must be device memory (<why>)"
+struct DeviceWord {
+    const void* p;
+    const char* name;
+    const char* why;
+};
+
+inline int fail_devices(const char* a, const char* b)
+{
+    char buf[128];
+    std::snprintf(buf, sizeof buf, "%s and %s live on different devices", a, b);
+    return fsint::fail_text(buf);
+}
+
+// A device entry up to its launch: d_out is plain device memory, so is the 33rd word if there is one, on the same device, as
+// is every input; the engine of that device, made current (for as long as this object lives), and the caller's stream on it.
+struct DeviceCall {
+    fsint::Engine* e = nullptr;
+    hipStream_t s = nullptr;
+    std::optional<fsint::DeviceGuard> guard;
+
+    int open(const void* d_out, const DeviceWord& word, const Input* in, int inputs, void* stream)
+    {
+        int dev_out = -1, dev = -1;
+        bool plain = false;
+        int rc = fsint::device_of_pointer(d_out, "d_out", &dev_out, &plain);
+        if (rc) return rc;
+        if (!plain) return fsint::fail_text("d_out must be device memory (the counters are added with device atomics)");
+        if (word.p) {
+            rc = fsint::device_of_pointer(word.p, word.name, &dev, &plain);
+            if (rc) return rc;
+            if (!plain) {
+                char buf[128];
+                std::snprintf(buf, sizeof buf, "%s must be device memory (%s)", word.name, word.why);
+                return fsint::fail_text(buf);
+            }
+            if (dev != dev_out) return fail_devices(word.name, "d_out");
+        }
+        for (int i = 0; i < inputs; ++i) {
+            rc = fsint::device_of_pointer(in[i].p, in[i].name, &dev);
+            if (rc) return rc;
+            if (dev != dev_out) return fail_devices(in[i].name, "d_out");
+        }
+        e = fsint::engine_for_device(dev_out);
+        if (!e) return -1;
+        guard.emplace(e->device);
+        if (!guard->ok()) return -1;
+        s = static_cast<hipStream_t>(stream);
+        return fsint::check_stream_device(s, e->device);
+    }
+};
+
+// every allocation holds what the call touches of it
+inline int check_extents(const void* d_out, const DeviceWord& word, const Input* in, int inputs)
+{
+    int rc;
+    if ((rc = fsint::check_extent(d_out, 32 * sizeof(uint64_t), "d_out"))) return rc;
+    if (word.p && (rc = fsint::check_extent(word.p, sizeof(uint64_t), word.name))) return rc;
+    for (int i = 0; i < inputs; ++i)
+        if ((rc = fsint::check_extent(in[i].p, in[i].bytes, in[i].name))) return rc;
+    return 0;
+}
+
+inline int fits_always(fsint::Engine&) { return 0; }
+
+// The synchronous form over device memory (n > 0, arguments checked): the inputs live on one device (the first one's); under its
+// engine's lock `fits(e)` may still refuse, the extents are checked, then `launch(e, row, s)` counts in the store form into a
+// row of its own on the engine's first stream and the result is applied to the caller's host words.
+template <typename Fits, typename Launch>
+int sync_call(const Input* in, int inputs, const char* row_what, uint64_t* out, uint64_t* word, int flags, WordOp op, Fits&& fits,
+              Launch&& launch)
+{
+    int rc, dev = -1, dev_i = -1;
+    rc = fsint::device_of_pointer(in[0].p, in[0].name, &dev);
+    if (rc) return rc;
+    for (int i = 1; i < inputs; ++i) {
+        rc = fsint::device_of_pointer(in[i].p, in[i].name, &dev_i);
+        if (rc) return rc;
+        if (dev_i != dev) return fail_devices(in[i].name, in[0].name);
+    }
+    fsint::Engine* ep = fsint::engine_for_device(dev);
+    if (!ep) return -1;
+    fsint::Engine& e = *ep;
+    std::lock_guard<std::mutex> lk(e.mu);
+    if (fsint::engine_alive(e)) return -1;
+    fsint::DeviceGuard guard(e.device);
+    if (!guard.ok()) return -1;
+    if ((rc = fits(e))) return rc;
+    for (int i = 0; i < inputs; ++i)
+        if ((rc = fsint::check_extent(in[i].p, in[i].bytes, in[i].name))) return rc;
+    Row row;
+    if ((rc = row.alloc(row_what))) return rc;
+    uint64_t got[33];
+    hipStream_t s = e.stream[0];
+    if ((rc = launch(e, row, s))) return rc;
+    FS_HIP_TRY(hipMemcpyAsync(got, row.d, sizeof got, hipMemcpyDeviceToHost, s));
+    FS_HIP_TRY(hipStreamSynchronize(s));
+    apply(out, word, got, flags, op);
+    return 0;
+}
+
+// The form over host memory (n > 0, arguments checked): the n elements cross the bus in chunks of `chunk` elements, alternating
+// between the default engine's two streams and staging buffers of `slot_flags` uint16 each (the copy of chunk k + 1 overlaps the
+// kernel on chunk k).  `chunk_fn(e, row, sl, pos, c)` copies the inputs of elements [pos, pos + c) into e.stage[sl] and launches
+// on e.stream[sl]; every chunk's launch adds into the same row.  `fits(e)` may refuse before anything is staged.
+template <typename Fits, typename Chunk>
+int host_call(uint64_t n, uint64_t chunk, uint64_t slot_flags, const char* row_what, uint64_t* out, uint64_t* word, int flags,
+              WordOp op, Fits&& fits, Chunk&& chunk_fn)
+{
+    int rc;
+    fsint::Engine* ep = fsint::default_engine();
+    if (!ep) return -1;
+    fsint::Engine& e = *ep;
+    std::lock_guard<std::mutex> lk(e.mu);
+    if (fsint::engine_alive(e)) return -1;
+    fsint::DeviceGuard guard(e.device);
+    if (!guard.ok()) return -1;
+    fsint::lz4_gpu_other_use(e);
+    Row row;
+    if ((rc = row.alloc(row_what))) return rc;
+    if ((rc = fsint::engine_second(e))) return rc;
+    if ((rc = fits(e))) return rc;
+    const int slots = n > chunk ? 2 : 1;
+    for (int i = 0; i < slots; ++i)
+        if ((rc = fsint::stage_reserve(e, i, slot_flags))) return rc;
+    hipStream_t s0 = e.stream[0];
+    FS_HIP_TRY(hipMemsetAsync(row.d, 0, 33 * sizeof(uint64_t), s0));
+    if (slots == 2 && (rc = fsint::stream_wait_stream(e, e.stream[1], s0))) return rc;
+    uint64_t k = 0;
+    for (uint64_t pos = 0; pos < n; pos += chunk, ++k) {
+        const int sl = static_cast<int>(k % static_cast<uint64_t>(slots));
+        const uint64_t c = n - pos < chunk ? n - pos : chunk;
+        if ((rc = chunk_fn(e, row, sl, pos, c))) return rc;
+    }
+    if (slots == 2 && (rc = fsint::stream_wait_stream(e, s0, e.stream[1]))) return rc;
+    uint64_t got[33];
+    FS_HIP_TRY(hipMemcpyAsync(got, row.d, sizeof got, hipMemcpyDeviceToHost, s0));
+    FS_HIP_TRY(hipStreamSynchronize(s0));
+    if (slots == 2) FS_HIP_TRY(hipStreamSynchronize(e.stream[1]));
+    apply(out, word, got, flags, op);
+    return 0;
+}
+
+// host streaming chunk in flags (knob "chunk_flags", at least one vector)
+inline uint64_t chunk_flags()
+{
+    const uint64_t c = fsint::knobs().chunk_flags.load();
+    return c < 8 ? 8 : c;
+}
+
+}  // namespace fsdrv
+
+#endif

@@ -8,8 +8,8 @@
 // aligned-down base, the caller's flags occupy positions [lo, hi) of it, steps of 32 KiB = 16,384 flags; workgroup b takes the
 // head edge step (b == 0), the tail edge step, then the fully covered steps b, b + G, ...; each wave owns a contiguous 8 KiB of a
 // step and lane l takes vectors u * 64 + l.  Edge steps go through guarded, zero-filling loaders; fast steps through K1's rolling
-// load schedule 71, restated below as flagstat_where.hip restates it.  The step split is fsk_where_geometry's
-// (tests/steps_oracle.StepSplit).
+// load schedule 71 (reissue, flagstat_count_core.h).  The step split is fsdrv::step_split's (flagstat_derived_host.h;
+// tests/steps_oracle.StepSplit).
 //
 // MAPQ.  Addressed like the byte form of `where`: the launcher hands the kernel `mq` such that the 8 bytes of grid vector j are
 // mq[8 j .. 8 j + 8), at any alignment; one unaligned dwordx2 per vector, loaded with the vector on fast steps.  Edge steps read
@@ -42,14 +42,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <cstdio>
-#include <mutex>
-
 #include "../../include/libflagstats_hip.h"
 #include "flagstat_count_core.h"
-#include "flagstat_engine.h"
+#include "flagstat_derived_host.h"
 #include "flagstat_filter.h"
-#include "flagstat_where.h"
 
 namespace fsk {
 
@@ -126,93 +122,10 @@ __device__ __forceinline__ uint32_t pass4(const FilterArgs& f, uint32_t L, uint3
     }
 }
 
-// One step: 8 vectors of 16 B per lane = 64 flags -> 16 T, 16 F, 16 S inputs through K1's tree (flagstat_kernels.hip: step).
-// ROLL 0 (edge steps): the vectors are in v[], their MAPQ bytes in m[], the bits of their positions that are elements in vb[].
-// ROLL 1, 2: K1's schedule 71 -- vector u's registers are re-issued for vector u + 6 of the same step (`cur`) or, ROLL 1 only,
-// u - 2 of the next one (`next`): 6 loads = 24 KiB per CU in flight; the MAPQ bytes of a vector are loaded right in front of
-// it and read out with it.
-template <bool MAPQ, int ROLL>
-__device__ __forceinline__ void filter_step(Lane<kFilterDepth>& s, const FilterArgs& f, uint4 (&v)[kUnroll], uint2 (&m)[kUnroll],
-                                            const uint32_t (&vb)[kUnroll], uint32_t blk, uint32_t& cnt, const uint4* __restrict__ cur,
-                                            const uint4* __restrict__ next, const uint8_t* __restrict__ mcur,
-                                            const uint8_t* __restrict__ mnext)
-{
-    constexpr int RD = 6;
-    constexpr int US = 64;           // each wave a contiguous 8 KiB of the step
-    constexpr int MS = US * 8;       // MAPQ bytes between a lane's consecutive vectors
-    uint32_t t8a = 0, t8b = 0, f8a = 0, f8b = 0, s8a = 0, s8b = 0;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        uint32_t t4a = 0, t4b = 0, f4a = 0, f4b = 0, s4a = 0, s4b = 0;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            uint32_t T[4], F[4], S[4];
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                uint32_t L0, H0, L1, H1;
-                const int uu = half * 4 + q * 2 + k;  // a constant after unrolling
-                __builtin_amdgcn_sched_barrier(0);
-                split_out(v[uu], L0, H0, L1, H1);
-                uint2 w = make_uint2(0, 0);
-                if constexpr (MAPQ) {
-                    w = m[uu];
-                    if constexpr (ROLL != 0) {
-                        if (uu + RD < kUnroll)
-                            m[uu + RD] = load_mapq(mcur + (uu + RD) * MS);
-                        else if constexpr (ROLL == 1)
-                            m[uu + RD - kUnroll] = load_mapq(mnext + (uu + RD - kUnroll) * MS);
-                    }
-                }
-                if constexpr (ROLL != 0) {
-                    if (uu + RD < kUnroll)
-                        v[uu + RD] = load_vec<true>(cur + (uu + RD) * US);
-                    else if constexpr (ROLL == 1)
-                        v[uu + RD - kUnroll] = load_vec<true>(next + (uu + RD - kUnroll) * US);
-                }
-                uint32_t p0 = pass4<MAPQ>(f, L0, H0, w.x);
-                uint32_t p1 = pass4<MAPQ>(f, L1, H1, w.y);
-                if constexpr (ROLL == 0) {
-                    p0 &= nibble_to_bit7(vb[uu] & 15u);
-                    p1 &= nibble_to_bit7(vb[uu] >> 4);
-                }
-                cnt += __builtin_popcount(p0);
-                cnt += __builtin_popcount(p1);
-                const uint32_t M0 = perm(0u, 0u, p0), M1 = perm(0u, 0u, p1);   // selector 0x80 -> 0xFF, 0x00 -> source byte 0 = 0x00
-                L0 &= M0;
-                H0 &= M0;
-                L1 &= M1;
-                H1 &= M1;
-                __builtin_amdgcn_sched_barrier(0);
-                uint32_t qa, qb, ka, kb;
-                front4(L0, H0, T[2 * k], qa, ka);
-                front4(L1, H1, T[2 * k + 1], qb, kb);
-                F[2 * k] = T[2 * k] & perm(0u, 0xFF00FF00u, qa);
-                F[2 * k + 1] = T[2 * k + 1] & perm(0u, 0xFF00FF00u, qb);
-                S[2 * k] = perm(0u, 0x84428140u, qa) & (ka | 0x3F3F3F3Fu);
-                S[2 * k + 1] = perm(0u, 0x84428140u, qb) & (kb | 0x3F3F3F3Fu);
-            }
-            uint32_t t2a, t2b, f2a, f2b, s2a, s2b;
-            csa(t2a, s.t1, s.t1, T[0], T[1]);
-            csa(t2b, s.t1, s.t1, T[2], T[3]);
-            csa(f2a, s.f1, s.f1, F[0], F[1]);
-            csa(f2b, s.f1, s.f1, F[2], F[3]);
-            csa(s2a, s.s1, s.s1, S[0], S[1]);
-            csa(s2b, s.s1, s.s1, S[2], S[3]);
-            csa(q ? t4b : t4a, s.t2, s.t2, t2a, t2b);
-            csa(q ? f4b : f4a, s.f2, s.f2, f2a, f2b);
-            csa(q ? s4b : s4a, s.s2, s.s2, s2a, s2b);
-        }
-        csa(half ? t8b : t8a, s.t4, s.t4, t4a, t4b);
-        csa(half ? f8b : f8a, s.f4, s.f4, f4a, f4b);
-        csa(half ? s8b : s8a, s.s4, s.s4, s4a, s4b);
-    }
-    uint32_t ct, cf, cs;
-    csa(ct, s.t8, s.t8, t8a, t8b);  // weight-16 carries
-    csa(cf, s.f8, s.f8, f8a, f8b);
-    csa(cs, s.s8, s.s8, s8a, s8b);
-    chain_push<0, kFilterDepth>(s, blk, ct, cf, cs);
-}
-
+// One step: 8 vectors of 16 B per lane = 64 flags through K1's tree (tree_step, flagstat_count_core.h), the predicate applied in
+// the per-vector front.  ROLL 0 (edge steps): the vectors are in v[], their MAPQ bytes in m[], the bits of their positions that
+// are elements in vb[].  ROLL 1, 2: K1's schedule 71 (reissue, same header); the MAPQ bytes of a vector are loaded right in
+// front of it and read out with it.
 template <bool MAPQ, int ROLL>
 __device__ __forceinline__ void filter_step_and_count(Lane<kFilterDepth>& s, const FilterArgs& f, uint4 (&v)[kUnroll], uint2 (&m)[kUnroll],
                                                       const uint32_t (&vb)[kUnroll], uint32_t& blk, uint32_t& cnt,
@@ -220,12 +133,31 @@ __device__ __forceinline__ void filter_step_and_count(Lane<kFilterDepth>& s, con
                                                       const uint8_t* __restrict__ mcur = nullptr, const uint8_t* __restrict__ mnext = nullptr)
 {
     blk = __builtin_amdgcn_readfirstlane(blk);
-    filter_step<MAPQ, ROLL>(s, f, v, m, vb, blk, cnt, cur, next, mcur, mnext);
-    ++blk;
-    if (blk == (1u << kFilterDepth) - 1u) {
-        flush(s, (1u << kFilterDepth) - 1u);
-        blk = 0;
-    }
+    tree_step<kFilterDepth>(s, blk, [&](int uu, uint32_t& L0, uint32_t& H0, uint32_t& L1, uint32_t& H1) __attribute__((always_inline)) {
+        __builtin_amdgcn_sched_barrier(0);
+        split_out(v[uu], L0, H0, L1, H1);
+        uint2 w = make_uint2(0, 0);
+        if constexpr (MAPQ) {
+            w = m[uu];
+            reissue<ROLL>(uu, m, mcur, mnext, kWaveStride * 8, load_mapq);
+        }
+        reissue<ROLL>(uu, v, cur, next, kWaveStride, load_vec<true>);
+        uint32_t p0 = pass4<MAPQ>(f, L0, H0, w.x);
+        uint32_t p1 = pass4<MAPQ>(f, L1, H1, w.y);
+        if constexpr (ROLL == 0) {
+            p0 &= nibble_to_bit7(vb[uu] & 15u);
+            p1 &= nibble_to_bit7(vb[uu] >> 4);
+        }
+        cnt += __builtin_popcount(p0);
+        cnt += __builtin_popcount(p1);
+        const uint32_t M0 = perm(0u, 0u, p0), M1 = perm(0u, 0u, p1);   // selector 0x80 -> 0xFF, 0x00 -> source byte 0 = 0x00
+        L0 &= M0;
+        H0 &= M0;
+        L1 &= M1;
+        H1 &= M1;
+        __builtin_amdgcn_sched_barrier(0);
+    });
+    end_step<kFilterDepth>(s, blk);
 }
 
 // a0: 16-B aligned-down base; the caller's flags occupy positions [lo, hi) of its grid.  mq: the MAPQ column on the same grid
@@ -242,8 +174,8 @@ __global__ __launch_bounds__(kThreads) void flagstat_count_filter(const uint4* _
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = threadIdx.x >> 6;
     constexpr int VPS = kVecPerStep;
-    constexpr int US = 64;
-    const uint64_t lane_off = static_cast<uint64_t>(wave) * (64 * kUnroll) + lane;
+    constexpr int US = kWaveStride;
+    const uint64_t lane_off = static_cast<uint64_t>(wave) * (US * kUnroll) + lane;
     const uint64_t G = gridDim.x;
     FilterArgs f;
     {
@@ -255,8 +187,7 @@ __global__ __launch_bounds__(kThreads) void flagstat_count_filter(const uint4* _
         f.y7 = (min_mapq & 0x7Fu) * 0x01010101u;
         f.k = min_mapq < 128u ? 0x80808080u : 0u;
     }
-    // wave w starts its first epoch at 64 * w, so at most one wave of a CU is flushing at any time (K1's mode bit 4)
-    uint32_t blk = (wave & 3u) * 64u;
+    uint32_t blk = stagger_start(wave);
     uint32_t cnt = 0;                           // passing elements of this lane
 
     auto edge_step = [&](uint64_t st) {
@@ -282,7 +213,7 @@ __global__ __launch_bounds__(kThreads) void flagstat_count_filter(const uint4* _
     uint64_t st = blockIdx.x;
     if (st < fast_begin) st += G;  // fast_begin is 0 or 1
     if (st < fast_end) {
-        constexpr int RD = 6;
+        constexpr int RD = kRollDistance;
         uint4 v[kUnroll];
         uint2 m[kUnroll];
         const uint32_t vb[kUnroll] = {};        // not looked at on fast steps
@@ -344,17 +275,10 @@ extern "C" hipError_t fsk_launch_filter(const uint16_t* d_array, uint64_t n, uin
     if ((mode & ~3) || grid == 0 || d_out32 == nullptr || require > 0xFFFFu || exclude > 0xFFFFu || min_mapq > 255u ||
         (n && (d_array == nullptr || (min_mapq && d_mapq == nullptr))))
         return hipErrorInvalidValue;
-    // the step split is K1's and where's: one copy of that arithmetic (the selection arguments only fill geo[6], geo[7])
-    uint64_t geo[8];
-    hipError_t e = fsk_where_geometry(reinterpret_cast<uintptr_t>(d_array), n, 0, 8, grid, geo);
+    uint64_t geo[6];
+    hipError_t e = fsdrv::step_split(reinterpret_cast<uintptr_t>(d_array), n, 2, grid, geo);
     if (e != hipSuccess) return e;
-    if (mode & 1) {
-        // counters and the selected count in one memset where they are one allocation's 33 words
-        const bool together = d_selected == d_out32 + 32;
-        e = hipMemsetAsync(d_out32, 0, (together ? 33 : 32) * sizeof(uint64_t), stream);
-        if (e == hipSuccess && d_selected && !together) e = hipMemsetAsync(d_selected, 0, sizeof(uint64_t), stream);
-        if (e != hipSuccess) return e;
-    }
+    if ((mode & 1) && (e = fsdrv::zero_counters(d_out32, d_selected, stream)) != hipSuccess) return e;
     // a bit both required and excluded: no flag passes (samtools accepts the pair); the kernel's test assumes a disjoint pair
     if (n == 0 || (require & exclude)) return hipSuccess;
     const uint4* a0 = reinterpret_cast<const uint4*>(reinterpret_cast<uintptr_t>(d_array) & ~static_cast<uintptr_t>(15));
@@ -372,9 +296,8 @@ extern "C" hipError_t fsk_launch_filter(const uint16_t* d_array, uint64_t n, uin
 }
 
 // ------------------------------------------------------------------ C entry points (include/libflagstats_hip.h)
-using fsint::DeviceGuard;
+// The three forms are the shared bodies of flagstat_derived_host.h; the 33rd word is the number of passing elements.
 using fsint::Engine;
-using fsint::fail_hip;
 using fsint::fail_text;
 
 namespace {
@@ -395,48 +318,13 @@ int filter_args(const uint16_t* array, uint64_t n, uint32_t require, uint32_t ex
     return 0;
 }
 
-// device counters[32] + selected count of one synchronous call
-struct FilterRow {
-    uint64_t* d = nullptr;
-    ~FilterRow()
-    {
-        if (d) (void)hipFree(d);
-    }
-    int alloc()
-    {
-        const hipError_t e = hipMalloc(&d, 33 * sizeof(uint64_t));
-        if (e != hipSuccess) {
-            d = nullptr;
-            return fail_hip("hipMalloc(filter counters)", e);
-        }
-        return 0;
-    }
-};
+constexpr const char* kFilterAlloc = "hipMalloc(filter counters)";
 
-void filter_apply(uint64_t* out, uint64_t* selected, const uint64_t (&got)[33], int flags)
-{
-    if (flags & 1) {
-        for (int i = 0; i < 32; ++i) out[i] = got[i];
-        if (selected) *selected = got[32];
-    } else {
-        for (int i = 0; i < 32; ++i) out[i] += got[i];
-        if (selected) *selected += got[32];
-    }
-}
-
-void filter_nothing(uint64_t* out, uint64_t* selected, int flags)
-{
-    if (flags & 1) {
-        for (int i = 0; i < 32; ++i) out[i] = 0;
-        if (selected) *selected = 0;
-    }
-}
-
-// a wave's totals are uint32: the one thing fsk_where_geometry still refuses once filter_args has passed (where's limit)
+// a wave's totals are uint32: the one thing the step split still refuses once filter_args has passed
 int filter_fits(const uint16_t* array, uint64_t n, uint32_t grid)
 {
-    uint64_t geo[8];
-    if (fsk_where_geometry(reinterpret_cast<uintptr_t>(array), n, 0, 8, grid, geo) != hipSuccess)
+    uint64_t geo[6];
+    if (fsdrv::step_split(reinterpret_cast<uintptr_t>(array), n, 2, grid, geo) != hipSuccess)
         return fail_text("n is too large for this grid: a wave's uint32 totals could overflow (split the array)");
     return 0;
 }
@@ -452,41 +340,15 @@ int FLAGSTATS_hip_device_u16_filter(const uint16_t* d_array, uint64_t n, uint32_
     int rc = filter_args(d_array, n, require, exclude, d_mapq, min_mapq, d_out, flags);
     if (rc) return rc;
     if (n == 0 && !(flags & 1)) return 0;
-    int dev_out = -1, dev = -1;
-    bool plain = false;
-    rc = fsint::device_of_pointer(d_out, "d_out", &dev_out, &plain);
-    if (rc) return rc;
-    if (!plain) return fail_text("d_out must be device memory (the counters are added with device atomics)");
-    if (d_selected) {
-        rc = fsint::device_of_pointer(d_selected, "d_selected", &dev, &plain);
-        if (rc) return rc;
-        if (!plain) return fail_text("d_selected must be device memory (the count is added with a device atomic)");
-        if (dev != dev_out) return fail_text("d_selected and d_out live on different devices");
-    }
-    if (n) {
-        rc = fsint::device_of_pointer(d_array, "d_array", &dev);
-        if (rc) return rc;
-        if (dev != dev_out) return fail_text("d_array and d_out live on different devices");
-        if (min_mapq) {
-            rc = fsint::device_of_pointer(d_mapq, "d_mapq", &dev);
-            if (rc) return rc;
-            if (dev != dev_out) return fail_text("d_mapq and d_out live on different devices");
-        }
-    }
-    Engine* e = fsint::engine_for_device(dev_out);
-    if (!e) return -1;
-    DeviceGuard guard(e->device);
-    if (!guard.ok()) return -1;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = fsint::check_stream_device(s, e->device);
-    if (rc) return rc;
+    const fsdrv::DeviceWord word{d_selected, "d_selected", "the count is added with a device atomic"};
+    const fsdrv::Input in[] = {{d_array, "d_array", n * 2}, {d_mapq, "d_mapq", n}};
+    const int inputs = n ? (min_mapq ? 2 : 1) : 0;
+    fsdrv::DeviceCall call;
+    if ((rc = call.open(d_out, word, in, inputs, stream))) return rc;
+    Engine* e = call.e;
+    hipStream_t s = call.s;
     if ((rc = filter_fits(d_array, n, fsint::grid_for(*e)))) return rc;
-    if ((rc = fsint::check_extent(d_out, 32 * sizeof(uint64_t), "d_out"))) return rc;
-    if (d_selected && (rc = fsint::check_extent(d_selected, sizeof(uint64_t), "d_selected"))) return rc;
-    if (n) {
-        if ((rc = fsint::check_extent(d_array, n * 2, "d_array"))) return rc;
-        if (min_mapq && (rc = fsint::check_extent(d_mapq, n, "d_mapq"))) return rc;
-    }
+    if ((rc = fsdrv::check_extents(d_out, word, in, inputs))) return rc;
     FS_HIP_TRY(fsk_launch_filter(d_array, n, require, exclude, d_mapq, min_mapq, d_out, d_selected, flags & 3, fsint::grid_for(*e), s));
     return 0;
 }
@@ -498,36 +360,17 @@ int FLAGSTATS_hip_device_u16_filter_sync(const uint16_t* d_array, uint64_t n, ui
     int rc = filter_args(d_array, n, require, exclude, d_mapq, min_mapq, out, flags);
     if (rc) return rc;
     if (n == 0) {
-        filter_nothing(out, selected, flags);
+        fsdrv::store_nothing(out, selected, flags);
         return 0;
     }
-    int dev = -1, dev_mapq = -1;
-    rc = fsint::device_of_pointer(d_array, "d_array", &dev);
-    if (rc) return rc;
-    if (min_mapq) {
-        rc = fsint::device_of_pointer(d_mapq, "d_mapq", &dev_mapq);
-        if (rc) return rc;
-        if (dev_mapq != dev) return fail_text("d_mapq and d_array live on different devices");
-    }
-    Engine* ep = fsint::engine_for_device(dev);
-    if (!ep) return -1;
-    Engine& e = *ep;
-    std::lock_guard<std::mutex> lk(e.mu);
-    if (fsint::engine_alive(e)) return -1;
-    DeviceGuard guard(e.device);
-    if (!guard.ok()) return -1;
-    if ((rc = filter_fits(d_array, n, fsint::grid_for(e)))) return rc;
-    if ((rc = fsint::check_extent(d_array, n * 2, "d_array"))) return rc;
-    if (min_mapq && (rc = fsint::check_extent(d_mapq, n, "d_mapq"))) return rc;
-    FilterRow row;
-    if ((rc = row.alloc())) return rc;
-    uint64_t got[33];
-    hipStream_t s = e.stream[0];
-    FS_HIP_TRY(fsk_launch_filter(d_array, n, require, exclude, d_mapq, min_mapq, row.d, row.d + 32, 1 | (flags & 2), fsint::grid_for(e), s));
-    FS_HIP_TRY(hipMemcpyAsync(got, row.d, sizeof got, hipMemcpyDeviceToHost, s));
-    FS_HIP_TRY(hipStreamSynchronize(s));
-    filter_apply(out, selected, got, flags);
-    return 0;
+    const fsdrv::Input in[] = {{d_array, "d_array", n * 2}, {d_mapq, "d_mapq", n}};
+    return fsdrv::sync_call(
+        in, min_mapq ? 2 : 1, kFilterAlloc, out, selected, flags, fsdrv::kWordAdd,
+        [&](Engine& e) { return filter_fits(d_array, n, fsint::grid_for(e)); },
+        [&](Engine& e, fsdrv::Row& row, hipStream_t s) {
+            FS_HIP_TRY(fsk_launch_filter(d_array, n, require, exclude, d_mapq, min_mapq, row.d, row.d + 32, 1 | (flags & 2), fsint::grid_for(e), s));
+            return 0;
+        });
 }
 
 int FLAGSTATS_hip_u16_x64_filter(const uint16_t* array, uint64_t n, uint32_t require, uint32_t exclude, const uint8_t* mapq, uint32_t min_mapq,
@@ -537,51 +380,25 @@ int FLAGSTATS_hip_u16_x64_filter(const uint16_t* array, uint64_t n, uint32_t req
     int rc = filter_args(array, n, require, exclude, mapq, min_mapq, out, flags);
     if (rc) return rc;
     if (n == 0) {
-        filter_nothing(out, selected, flags);
+        fsdrv::store_nothing(out, selected, flags);
         return 0;
     }
-    Engine* ep = fsint::default_engine();
-    if (!ep) return -1;
-    Engine& e = *ep;
-    std::lock_guard<std::mutex> lk(e.mu);
-    if (fsint::engine_alive(e)) return -1;
-    DeviceGuard guard(e.device);
-    if (!guard.ok()) return -1;
-    fsint::lz4_gpu_other_use(e);
-    FilterRow row;
-    if ((rc = row.alloc())) return rc;
-    if ((rc = fsint::engine_second(e))) return rc;
-    // the array crosses the bus in chunks of "chunk_flags" flags, alternating between the engine's two streams and staging
-    // buffers (the copy of chunk k + 1 overlaps the kernel on chunk k); a chunk's slice of the MAPQ column rides in the same
-    // staging buffer, behind the flags.  Every chunk's launch adds into the same device counters.
-    const uint64_t chunk = fsint::knobs().chunk_flags.load() < 8 ? 8 : fsint::knobs().chunk_flags.load();
+    // a chunk's slice of the MAPQ column rides in the same staging buffer, behind the flags
+    const uint64_t chunk = fsdrv::chunk_flags();
     const uint64_t cap = n < chunk ? n : chunk;                         // flags of the largest chunk
     const uint64_t mapq_cap = min_mapq ? cap : 0;                       // bytes of its MAPQ slice
-    if ((rc = filter_fits(nullptr, cap, fsint::grid_for(e)))) return rc;
-    const int slots = n > chunk ? 2 : 1;
-    for (int i = 0; i < slots; ++i)
-        if ((rc = fsint::stage_reserve(e, i, cap + (mapq_cap + 1) / 2))) return rc;
-    hipStream_t s0 = e.stream[0];
-    FS_HIP_TRY(hipMemsetAsync(row.d, 0, 33 * sizeof(uint64_t), s0));
-    if (slots == 2 && (rc = fsint::stream_wait_stream(e, e.stream[1], s0))) return rc;
-    const uint32_t grid = fsint::grid_for(e);
     const int mode = flags & 2;
-    uint64_t k = 0;
-    for (uint64_t pos = 0; pos < n; pos += chunk, ++k) {
-        const int sl = static_cast<int>(k % static_cast<uint64_t>(slots));
-        const uint64_t c = n - pos < chunk ? n - pos : chunk;
-        uint8_t* d_mapq = reinterpret_cast<uint8_t*>(e.stage[sl] + cap);
-        FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], array + pos, c * 2, hipMemcpyHostToDevice, e.stream[sl]));
-        if (min_mapq) FS_HIP_TRY(hipMemcpyAsync(d_mapq, mapq + pos, c, hipMemcpyHostToDevice, e.stream[sl]));
-        FS_HIP_TRY(fsk_launch_filter(e.stage[sl], c, require, exclude, d_mapq, min_mapq, row.d, row.d + 32, mode, grid, e.stream[sl]));
-    }
-    if (slots == 2 && (rc = fsint::stream_wait_stream(e, s0, e.stream[1]))) return rc;
-    uint64_t got[33];
-    FS_HIP_TRY(hipMemcpyAsync(got, row.d, sizeof got, hipMemcpyDeviceToHost, s0));
-    FS_HIP_TRY(hipStreamSynchronize(s0));
-    if (slots == 2) FS_HIP_TRY(hipStreamSynchronize(e.stream[1]));
-    filter_apply(out, selected, got, flags);
-    return 0;
+    return fsdrv::host_call(
+        n, chunk, cap + (mapq_cap + 1) / 2, kFilterAlloc, out, selected, flags, fsdrv::kWordAdd,
+        [&](Engine& e) { return filter_fits(nullptr, cap, fsint::grid_for(e)); },
+        [&](Engine& e, fsdrv::Row& row, int sl, uint64_t pos, uint64_t c) {
+            const uint32_t grid = fsint::grid_for(e);
+            uint8_t* d_mapq = reinterpret_cast<uint8_t*>(e.stage[sl] + cap);
+            FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], array + pos, c * 2, hipMemcpyHostToDevice, e.stream[sl]));
+            if (min_mapq) FS_HIP_TRY(hipMemcpyAsync(d_mapq, mapq + pos, c, hipMemcpyHostToDevice, e.stream[sl]));
+            FS_HIP_TRY(fsk_launch_filter(e.stage[sl], c, require, exclude, d_mapq, min_mapq, row.d, row.d + 32, mode, grid, e.stream[sl]));
+            return 0;
+        });
 }
 
 }  // extern "C"

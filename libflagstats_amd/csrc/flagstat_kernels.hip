@@ -57,75 +57,33 @@ __device__ __forceinline__ void step(Lane<DEPTH>& s, uint4 (&v)[kUnroll], uint32
                                      const uint4* __restrict__ cur = nullptr)
 {
     static_assert(STAGE == 0 || STAGE == 1 || STAGE == 9, "the product carries three schedules; the others: flagstat_kernels_tuning.hip");
-    uint32_t t8a = 0, t8b = 0, f8a = 0, f8b = 0, s8a = 0, s8b = 0;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        uint32_t t4a = 0, t4b = 0, f4a = 0, f4b = 0, s4a = 0, s4b = 0;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            // two vectors -> 4 T/F/S inputs
-            uint32_t T[4], F[4], S[4];
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                uint32_t L0, H0, L1, H1;
-                const int uu = half * 4 + q * 2 + k;  // a constant after unrolling
-                if constexpr (STAGE == 9) {
-                    constexpr int RD = 6;
-                    __builtin_amdgcn_sched_barrier(0);
-                    split_out(v[uu], L0, H0, L1, H1);
-                    if (uu + RD < 8)
-                        v[uu + RD] = load_vec<NT>(cur + (uu + RD) * USTRIDE);
-                    else if constexpr (HAS_NEXT)
-                        v[uu + RD - 8] = load_vec<NT>(next + (uu + RD - 8) * USTRIDE);
-                    __builtin_amdgcn_sched_barrier(0);
-                } else if constexpr (STAGE == 1) {
-                    // Split the vector out of its registers HERE (a load may land at any time, so the registers it
-                    // targets must be dead first), then re-issue into the same registers.  The asm keeps hipcc from
-                    // turning the reads into loop-top PHI moves (which wait for all 8 loads), the sched_barriers from
-                    // sinking the loads below the arithmetic.
-                    __builtin_amdgcn_sched_barrier(0);
-                    split_out(v[uu], L0, H0, L1, H1);
-                    v[uu] = load_vec<NT>(next + uu * USTRIDE);
-                    __builtin_amdgcn_sched_barrier(0);
-                } else {
-                    const uint4 x = v[uu];
-                    L0 = perm(x.y, x.x, 0x06040200u);
-                    H0 = perm(x.y, x.x, 0x07050301u);
-                    L1 = perm(x.w, x.z, 0x06040200u);
-                    H1 = perm(x.w, x.z, 0x07050301u);
-                }
-                uint32_t qa, qb, ka, kb;
-                front4(L0, H0, T[2 * k], qa, ka);
-                front4(L1, H1, T[2 * k + 1], qb, kb);
-                // fail-QC byte masks
-                F[2 * k] = T[2 * k] & perm(0u, 0xFF00FF00u, qa);
-                F[2 * k + 1] = T[2 * k + 1] & perm(0u, 0xFF00FF00u, qb);
-                // S byte: LUT over (qcfail, dup) = one-hot {QC only, DUP only, both} in bits 0-2 plus a
-                // QC-class template in bits 6 (pass) / 7 (fail), which survives only for primary paired
-                // reads (bits 6,7 of the keep-mask).  lut & (keep | 0x3f) is ONE v_bitop3_b32.
-                S[2 * k] = perm(0u, 0x84428140u, qa) & (ka | 0x3F3F3F3Fu);
-                S[2 * k + 1] = perm(0u, 0x84428140u, qb) & (kb | 0x3F3F3F3Fu);
-            }
-            uint32_t t2a, t2b, f2a, f2b, s2a, s2b;
-            csa(t2a, s.t1, s.t1, T[0], T[1]);
-            csa(t2b, s.t1, s.t1, T[2], T[3]);
-            csa(f2a, s.f1, s.f1, F[0], F[1]);
-            csa(f2b, s.f1, s.f1, F[2], F[3]);
-            csa(s2a, s.s1, s.s1, S[0], S[1]);
-            csa(s2b, s.s1, s.s1, S[2], S[3]);
-            csa(q ? t4b : t4a, s.t2, s.t2, t2a, t2b);
-            csa(q ? f4b : f4a, s.f2, s.f2, f2a, f2b);
-            csa(q ? s4b : s4a, s.s2, s.s2, s2a, s2b);
+    tree_step<DEPTH>(s, blk, [&](int uu, uint32_t& L0, uint32_t& H0, uint32_t& L1, uint32_t& H1) __attribute__((always_inline)) {
+        if constexpr (STAGE == 9) {
+            constexpr int RD = kRollDistance;
+            __builtin_amdgcn_sched_barrier(0);
+            split_out(v[uu], L0, H0, L1, H1);
+            if (uu + RD < 8)
+                v[uu + RD] = load_vec<NT>(cur + (uu + RD) * USTRIDE);
+            else if constexpr (HAS_NEXT)
+                v[uu + RD - 8] = load_vec<NT>(next + (uu + RD - 8) * USTRIDE);
+            __builtin_amdgcn_sched_barrier(0);
+        } else if constexpr (STAGE == 1) {
+            // Split the vector out of its registers HERE (a load may land at any time, so the registers it
+            // targets must be dead first), then re-issue into the same registers.  The asm keeps hipcc from
+            // turning the reads into loop-top PHI moves (which wait for all 8 loads), the sched_barriers from
+            // sinking the loads below the arithmetic.
+            __builtin_amdgcn_sched_barrier(0);
+            split_out(v[uu], L0, H0, L1, H1);
+            v[uu] = load_vec<NT>(next + uu * USTRIDE);
+            __builtin_amdgcn_sched_barrier(0);
+        } else {
+            const uint4 x = v[uu];
+            L0 = perm(x.y, x.x, 0x06040200u);
+            H0 = perm(x.y, x.x, 0x07050301u);
+            L1 = perm(x.w, x.z, 0x06040200u);
+            H1 = perm(x.w, x.z, 0x07050301u);
         }
-        csa(half ? t8b : t8a, s.t4, s.t4, t4a, t4b);
-        csa(half ? f8b : f8a, s.f4, s.f4, f4a, f4b);
-        csa(half ? s8b : s8a, s.s4, s.s4, s4a, s4b);
-    }
-    uint32_t ct, cf, cs;
-    csa(ct, s.t8, s.t8, t8a, t8b);  // weight-16 carries
-    csa(cf, s.f8, s.f8, f8a, f8b);
-    csa(cs, s.s8, s.s8, s8a, s8b);
-    chain_push<0, DEPTH>(s, blk, ct, cf, cs);
+    });
 }
 
 template <int DEPTH, int STAGE = 0, bool NT = false, int USTRIDE = 64, bool HAS_NEXT = true>
@@ -136,11 +94,7 @@ __device__ __forceinline__ void step_and_count(Lane<DEPTH>& s, uint4 (&v)[kUnrol
     // s_and_saveexec per chain level) unless told so
     blk = __builtin_amdgcn_readfirstlane(blk);
     step<DEPTH, STAGE, NT, USTRIDE, HAS_NEXT>(s, v, blk, next, cur);
-    ++blk;
-    if (blk == (1u << DEPTH) - 1u) {
-        flush(s, (1u << DEPTH) - 1u);
-        blk = 0;
-    }
+    end_step(s, blk);
 }
 
 // ------------------------------------------------------------------ K1
@@ -167,7 +121,7 @@ __global__ __launch_bounds__(kThreads) void flagstat_count(const uint4* __restri
     // starts wave w of a workgroup at 64 * w: its first epoch is that much shorter, so at any time at most one wave of
     // a CU is flushing while the other three keep their loads in flight.  (Any start is arithmetically fine: the chain
     // levels are adders; a level whose pending plane is empty while its bit of blk is set just adds a zero.)
-    uint32_t blk = (mode & 16) ? (wave & 3u) * 64u : 0u;
+    uint32_t blk = (mode & 16) ? stagger_start(wave) : 0u;
 
     constexpr bool ROLL = (STAGE != 0);
     if constexpr (ROLL) {
@@ -203,7 +157,7 @@ __global__ __launch_bounds__(kThreads) void flagstat_count(const uint4* __restri
                 step_and_count(s, v, blk);
             }
         } else {
-            constexpr int RD = 6;
+            constexpr int RD = kRollDistance;
             if (st < fast_end) {
                 uint4 v[kUnroll];
                 const uint4* p = a0 + st * VPS + lane_off;

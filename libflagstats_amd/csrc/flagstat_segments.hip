@@ -12,8 +12,8 @@
 //
 // Two regimes, chosen per stretch:
 //   * a run of at least `min_units` whole units inside one segment goes through K1's carry-save chain with K1's rolling load
-//     schedule (6 vectors in flight per lane), restated below from flagstat_kernels.hip; the chain is flushed (exact at any
-//     step count) when the segment ends;
+//     schedule (6 vectors in flight per lane): the shared tree_step, end_step and reissue of flagstat_count_core.h; the
+//     chain is flushed (exact at any step count) when the segment ends;
 //   * every other unit -- a segment's ragged head and tail, and units dense with boundaries -- is loaded once (8 vectors in
 //     flight) and counted per flag: front4's bytes are popcounted into the lane counters, one piece of the unit per segment it
 //     holds (lanes and flags outside the piece read as zero, which counts nothing), and the wave reduction runs once per
@@ -40,72 +40,20 @@ constexpr int kSegDepth = 8;                       // chain depth as K1: epochs 
 constexpr int kSegRowVecs = 64;                    // vectors per row (one per lane)
 constexpr int kSegUnitVecs = kSegWaveFlags / 8;    // 512 vectors per unit
 
-// K1's step at the default schedule (flagstat_kernels.hip, STAGE 9 with non-temporal loads, each wave a contiguous 8 KiB):
-// vector u's registers are re-issued for vector u + 6 of the same unit (`cur`) or u - 2 of the next (`next`, if HAS_NEXT).
-template <bool HAS_NEXT>
-__device__ __forceinline__ void seg_step(Lane<kSegDepth>& s, uint4 (&v)[kUnroll], uint32_t blk, const uint4* __restrict__ cur,
-                                         const uint4* __restrict__ next)
-{
-    uint32_t t8a = 0, t8b = 0, f8a = 0, f8b = 0, s8a = 0, s8b = 0;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        uint32_t t4a = 0, t4b = 0, f4a = 0, f4b = 0, s4a = 0, s4b = 0;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            uint32_t T[4], F[4], S[4];
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                uint32_t L0, H0, L1, H1;
-                const int uu = half * 4 + q * 2 + k;
-                constexpr int RD = 6;
-                __builtin_amdgcn_sched_barrier(0);
-                split_out(v[uu], L0, H0, L1, H1);
-                if (uu + RD < 8)
-                    v[uu + RD] = load_vec<true>(cur + (uu + RD) * kSegRowVecs);
-                else if constexpr (HAS_NEXT)
-                    v[uu + RD - 8] = load_vec<true>(next + (uu + RD - 8) * kSegRowVecs);
-                __builtin_amdgcn_sched_barrier(0);
-                uint32_t qa, qb, ka, kb;
-                front4(L0, H0, T[2 * k], qa, ka);
-                front4(L1, H1, T[2 * k + 1], qb, kb);
-                F[2 * k] = T[2 * k] & perm(0u, 0xFF00FF00u, qa);
-                F[2 * k + 1] = T[2 * k + 1] & perm(0u, 0xFF00FF00u, qb);
-                S[2 * k] = perm(0u, 0x84428140u, qa) & (ka | 0x3F3F3F3Fu);
-                S[2 * k + 1] = perm(0u, 0x84428140u, qb) & (kb | 0x3F3F3F3Fu);
-            }
-            uint32_t t2a, t2b, f2a, f2b, s2a, s2b;
-            csa(t2a, s.t1, s.t1, T[0], T[1]);
-            csa(t2b, s.t1, s.t1, T[2], T[3]);
-            csa(f2a, s.f1, s.f1, F[0], F[1]);
-            csa(f2b, s.f1, s.f1, F[2], F[3]);
-            csa(s2a, s.s1, s.s1, S[0], S[1]);
-            csa(s2b, s.s1, s.s1, S[2], S[3]);
-            csa(q ? t4b : t4a, s.t2, s.t2, t2a, t2b);
-            csa(q ? f4b : f4a, s.f2, s.f2, f2a, f2b);
-            csa(q ? s4b : s4a, s.s2, s.s2, s2a, s2b);
-        }
-        csa(half ? t8b : t8a, s.t4, s.t4, t4a, t4b);
-        csa(half ? f8b : f8a, s.f4, s.f4, f4a, f4b);
-        csa(half ? s8b : s8a, s.s4, s.s4, s4a, s4b);
-    }
-    uint32_t ct, cf, cs;
-    csa(ct, s.t8, s.t8, t8a, t8b);
-    csa(cf, s.f8, s.f8, f8a, f8b);
-    csa(cs, s.s8, s.s8, s8a, s8b);
-    chain_push<0, kSegDepth>(s, blk, ct, cf, cs);
-}
-
+// K1's step at the default schedule (schedule 71 with non-temporal loads, each wave a contiguous 8 KiB): vector u's registers are
+// re-issued for vector u + 6 of the same unit (`cur`) or u - 2 of the next (`next`, if HAS_NEXT).
 template <bool HAS_NEXT>
 __device__ __forceinline__ void seg_step_and_count(Lane<kSegDepth>& s, uint4 (&v)[kUnroll], uint32_t& blk, const uint4* cur,
                                                    const uint4* next)
 {
     blk = __builtin_amdgcn_readfirstlane(blk);
-    seg_step<HAS_NEXT>(s, v, blk, cur, next);
-    ++blk;
-    if (blk == (1u << kSegDepth) - 1u) {
-        flush(s, (1u << kSegDepth) - 1u);
-        blk = 0;
-    }
+    tree_step<kSegDepth>(s, blk, [&](int uu, uint32_t& L0, uint32_t& H0, uint32_t& L1, uint32_t& H1) __attribute__((always_inline)) {
+        __builtin_amdgcn_sched_barrier(0);
+        split_out(v[uu], L0, H0, L1, H1);
+        reissue<HAS_NEXT ? 1 : 2>(uu, v, cur, next, kSegRowVecs, load_vec<true>);
+        __builtin_amdgcn_sched_barrier(0);
+    });
+    end_step<kSegDepth>(s, blk);
 }
 
 // Per-flag form: the 8 flags of one vector straight into the 21 lane counters (T bits 0-7, F bits 0-7, S bits 0-2 and 6-7).
@@ -335,7 +283,7 @@ __global__ __launch_bounds__(kThreads) void flagstat_segments(const uint4* __res
                 const uint4* p = a0 + u * kSegUnitVecs + lane;
                 uint4 v[kUnroll];
 #pragma unroll
-                for (int r = 0; r < 6; ++r) {
+                for (int r = 0; r < kRollDistance; ++r) {
                     v[r] = load_vec<true>(p + r * kSegRowVecs);
                     __builtin_amdgcn_sched_barrier(0);
                 }

@@ -7,7 +7,7 @@
 // edge step (b == 0), the tail edge step, then the fully covered steps b, b + G, ...; each wave owns a contiguous 8 KiB of a
 // step and lane l takes vectors u * 64 + l.  Edge steps go through guarded, zero-filling loaders; fast steps through K1's
 // rolling load schedule (schedule 71: a vector's registers are re-issued for the vector six places on as soon as it has been
-// read out), restated below from flagstat_kernels.hip.  tests/steps_oracle.StepSplit(addr % 16, n, grid) is the step split.
+// read out: reissue, flagstat_count_core.h).  tests/steps_oracle.StepSplit(addr % 16, n, grid) is the step split.
 //
 // Selection.  The selection is addressed on the array's grid as well: the launcher hands the kernel a base pointer `sel` such
 // that the 8 bits of grid vector j start at bit `sh` of sel[j] (bitmap: sh == 0 takes one byte per vector, otherwise two are
@@ -34,12 +34,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <cstdio>
-#include <mutex>
-
 #include "../../include/libflagstats_hip.h"
 #include "flagstat_count_core.h"
-#include "flagstat_engine.h"
+#include "flagstat_derived_host.h"
 #include "flagstat_where.h"
 
 namespace fsk {
@@ -155,109 +152,41 @@ __device__ __forceinline__ uint4 lookup(const uint4* __restrict__ lut, uint32_t 
     return lut[bits];
 }
 
-// One step: 8 vectors of 16 B per lane = 64 flags -> 16 T, 16 F, 16 S inputs through K1's tree (flagstat_kernels.hip: step).
-// ROLL 0: the vectors are in v[], their selection in m[].  ROLL 1, 2: K1's schedule 71 -- vector u's registers are re-issued for
-// vector u + 6 of the same step (`cur`) or, ROLL 1 only, u - 2 of the next one (`next`): 6 loads = 24 KiB per CU in flight.
-// Byte form: the selection of a vector is loaded right in front of it and read out with it.  Bitmap form: the selection byte
-// of a vector is loaded in front of the vector BEFORE it, so that it has arrived when that one has; its table entry is
-// fetched while that one is being counted and handed on in `entry` (on entry: vector 0's; on exit, ROLL 1: the next step's
-// vector 0's).
-template <int SEL_BITS, bool FUNNEL, int ROLL>
-__device__ __forceinline__ void where_step(Lane<kWhereDepth>& s, uint4 (&v)[kUnroll], typename SelWord<SEL_BITS>::type (&m)[kUnroll],
-                                           uint4& entry, const uint4* __restrict__ lut, uint32_t blk, uint32_t sh, uint32_t& cnt,
-                                           const uint4* __restrict__ cur, const uint4* __restrict__ next, const uint8_t* __restrict__ scur,
-                                           const uint8_t* __restrict__ snext)
-{
-    constexpr int RD = 6;
-    constexpr int US = 64;                              // each wave a contiguous 8 KiB of the step
-    constexpr int SS = SEL_BITS == 1 ? US : US * 8;     // selection bytes between a lane's consecutive vectors
-    uint32_t t8a = 0, t8b = 0, f8a = 0, f8b = 0, s8a = 0, s8b = 0;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        uint32_t t4a = 0, t4b = 0, f4a = 0, f4b = 0, s4a = 0, s4b = 0;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            uint32_t T[4], F[4], S[4];
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                uint32_t L0, H0, L1, H1;
-                const int uu = half * 4 + q * 2 + k;  // a constant after unrolling
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (SEL_BITS == 1) {
-                    split_out_selected(v[uu], entry, L0, H0, L1, H1);
-                    if (uu + 1 < kUnroll || ROLL == 1) entry = lookup(lut, m[(uu + 1) % kUnroll], sh, cnt);
-                    if constexpr (ROLL != 0) {
-                        if (uu + RD + 1 < kUnroll)
-                            m[uu + RD + 1] = load_sel<SEL_BITS, FUNNEL>(scur + (uu + RD + 1) * SS);
-                        else if constexpr (ROLL == 1)
-                            m[uu + RD + 1 - kUnroll] = load_sel<SEL_BITS, FUNNEL>(snext + (uu + RD + 1 - kUnroll) * SS);
-                    }
-                } else {
-                    split_out(v[uu], L0, H0, L1, H1);
-                    const uint2 w = m[uu];
-                    if constexpr (ROLL != 0) {
-                        if (uu + RD < kUnroll)
-                            m[uu + RD] = load_sel<SEL_BITS, FUNNEL>(scur + (uu + RD) * SS);
-                        else if constexpr (ROLL == 1)
-                            m[uu + RD - kUnroll] = load_sel<SEL_BITS, FUNNEL>(snext + (uu + RD - kUnroll) * SS);
-                    }
-                    uint32_t M0, M1;
-                    bytes_masks(w, M0, M1, cnt);
-                    L0 &= M0;
-                    H0 &= M0;
-                    L1 &= M1;
-                    H1 &= M1;
-                }
-                if constexpr (ROLL != 0) {
-                    if (uu + RD < kUnroll)
-                        v[uu + RD] = load_vec<true>(cur + (uu + RD) * US);
-                    else if constexpr (ROLL == 1)
-                        v[uu + RD - kUnroll] = load_vec<true>(next + (uu + RD - kUnroll) * US);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                uint32_t qa, qb, ka, kb;
-                front4(L0, H0, T[2 * k], qa, ka);
-                front4(L1, H1, T[2 * k + 1], qb, kb);
-                F[2 * k] = T[2 * k] & perm(0u, 0xFF00FF00u, qa);
-                F[2 * k + 1] = T[2 * k + 1] & perm(0u, 0xFF00FF00u, qb);
-                S[2 * k] = perm(0u, 0x84428140u, qa) & (ka | 0x3F3F3F3Fu);
-                S[2 * k + 1] = perm(0u, 0x84428140u, qb) & (kb | 0x3F3F3F3Fu);
-            }
-            uint32_t t2a, t2b, f2a, f2b, s2a, s2b;
-            csa(t2a, s.t1, s.t1, T[0], T[1]);
-            csa(t2b, s.t1, s.t1, T[2], T[3]);
-            csa(f2a, s.f1, s.f1, F[0], F[1]);
-            csa(f2b, s.f1, s.f1, F[2], F[3]);
-            csa(s2a, s.s1, s.s1, S[0], S[1]);
-            csa(s2b, s.s1, s.s1, S[2], S[3]);
-            csa(q ? t4b : t4a, s.t2, s.t2, t2a, t2b);
-            csa(q ? f4b : f4a, s.f2, s.f2, f2a, f2b);
-            csa(q ? s4b : s4a, s.s2, s.s2, s2a, s2b);
-        }
-        csa(half ? t8b : t8a, s.t4, s.t4, t4a, t4b);
-        csa(half ? f8b : f8a, s.f4, s.f4, f4a, f4b);
-        csa(half ? s8b : s8a, s.s4, s.s4, s4a, s4b);
-    }
-    uint32_t ct, cf, cs;
-    csa(ct, s.t8, s.t8, t8a, t8b);  // weight-16 carries
-    csa(cf, s.f8, s.f8, f8a, f8b);
-    csa(cs, s.s8, s.s8, s8a, s8b);
-    chain_push<0, kWhereDepth>(s, blk, ct, cf, cs);
-}
-
+// One step: 8 vectors of 16 B per lane = 64 flags through K1's tree (tree_step, flagstat_count_core.h), the selection applied in
+// the per-vector front.  ROLL 0: the vectors are in v[], their selection in m[].  ROLL 1, 2: K1's schedule 71 (reissue, same
+// header).  Byte form: the selection of a vector is loaded right in front of it and read out with it.  Bitmap form: the
+// selection byte of a vector is loaded in front of the vector BEFORE it, so that it has arrived when that one has; its table
+// entry is fetched while that one is being counted and handed on in `entry` (on entry: vector 0's; on exit, ROLL 1: the next
+// step's vector 0's).
 template <int SEL_BITS, bool FUNNEL, int ROLL>
 __device__ __forceinline__ void where_step_and_count(Lane<kWhereDepth>& s, uint4 (&v)[kUnroll], typename SelWord<SEL_BITS>::type (&m)[kUnroll],
                                                      uint4& entry, const uint4* __restrict__ lut, uint32_t& blk, uint32_t sh, uint32_t& cnt,
                                                      const uint4* __restrict__ cur = nullptr, const uint4* __restrict__ next = nullptr,
                                                      const uint8_t* __restrict__ scur = nullptr, const uint8_t* __restrict__ snext = nullptr)
 {
+    constexpr int SS = SEL_BITS == 1 ? kWaveStride : kWaveStride * 8;   // selection bytes between a lane's consecutive vectors
     blk = __builtin_amdgcn_readfirstlane(blk);
-    where_step<SEL_BITS, FUNNEL, ROLL>(s, v, m, entry, lut, blk, sh, cnt, cur, next, scur, snext);
-    ++blk;
-    if (blk == (1u << kWhereDepth) - 1u) {
-        flush(s, (1u << kWhereDepth) - 1u);
-        blk = 0;
-    }
+    tree_step<kWhereDepth>(s, blk, [&](int uu, uint32_t& L0, uint32_t& H0, uint32_t& L1, uint32_t& H1) __attribute__((always_inline)) {
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (SEL_BITS == 1) {
+            split_out_selected(v[uu], entry, L0, H0, L1, H1);
+            if (uu + 1 < kUnroll || ROLL == 1) entry = lookup(lut, m[(uu + 1) % kUnroll], sh, cnt);
+            reissue<ROLL, 1>(uu, m, scur, snext, SS, load_sel<SEL_BITS, FUNNEL>);
+        } else {
+            split_out(v[uu], L0, H0, L1, H1);
+            const uint2 w = m[uu];
+            reissue<ROLL>(uu, m, scur, snext, SS, load_sel<SEL_BITS, FUNNEL>);
+            uint32_t M0, M1;
+            bytes_masks(w, M0, M1, cnt);
+            L0 &= M0;
+            H0 &= M0;
+            L1 &= M1;
+            H1 &= M1;
+        }
+        reissue<ROLL>(uu, v, cur, next, kWaveStride, load_vec<true>);
+        __builtin_amdgcn_sched_barrier(0);
+    });
+    end_step<kWhereDepth>(s, blk);
 }
 
 // a0: 16-B aligned-down base; the caller's flags occupy positions [lo, hi) of its grid.  sel, shift: the selection on the same
@@ -282,12 +211,11 @@ __global__ __launch_bounds__(kThreads) void flagstat_count_where(const uint4* __
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = threadIdx.x >> 6;
     constexpr int VPS = kVecPerStep;
-    constexpr int US = 64;
+    constexpr int US = kWaveStride;
     constexpr int SB = SEL_BITS == 1 ? 1 : 8;   // selection bytes per vector
-    const uint64_t lane_off = static_cast<uint64_t>(wave) * (64 * kUnroll) + lane;
+    const uint64_t lane_off = static_cast<uint64_t>(wave) * (US * kUnroll) + lane;
     const uint64_t G = gridDim.x;
-    // wave w starts its first epoch at 64 * w, so at most one wave of a CU is flushing at any time (K1's mode bit 4)
-    uint32_t blk = (wave & 3u) * 64u;
+    uint32_t blk = stagger_start(wave);
     uint32_t cnt = 0;                           // selected elements of this lane
     const uint32_t sh = FUNNEL ? __builtin_amdgcn_readfirstlane(shift) : 0u;
     uint4 entry = make_uint4(0, 0, 0, 0);       // bitmap form: the table entry of the vector that is counted next
@@ -311,7 +239,7 @@ __global__ __launch_bounds__(kThreads) void flagstat_count_where(const uint4* __
     uint64_t st = blockIdx.x;
     if (st < fast_begin) st += G;  // fast_begin is 0 or 1
     if (st < fast_end) {
-        constexpr int RD = 6;
+        constexpr int RD = kRollDistance;
         uint4 v[kUnroll];
         sel_t m[kUnroll];
         const uint4* p = a0 + st * VPS + lane_off;
@@ -370,39 +298,35 @@ __global__ __launch_bounds__(kThreads) void flagstat_count_where(const uint4* __
 }  // namespace fsk
 
 // ------------------------------------------------------------------ launcher
-// Host-side geometry: everything the kernel assumes is derived here from (address, n, sel_offset, sel_bits).
+namespace {
+
+// the bytes of the selection that hold an element's bit or byte: [first, first + bytes) from `sel` on (n > 0).  The device
+// entries check the allocation from `sel` itself up to first + bytes: only `sel` is known to be device memory, and an offset at
+// or past the allocation's end would otherwise name an address the runtime cannot vouch for
+void where_extent(uint64_t n, uint64_t sel_offset, int sel_bits, uint64_t* first, uint64_t* bytes)
+{
+    *first = sel_bits == 1 ? sel_offset >> 3 : sel_offset;
+    *bytes = (sel_bits == 1 ? ((sel_offset + n - 1) >> 3) + 1 : sel_offset + n) - *first;
+}
+
+}  // namespace
+
+// Host-side geometry: the shared step split (flagstat_derived_host.h) at W = 2; geo[6], geo[7]: the selection bytes
+// [geo[6], geo[7]) hold the bit or byte of an element.
 extern "C" hipError_t fsk_where_geometry(uint64_t address, uint64_t n, uint64_t sel_offset, int sel_bits, uint32_t grid, uint64_t* geo)
 {
-    if ((sel_bits != 1 && sel_bits != 8) || grid == 0 || geo == nullptr) return hipErrorInvalidValue;
-    const uint64_t addr = address;
-    if (addr & 1u) return hipErrorInvalidValue;
-    for (int i = 0; i < 8; ++i) geo[i] = 0;
-    if (n == 0) return hipSuccess;
-    if (n > (~0ull - 64) / 2) return hipErrorInvalidValue;  // n * 2 must be a size
-    if (sel_offset > ~0ull - 64 - n) return hipErrorInvalidValue;  // sel_offset + n must be an index
-    const uint64_t base = addr & ~static_cast<uint64_t>(15);
-    const uint64_t lo = (addr - base) / 2, hi = lo + n;
-    const uint64_t nvec = (hi + 7) / 8;
-    const uint64_t vps = fsk::kVecPerStep;
-    const uint64_t nsteps = (nvec + vps - 1) / vps;
-    // steps whose vectors are all fully inside [lo, hi)
-    uint64_t fast_begin = (lo == 0) ? 0 : 1;
-    uint64_t fast_end = (hi / 8) / vps;
-    if (fast_end < fast_begin) fast_end = fast_begin;
-    if (static_cast<uint64_t>(grid) > nsteps) grid = static_cast<uint32_t>(nsteps);
-    // a wave's totals are uint32: a workgroup pushes at most ceil(nsteps / grid) + 2 steps (its share and both edge steps), each
-    // wave a quarter of every step
-    const uint64_t wave_elems_per_step = fsk::kVecPerStep * 8 / (fsk::kThreads / 64);
-    if (nsteps / grid + 3 >= (1ull << 32) / wave_elems_per_step) return hipErrorInvalidValue;
-    geo[0] = lo;
-    geo[1] = hi;
-    geo[2] = nsteps;
-    geo[3] = fast_begin;
-    geo[4] = fast_end;
-    geo[5] = grid;
-    // the selection bytes that hold the bit or byte of an element
-    geo[6] = sel_bits == 1 ? sel_offset >> 3 : sel_offset;
-    geo[7] = sel_bits == 1 ? ((sel_offset + n - 1) >> 3) + 1 : sel_offset + n;
+    if ((sel_bits != 1 && sel_bits != 8) || geo == nullptr) return hipErrorInvalidValue;
+    geo[6] = geo[7] = 0;
+    const hipError_t e = fsdrv::step_split(address, n, 2, grid, geo);
+    if (e != hipSuccess || n == 0) return e;
+    if (sel_offset > ~0ull - 64 - n) {  // sel_offset + n must be an index
+        for (int i = 0; i < 6; ++i) geo[i] = 0;
+        return hipErrorInvalidValue;
+    }
+    uint64_t first, bytes;
+    where_extent(n, sel_offset, sel_bits, &first, &bytes);
+    geo[6] = first;
+    geo[7] = first + bytes;
     return hipSuccess;
 }
 
@@ -414,13 +338,7 @@ extern "C" hipError_t fsk_launch_where(const uint16_t* d_array, uint64_t n, cons
     uint64_t geo[8];
     hipError_t e = fsk_where_geometry(reinterpret_cast<uintptr_t>(d_array), n, sel_offset, sel_bits, grid, geo);
     if (e != hipSuccess) return e;
-    if (mode & 1) {
-        // counters and the selected count in one memset where they are one allocation's 33 words
-        const bool together = d_selected == d_out32 + 32;
-        e = hipMemsetAsync(d_out32, 0, (together ? 33 : 32) * sizeof(uint64_t), stream);
-        if (e == hipSuccess && d_selected && !together) e = hipMemsetAsync(d_selected, 0, sizeof(uint64_t), stream);
-        if (e != hipSuccess) return e;
-    }
+    if ((mode & 1) && (e = fsdrv::zero_counters(d_out32, d_selected, stream)) != hipSuccess) return e;
     if (n == 0) return hipSuccess;
     const uint4* a0 = reinterpret_cast<const uint4*>(reinterpret_cast<uintptr_t>(d_array) & ~static_cast<uintptr_t>(15));
     const dim3 g(static_cast<uint32_t>(geo[5])), b(fsk::kThreads);
@@ -447,9 +365,8 @@ extern "C" hipError_t fsk_launch_where(const uint16_t* d_array, uint64_t n, cons
 }
 
 // ------------------------------------------------------------------ C entry points (include/libflagstats_hip.h)
-using fsint::DeviceGuard;
+// The three forms are the shared bodies of flagstat_derived_host.h; the 33rd word is the number of selected elements.
 using fsint::Engine;
-using fsint::fail_hip;
 using fsint::fail_text;
 
 namespace {
@@ -468,51 +385,19 @@ int where_args(const uint16_t* array, uint64_t n, const void* sel, uint64_t sel_
     return 0;
 }
 
-// the bytes of the selection that hold an element's bit or byte: [first, first + bytes) from `sel` on (n > 0).  The device
-// entries check the allocation from `sel` itself up to first + bytes: only `sel` is known to be device memory, and an offset at
-// or past the allocation's end would otherwise name an address the runtime cannot vouch for
-void where_extent(uint64_t n, uint64_t sel_offset, int sel_bits, uint64_t* first, uint64_t* bytes)
-{
-    *first = sel_bits == 1 ? sel_offset >> 3 : sel_offset;
-    *bytes = (sel_bits == 1 ? ((sel_offset + n - 1) >> 3) + 1 : sel_offset + n) - *first;
-}
+constexpr const char* kWhereAlloc = "hipMalloc(where counters)";
 
-// device counters[32] + selected count of one synchronous call
-struct WhereRow {
-    uint64_t* d = nullptr;
-    ~WhereRow()
+// the array and the selection as a call's inputs (n > 0)
+struct WhereInputs {
+    fsdrv::Input in[2];
+    WhereInputs(const uint16_t* d_array, uint64_t n, const void* d_sel, uint64_t sel_offset, int sel_bits)
     {
-        if (d) (void)hipFree(d);
-    }
-    int alloc()
-    {
-        const hipError_t e = hipMalloc(&d, 33 * sizeof(uint64_t));
-        if (e != hipSuccess) {
-            d = nullptr;
-            return fail_hip("hipMalloc(where counters)", e);
-        }
-        return 0;
+        uint64_t first = 0, bytes = 0;
+        if (n) where_extent(n, sel_offset, sel_bits, &first, &bytes);
+        in[0] = fsdrv::Input{d_array, "d_array", n * 2};
+        in[1] = fsdrv::Input{d_sel, "d_sel", first + bytes};
     }
 };
-
-void where_apply(uint64_t* out, uint64_t* selected, const uint64_t (&got)[33], int flags)
-{
-    if (flags & 1) {
-        for (int i = 0; i < 32; ++i) out[i] = got[i];
-        if (selected) *selected = got[32];
-    } else {
-        for (int i = 0; i < 32; ++i) out[i] += got[i];
-        if (selected) *selected += got[32];
-    }
-}
-
-void where_nothing(uint64_t* out, uint64_t* selected, int flags)
-{
-    if (flags & 1) {
-        for (int i = 0; i < 32; ++i) out[i] = 0;
-        if (selected) *selected = 0;
-    }
-}
 
 }  // namespace
 
@@ -525,40 +410,14 @@ int FLAGSTATS_hip_device_u16_where(const uint16_t* d_array, uint64_t n, const vo
     int rc = where_args(d_array, n, d_sel, sel_offset, sel_bits, d_out, flags);
     if (rc) return rc;
     if (n == 0 && !(flags & 1)) return 0;
-    int dev_out = -1, dev = -1;
-    bool plain = false;
-    rc = fsint::device_of_pointer(d_out, "d_out", &dev_out, &plain);
-    if (rc) return rc;
-    if (!plain) return fail_text("d_out must be device memory (the counters are added with device atomics)");
-    if (d_selected) {
-        rc = fsint::device_of_pointer(d_selected, "d_selected", &dev, &plain);
-        if (rc) return rc;
-        if (!plain) return fail_text("d_selected must be device memory (the count is added with a device atomic)");
-        if (dev != dev_out) return fail_text("d_selected and d_out live on different devices");
-    }
-    if (n) {
-        rc = fsint::device_of_pointer(d_array, "d_array", &dev);
-        if (rc) return rc;
-        if (dev != dev_out) return fail_text("d_array and d_out live on different devices");
-        rc = fsint::device_of_pointer(d_sel, "d_sel", &dev);
-        if (rc) return rc;
-        if (dev != dev_out) return fail_text("d_sel and d_out live on different devices");
-    }
-    Engine* e = fsint::engine_for_device(dev_out);
-    if (!e) return -1;
-    DeviceGuard guard(e->device);
-    if (!guard.ok()) return -1;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = fsint::check_stream_device(s, e->device);
-    if (rc) return rc;
-    if ((rc = fsint::check_extent(d_out, 32 * sizeof(uint64_t), "d_out"))) return rc;
-    if (d_selected && (rc = fsint::check_extent(d_selected, sizeof(uint64_t), "d_selected"))) return rc;
-    if (n) {
-        if ((rc = fsint::check_extent(d_array, n * 2, "d_array"))) return rc;
-        uint64_t first, bytes;
-        where_extent(n, sel_offset, sel_bits, &first, &bytes);
-        if ((rc = fsint::check_extent(d_sel, first + bytes, "d_sel"))) return rc;
-    }
+    const fsdrv::DeviceWord word{d_selected, "d_selected", "the count is added with a device atomic"};
+    const WhereInputs w(d_array, n, d_sel, sel_offset, sel_bits);
+    const int inputs = n ? 2 : 0;
+    fsdrv::DeviceCall call;
+    if ((rc = call.open(d_out, word, w.in, inputs, stream))) return rc;
+    if ((rc = fsdrv::check_extents(d_out, word, w.in, inputs))) return rc;
+    Engine* e = call.e;
+    hipStream_t s = call.s;
     FS_HIP_TRY(fsk_launch_where(d_array, n, d_sel, sel_offset, sel_bits, d_out, d_selected, flags & 3, fsint::grid_for(*e), s));
     return 0;
 }
@@ -570,35 +429,15 @@ int FLAGSTATS_hip_device_u16_where_sync(const uint16_t* d_array, uint64_t n, con
     int rc = where_args(d_array, n, d_sel, sel_offset, sel_bits, out, flags);
     if (rc) return rc;
     if (n == 0) {
-        where_nothing(out, selected, flags);
+        fsdrv::store_nothing(out, selected, flags);
         return 0;
     }
-    int dev = -1, dev_sel = -1;
-    rc = fsint::device_of_pointer(d_array, "d_array", &dev);
-    if (rc) return rc;
-    rc = fsint::device_of_pointer(d_sel, "d_sel", &dev_sel);
-    if (rc) return rc;
-    if (dev_sel != dev) return fail_text("d_sel and d_array live on different devices");
-    Engine* ep = fsint::engine_for_device(dev);
-    if (!ep) return -1;
-    Engine& e = *ep;
-    std::lock_guard<std::mutex> lk(e.mu);
-    if (fsint::engine_alive(e)) return -1;
-    DeviceGuard guard(e.device);
-    if (!guard.ok()) return -1;
-    if ((rc = fsint::check_extent(d_array, n * 2, "d_array"))) return rc;
-    uint64_t first, bytes;
-    where_extent(n, sel_offset, sel_bits, &first, &bytes);
-    if ((rc = fsint::check_extent(d_sel, first + bytes, "d_sel"))) return rc;
-    WhereRow row;
-    if ((rc = row.alloc())) return rc;
-    uint64_t got[33];
-    hipStream_t s = e.stream[0];
-    FS_HIP_TRY(fsk_launch_where(d_array, n, d_sel, sel_offset, sel_bits, row.d, row.d + 32, 1 | (flags & 2), fsint::grid_for(e), s));
-    FS_HIP_TRY(hipMemcpyAsync(got, row.d, sizeof got, hipMemcpyDeviceToHost, s));
-    FS_HIP_TRY(hipStreamSynchronize(s));
-    where_apply(out, selected, got, flags);
-    return 0;
+    const WhereInputs w(d_array, n, d_sel, sel_offset, sel_bits);
+    return fsdrv::sync_call(w.in, 2, kWhereAlloc, out, selected, flags, fsdrv::kWordAdd, fsdrv::fits_always,
+                            [&](Engine& e, fsdrv::Row& row, hipStream_t s) {
+                                FS_HIP_TRY(fsk_launch_where(d_array, n, d_sel, sel_offset, sel_bits, row.d, row.d + 32, 1 | (flags & 2), fsint::grid_for(e), s));
+                                return 0;
+                            });
 }
 
 int FLAGSTATS_hip_u16_x64_where(const uint16_t* array, uint64_t n, const void* sel, uint64_t sel_offset, int sel_bits, uint64_t* out,
@@ -608,55 +447,28 @@ int FLAGSTATS_hip_u16_x64_where(const uint16_t* array, uint64_t n, const void* s
     int rc = where_args(array, n, sel, sel_offset, sel_bits, out, flags);
     if (rc) return rc;
     if (n == 0) {
-        where_nothing(out, selected, flags);
+        fsdrv::store_nothing(out, selected, flags);
         return 0;
     }
-    Engine* ep = fsint::default_engine();
-    if (!ep) return -1;
-    Engine& e = *ep;
-    std::lock_guard<std::mutex> lk(e.mu);
-    if (fsint::engine_alive(e)) return -1;
-    DeviceGuard guard(e.device);
-    if (!guard.ok()) return -1;
-    fsint::lz4_gpu_other_use(e);
-    WhereRow row;
-    if ((rc = row.alloc())) return rc;
-    if ((rc = fsint::engine_second(e))) return rc;
-    // the array crosses the bus in chunks of "chunk_flags" flags, alternating between the engine's two streams and staging
-    // buffers (the copy of chunk k + 1 overlaps the kernel on chunk k); a chunk's slice of the selection rides in the same
-    // staging buffer, behind the flags: a bitmap slice from the byte that holds the chunk's first bit (the launch then starts
-    // (sel_offset + pos) & 7 bits into it).  Every chunk's launch adds into the same device counters.
-    const uint64_t chunk = fsint::knobs().chunk_flags.load() < 8 ? 8 : fsint::knobs().chunk_flags.load();
+    // a chunk's slice of the selection rides in the same staging buffer, behind the flags: a bitmap slice from the byte that
+    // holds the chunk's first bit (the launch then starts (sel_offset + pos) & 7 bits into it)
+    const uint64_t chunk = fsdrv::chunk_flags();
     const uint64_t cap = n < chunk ? n : chunk;                         // flags of the largest chunk
     const uint64_t sel_cap = sel_bits == 1 ? (cap + 7) / 8 + 1 : cap;   // bytes of its slice
-    const int slots = n > chunk ? 2 : 1;
-    for (int i = 0; i < slots; ++i)
-        if ((rc = fsint::stage_reserve(e, i, cap + (sel_cap + 1) / 2))) return rc;
-    hipStream_t s0 = e.stream[0];
-    FS_HIP_TRY(hipMemsetAsync(row.d, 0, 33 * sizeof(uint64_t), s0));
-    if (slots == 2 && (rc = fsint::stream_wait_stream(e, e.stream[1], s0))) return rc;
-    const uint32_t grid = fsint::grid_for(e);
     const int mode = flags & 2;
     const uint8_t* sel_src = static_cast<const uint8_t*>(sel);
-    uint64_t k = 0;
-    for (uint64_t pos = 0; pos < n; pos += chunk, ++k) {
-        const int sl = static_cast<int>(k % static_cast<uint64_t>(slots));
-        const uint64_t c = n - pos < chunk ? n - pos : chunk;
-        uint64_t first, bytes;
-        where_extent(c, sel_offset + pos, sel_bits, &first, &bytes);
-        uint8_t* d_sel = reinterpret_cast<uint8_t*>(e.stage[sl] + cap);
-        FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], array + pos, c * 2, hipMemcpyHostToDevice, e.stream[sl]));
-        FS_HIP_TRY(hipMemcpyAsync(d_sel, sel_src + first, bytes, hipMemcpyHostToDevice, e.stream[sl]));
-        FS_HIP_TRY(fsk_launch_where(e.stage[sl], c, d_sel, sel_bits == 1 ? (sel_offset + pos) & 7 : 0, sel_bits, row.d, row.d + 32, mode,
-                                    grid, e.stream[sl]));
-    }
-    if (slots == 2 && (rc = fsint::stream_wait_stream(e, s0, e.stream[1]))) return rc;
-    uint64_t got[33];
-    FS_HIP_TRY(hipMemcpyAsync(got, row.d, sizeof got, hipMemcpyDeviceToHost, s0));
-    FS_HIP_TRY(hipStreamSynchronize(s0));
-    if (slots == 2) FS_HIP_TRY(hipStreamSynchronize(e.stream[1]));
-    where_apply(out, selected, got, flags);
-    return 0;
+    return fsdrv::host_call(n, chunk, cap + (sel_cap + 1) / 2, kWhereAlloc, out, selected, flags, fsdrv::kWordAdd, fsdrv::fits_always,
+                            [&](Engine& e, fsdrv::Row& row, int sl, uint64_t pos, uint64_t c) {
+                                const uint32_t grid = fsint::grid_for(e);
+                                uint64_t first, bytes;
+                                where_extent(c, sel_offset + pos, sel_bits, &first, &bytes);
+                                uint8_t* d_sel = reinterpret_cast<uint8_t*>(e.stage[sl] + cap);
+                                FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], array + pos, c * 2, hipMemcpyHostToDevice, e.stream[sl]));
+                                FS_HIP_TRY(hipMemcpyAsync(d_sel, sel_src + first, bytes, hipMemcpyHostToDevice, e.stream[sl]));
+                                FS_HIP_TRY(fsk_launch_where(e.stage[sl], c, d_sel, sel_bits == 1 ? (sel_offset + pos) & 7 : 0, sel_bits, row.d, row.d + 32, mode,
+                                                            grid, e.stream[sl]));
+                                return 0;
+                            });
 }
 
 }  // extern "C"

@@ -6,8 +6,8 @@
 // (256 lanes x 8 vectors of 16 B: 8,192 elements at W = 4, 4,096 at W = 8); workgroup b takes the head edge step (b == 0), the
 // tail edge step, then the fully covered steps b, b + G, ...; each wave owns a contiguous 8 KiB of a step.  Edge steps go through
 // a guarded, zero-filling loader (a zero element counts nothing and sets no mask bit); fast steps through K1's rolling load
-// schedule (schedule 71: a vector's registers are re-issued for the vector six places on as soon as it has been read out),
-// restated below from flagstat_kernels.hip.  tests/steps_oracle.StepSplit(addr % 16, n * W / 2, grid) is the step split.
+// schedule (schedule 71: a vector's registers are re-issued for the vector six places on as soon as it has been read out:
+// reissue, flagstat_count_core.h).  tests/steps_oracle.StepSplit(addr % 16, n * W / 2, grid) is the step split.
 //
 // Narrowing.  front4 (flagstat_count_core.h) wants 4 flags as a dword L of their low bytes and a dword H of their high bytes.
 // One v_perm_b32 takes two flag-carrying dwords a, b to P = [a.b0, b.b0, a.b1, b.b1]; a second pair of perms takes two P to L
@@ -25,18 +25,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <cstdio>
-#include <mutex>
-
 #include "../../include/libflagstats_hip.h"
 #include "flagstat_count_core.h"
-#include "flagstat_engine.h"
+#include "flagstat_derived_host.h"
 #include "flagstat_wide.h"
 
 namespace fsk {
 
 constexpr int kWideDepth = 8;        // chain depth as K1: epochs of 255 steps
-constexpr int kWideStepBytes = kVecPerStep * 16;   // 32 KiB
 
 // Read a just-loaded vector out of its registers AT THIS POINT of the instruction stream (they are re-targeted by the load of
 // a later vector right after, as in K1's split_out): the flag-carrying dwords pairwise to P = [a.b0, b.b0, a.b1, b.b1], every
@@ -88,8 +84,6 @@ __device__ __forceinline__ void wide_step(Lane<kWideDepth>& s, uint4 (&v)[kUnrol
                                           const uint4* __restrict__ cur, const uint4* __restrict__ next)
 {
     constexpr int NIN = 32 / W;
-    constexpr int RD = 6;
-    constexpr int US = 64;   // each wave a contiguous 8 KiB of the step
     uint32_t T[NIN], F[NIN], S[NIN];
     uint32_t held = 0;       // W = 8: the even vector's P until the odd one's arrives
 #pragma unroll
@@ -97,12 +91,7 @@ __device__ __forceinline__ void wide_step(Lane<kWideDepth>& s, uint4 (&v)[kUnrol
         uint32_t p0, p1 = 0;
         __builtin_amdgcn_sched_barrier(0);
         narrow_out<W>(v[u], p0, p1, or_even, or_odd);
-        if constexpr (ROLL != 0) {
-            if (u + RD < kUnroll)
-                v[u + RD] = load_vec<true>(cur + (u + RD) * US);
-            else if constexpr (ROLL == 1)
-                v[u + RD - kUnroll] = load_vec<true>(next + (u + RD - kUnroll) * US);
-        }
+        reissue<ROLL>(u, v, cur, next, kWaveStride, load_vec<true>);
         __builtin_amdgcn_sched_barrier(0);
         if (W == 8 && (u & 1) == 0) {
             held = p0;
@@ -129,11 +118,7 @@ __device__ __forceinline__ void wide_step_and_count(Lane<kWideDepth>& s, uint4 (
 {
     blk = __builtin_amdgcn_readfirstlane(blk);
     wide_step<W, ROLL>(s, v, blk, or_even, or_odd, cur, next);
-    ++blk;
-    if (blk == (1u << kWideDepth) - 1u) {
-        flush(s, (1u << kWideDepth) - 1u);
-        blk = 0;
-    }
+    end_step<kWideDepth>(s, blk);
 }
 
 // Vector j of the 16-byte grid holds element positions [j * 16 / W, (j + 1) * 16 / W); positions in [lo, hi) are the caller's
@@ -184,11 +169,10 @@ __global__ __launch_bounds__(kThreads) void flagstat_count_wide(const uint4* __r
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = threadIdx.x >> 6;
     constexpr int VPS = kVecPerStep;
-    constexpr int US = 64;
-    const uint64_t lane_off = static_cast<uint64_t>(wave) * (64 * kUnroll) + lane;
+    constexpr int US = kWaveStride;
+    const uint64_t lane_off = static_cast<uint64_t>(wave) * (US * kUnroll) + lane;
     const uint64_t G = gridDim.x;
-    // wave w starts its first epoch at 64 * w, so at most one wave of a CU is flushing at any time (K1's mode bit 4)
-    uint32_t blk = (wave & 3u) * 64u;
+    uint32_t blk = stagger_start(wave);
     uint32_t or_even = 0, or_odd = 0;
 
     auto edge_step = [&](uint64_t st) {
@@ -205,7 +189,7 @@ __global__ __launch_bounds__(kThreads) void flagstat_count_wide(const uint4* __r
     uint64_t st = blockIdx.x;
     if (st < fast_begin) st += G;  // fast_begin is 0 or 1
     if (st < fast_end) {
-        constexpr int RD = 6;
+        constexpr int RD = kRollDistance;
         uint4 v[kUnroll];
         const uint4* p = a0 + st * VPS + lane_off;
 #pragma unroll
@@ -263,38 +247,11 @@ __global__ __launch_bounds__(kThreads) void flagstat_count_wide(const uint4* __r
 }  // namespace fsk
 
 // ------------------------------------------------------------------ launcher
-// Host-side geometry: everything the kernel assumes is derived here from (address, n, W).
+// Host-side geometry: the shared step split (flagstat_derived_host.h) at W = 4 or 8.
 extern "C" hipError_t fsk_wide_geometry(uint64_t address, uint64_t n, int elem_bytes, uint32_t grid, uint64_t* geo)
 {
-    if ((elem_bytes != 4 && elem_bytes != 8) || grid == 0 || geo == nullptr) return hipErrorInvalidValue;
-    const uint64_t W = static_cast<uint64_t>(elem_bytes);
-    const uint64_t addr = address;
-    if (addr & (W - 1)) return hipErrorInvalidValue;
-    for (int i = 0; i < 6; ++i) geo[i] = 0;
-    if (n == 0) return hipSuccess;
-    if (n > (~0ull - 64) / W) return hipErrorInvalidValue;  // n * W must be a size
-    const uint64_t base = addr & ~static_cast<uint64_t>(15);
-    const uint64_t epv = 16 / W;                            // elements per 16-byte vector
-    const uint64_t lo = (addr - base) / W, hi = lo + n;
-    const uint64_t nvec = (hi + epv - 1) / epv;
-    const uint64_t vps = fsk::kVecPerStep;
-    const uint64_t nsteps = (nvec + vps - 1) / vps;
-    // steps whose vectors are all fully inside [lo, hi)
-    uint64_t fast_begin = (lo == 0) ? 0 : 1;
-    uint64_t fast_end = (hi / epv) / vps;
-    if (fast_end < fast_begin) fast_end = fast_begin;
-    if (static_cast<uint64_t>(grid) > nsteps) grid = static_cast<uint32_t>(nsteps);
-    // a wave's totals are uint32: a workgroup pushes at most ceil(nsteps / grid) + 2 steps (its share and both edge steps), each
-    // wave a quarter of every step
-    const uint64_t wave_elems_per_step = fsk::kWideStepBytes / W / (fsk::kThreads / 64);
-    if (nsteps / grid + 3 >= (1ull << 32) / wave_elems_per_step) return hipErrorInvalidValue;
-    geo[0] = lo;
-    geo[1] = hi;
-    geo[2] = nsteps;
-    geo[3] = fast_begin;
-    geo[4] = fast_end;
-    geo[5] = grid;
-    return hipSuccess;
+    if (elem_bytes != 4 && elem_bytes != 8) return hipErrorInvalidValue;
+    return fsdrv::step_split(address, n, elem_bytes, grid, geo);
 }
 
 extern "C" hipError_t fsk_launch_wide(const void* d_array, uint64_t n, int elem_bytes, uint64_t* d_out32, uint64_t* d_high, int mode,
@@ -305,13 +262,7 @@ extern "C" hipError_t fsk_launch_wide(const void* d_array, uint64_t n, int elem_
     uint64_t geo[6];
     hipError_t e = fsk_wide_geometry(reinterpret_cast<uintptr_t>(d_array), n, elem_bytes, grid, geo);
     if (e != hipSuccess) return e;
-    if (mode & 1) {
-        // counters and mask word in one memset where they are one allocation's 33 words
-        const bool together = d_high == d_out32 + 32;
-        e = hipMemsetAsync(d_out32, 0, (together ? 33 : 32) * sizeof(uint64_t), stream);
-        if (e == hipSuccess && d_high && !together) e = hipMemsetAsync(d_high, 0, sizeof(uint64_t), stream);
-        if (e != hipSuccess) return e;
-    }
+    if ((mode & 1) && (e = fsdrv::zero_counters(d_out32, d_high, stream)) != hipSuccess) return e;
     if (n == 0) return hipSuccess;
     const uint4* a0 = reinterpret_cast<const uint4*>(reinterpret_cast<uintptr_t>(d_array) & ~static_cast<uintptr_t>(15));
     const dim3 g(static_cast<uint32_t>(geo[5])), b(fsk::kThreads);
@@ -323,9 +274,8 @@ extern "C" hipError_t fsk_launch_wide(const void* d_array, uint64_t n, int elem_
 }
 
 // ------------------------------------------------------------------ C entry points (include/libflagstats_hip.h)
-using fsint::DeviceGuard;
+// The three forms are the shared bodies of flagstat_derived_host.h; the 33rd word is the mask, ORed in the accumulate form.
 using fsint::Engine;
-using fsint::fail_hip;
 using fsint::fail_text;
 
 namespace {
@@ -344,34 +294,7 @@ int wide_args(const void* array, uint64_t n, int elem_bytes, const void* out, in
     return 0;
 }
 
-// device counters[32] + mask word of one synchronous call
-struct WideRow {
-    uint64_t* d = nullptr;
-    ~WideRow()
-    {
-        if (d) (void)hipFree(d);
-    }
-    int alloc()
-    {
-        const hipError_t e = hipMalloc(&d, 33 * sizeof(uint64_t));
-        if (e != hipSuccess) {
-            d = nullptr;
-            return fail_hip("hipMalloc(wide counters)", e);
-        }
-        return 0;
-    }
-};
-
-void wide_apply(uint64_t* out, uint64_t* high, const uint64_t (&got)[33], int flags)
-{
-    if (flags & 1) {
-        for (int i = 0; i < 32; ++i) out[i] = got[i];
-        if (high) *high = got[32];
-    } else {
-        for (int i = 0; i < 32; ++i) out[i] += got[i];
-        if (high) *high |= got[32];
-    }
-}
+constexpr const char* kWideAlloc = "hipMalloc(wide counters)";
 
 }  // namespace
 
@@ -383,32 +306,14 @@ int FLAGSTATS_hip_device_wide(const void* d_array, uint64_t n, int elem_bytes, u
     int rc = wide_args(d_array, n, elem_bytes, d_out, flags);
     if (rc) return rc;
     if (n == 0 && !(flags & 1)) return 0;
-    int dev_out = -1, dev = -1;
-    bool plain = false;
-    rc = fsint::device_of_pointer(d_out, "d_out", &dev_out, &plain);
-    if (rc) return rc;
-    if (!plain) return fail_text("d_out must be device memory (the counters are added with device atomics)");
-    if (d_high) {
-        rc = fsint::device_of_pointer(d_high, "d_high", &dev, &plain);
-        if (rc) return rc;
-        if (!plain) return fail_text("d_high must be device memory (the mask is ORed with a device atomic)");
-        if (dev != dev_out) return fail_text("d_high and d_out live on different devices");
-    }
-    if (n) {
-        rc = fsint::device_of_pointer(d_array, "d_array", &dev);
-        if (rc) return rc;
-        if (dev != dev_out) return fail_text("d_array and d_out live on different devices");
-    }
-    Engine* e = fsint::engine_for_device(dev_out);
-    if (!e) return -1;
-    DeviceGuard guard(e->device);
-    if (!guard.ok()) return -1;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = fsint::check_stream_device(s, e->device);
-    if (rc) return rc;
-    if ((rc = fsint::check_extent(d_out, 32 * sizeof(uint64_t), "d_out"))) return rc;
-    if (d_high && (rc = fsint::check_extent(d_high, sizeof(uint64_t), "d_high"))) return rc;
-    if (n && (rc = fsint::check_extent(d_array, n * static_cast<uint64_t>(elem_bytes), "d_array"))) return rc;
+    const fsdrv::DeviceWord word{d_high, "d_high", "the mask is ORed with a device atomic"};
+    const fsdrv::Input in[] = {{d_array, "d_array", n * static_cast<uint64_t>(elem_bytes)}};
+    const int inputs = n ? 1 : 0;
+    fsdrv::DeviceCall call;
+    if ((rc = call.open(d_out, word, in, inputs, stream))) return rc;
+    if ((rc = fsdrv::check_extents(d_out, word, in, inputs))) return rc;
+    Engine* e = call.e;
+    hipStream_t s = call.s;
     FS_HIP_TRY(fsk_launch_wide(d_array, n, elem_bytes, d_out, d_high, flags & 3, fsint::grid_for(*e), s));
     return 0;
 }
@@ -419,32 +324,14 @@ int FLAGSTATS_hip_device_wide_sync(const void* d_array, uint64_t n, int elem_byt
     int rc = wide_args(d_array, n, elem_bytes, out, flags);
     if (rc) return rc;
     if (n == 0) {
-        if (flags & 1) {
-            for (int i = 0; i < 32; ++i) out[i] = 0;
-            if (high) *high = 0;
-        }
+        fsdrv::store_nothing(out, high, flags);
         return 0;
     }
-    int dev = -1;
-    rc = fsint::device_of_pointer(d_array, "d_array", &dev);
-    if (rc) return rc;
-    Engine* ep = fsint::engine_for_device(dev);
-    if (!ep) return -1;
-    Engine& e = *ep;
-    std::lock_guard<std::mutex> lk(e.mu);
-    if (fsint::engine_alive(e)) return -1;
-    DeviceGuard guard(e.device);
-    if (!guard.ok()) return -1;
-    if ((rc = fsint::check_extent(d_array, n * static_cast<uint64_t>(elem_bytes), "d_array"))) return rc;
-    WideRow row;
-    if ((rc = row.alloc())) return rc;
-    uint64_t got[33];
-    hipStream_t s = e.stream[0];
-    FS_HIP_TRY(fsk_launch_wide(d_array, n, elem_bytes, row.d, row.d + 32, 1 | (flags & 2), fsint::grid_for(e), s));
-    FS_HIP_TRY(hipMemcpyAsync(got, row.d, sizeof got, hipMemcpyDeviceToHost, s));
-    FS_HIP_TRY(hipStreamSynchronize(s));
-    wide_apply(out, high, got, flags);
-    return 0;
+    const fsdrv::Input in[] = {{d_array, "d_array", n * static_cast<uint64_t>(elem_bytes)}};
+    return fsdrv::sync_call(in, 1, kWideAlloc, out, high, flags, fsdrv::kWordOr, fsdrv::fits_always, [&](Engine& e, fsdrv::Row& row, hipStream_t s) {
+        FS_HIP_TRY(fsk_launch_wide(d_array, n, elem_bytes, row.d, row.d + 32, 1 | (flags & 2), fsint::grid_for(e), s));
+        return 0;
+    });
 }
 
 int FLAGSTATS_hip_wide_x64(const void* array, uint64_t n, int elem_bytes, uint64_t* out, uint64_t* high, int flags)
@@ -453,52 +340,23 @@ int FLAGSTATS_hip_wide_x64(const void* array, uint64_t n, int elem_bytes, uint64
     int rc = wide_args(array, n, elem_bytes, out, flags);
     if (rc) return rc;
     if (n == 0) {
-        if (flags & 1) {
-            for (int i = 0; i < 32; ++i) out[i] = 0;
-            if (high) *high = 0;
-        }
+        fsdrv::store_nothing(out, high, flags);
         return 0;
     }
-    Engine* ep = fsint::default_engine();
-    if (!ep) return -1;
-    Engine& e = *ep;
-    std::lock_guard<std::mutex> lk(e.mu);
-    if (fsint::engine_alive(e)) return -1;
-    DeviceGuard guard(e.device);
-    if (!guard.ok()) return -1;
-    fsint::lz4_gpu_other_use(e);
-    WideRow row;
-    if ((rc = row.alloc())) return rc;
-    if ((rc = fsint::engine_second(e))) return rc;
-    // the array crosses the bus as it is, in chunks of "chunk_flags" * 2 bytes, alternating between the engine's two streams
-    // and staging buffers (the copy of chunk k + 1 overlaps the kernel on chunk k); every chunk's launch adds into the same
-    // device counters and ORs into the same mask word
+    // the array crosses the bus as it is, in chunks of "chunk_flags" * 2 bytes; every chunk's launch adds into the same device
+    // counters and ORs into the same mask word
     const uint64_t W = static_cast<uint64_t>(elem_bytes);
-    const uint64_t chunk_flags = fsint::knobs().chunk_flags.load() < 8 ? 8 : fsint::knobs().chunk_flags.load();
+    const uint64_t chunk_flags = fsdrv::chunk_flags();
     const uint64_t chunk = chunk_flags * 2 / W;   // elements per chunk
-    const int slots = n > chunk ? 2 : 1;
-    for (int i = 0; i < slots; ++i)
-        if ((rc = fsint::stage_reserve(e, i, n < chunk ? (n * W + 1) / 2 : chunk_flags))) return rc;
-    hipStream_t s0 = e.stream[0];
-    FS_HIP_TRY(hipMemsetAsync(row.d, 0, 33 * sizeof(uint64_t), s0));
-    if (slots == 2 && (rc = fsint::stream_wait_stream(e, e.stream[1], s0))) return rc;
-    const uint32_t grid = fsint::grid_for(e);
     const int mode = flags & 2;
     const uint8_t* src = static_cast<const uint8_t*>(array);
-    uint64_t k = 0;
-    for (uint64_t pos = 0; pos < n; pos += chunk, ++k) {
-        const int sl = static_cast<int>(k % static_cast<uint64_t>(slots));
-        const uint64_t c = n - pos < chunk ? n - pos : chunk;
-        FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], src + pos * W, c * W, hipMemcpyHostToDevice, e.stream[sl]));
-        FS_HIP_TRY(fsk_launch_wide(e.stage[sl], c, elem_bytes, row.d, row.d + 32, mode, grid, e.stream[sl]));
-    }
-    if (slots == 2 && (rc = fsint::stream_wait_stream(e, s0, e.stream[1]))) return rc;
-    uint64_t got[33];
-    FS_HIP_TRY(hipMemcpyAsync(got, row.d, sizeof got, hipMemcpyDeviceToHost, s0));
-    FS_HIP_TRY(hipStreamSynchronize(s0));
-    if (slots == 2) FS_HIP_TRY(hipStreamSynchronize(e.stream[1]));
-    wide_apply(out, high, got, flags);
-    return 0;
+    return fsdrv::host_call(n, chunk, n < chunk ? (n * W + 1) / 2 : chunk_flags, kWideAlloc, out, high, flags, fsdrv::kWordOr, fsdrv::fits_always,
+                            [&](Engine& e, fsdrv::Row& row, int sl, uint64_t pos, uint64_t c) {
+                                const uint32_t grid = fsint::grid_for(e);
+                                FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], src + pos * W, c * W, hipMemcpyHostToDevice, e.stream[sl]));
+                                FS_HIP_TRY(fsk_launch_wide(e.stage[sl], c, elem_bytes, row.d, row.d + 32, mode, grid, e.stream[sl]));
+                                return 0;
+                            });
 }
 
 }  // extern "C"

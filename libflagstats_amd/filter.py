@@ -12,7 +12,7 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _checks, _lib
 from .pyflagstats import _as_dict
 
 STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
@@ -20,12 +20,10 @@ STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
 
 def _check_predicate(require, exclude, min_mapq, has_mapq: bool):
     for name, x in (("require", require), ("exclude", exclude)):
-        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
-            raise ValueError("%s must be an int, not %s" % (name, type(x).__name__))
+        _checks.check_int(name, x)
         if not 0 <= x <= 0xFFFF:
             raise ValueError("%s must be a 16-bit FLAG mask (0..65535), not %d" % (name, x))
-    if isinstance(min_mapq, bool) or not isinstance(min_mapq, (int, np.integer)):
-        raise ValueError("min_mapq must be an int, not %s" % type(min_mapq).__name__)
+    _checks.check_int("min_mapq", min_mapq)
     if not 0 <= min_mapq <= 255:
         raise ValueError("min_mapq must be in 0..255 (MAPQ is one byte), not %d" % min_mapq)
     if min_mapq > 0 and not has_mapq:
@@ -79,14 +77,7 @@ def count_device_ptr_filter(ptr: int, n: int, require: int = 0, exclude: int = 0
                             superset: bool = False):
     """``(uint64[32], int selected)`` of a device array of ``n`` ``uint16`` flags under the filter, array and MAPQ column
     (``n`` bytes; ``mapq_ptr`` 0: none) given as raw pointers.  Synchronous (``FLAGSTATS_hip_device_u16_filter_sync``)."""
-    for name, x in (("ptr", ptr), ("n", n), ("mapq_ptr", mapq_ptr)):
-        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
-            raise ValueError("%s must be an int, not %s" % (name, type(x).__name__))
-    if n < 0:
-        raise ValueError("n must not be negative")
-    for name, x in (("ptr", ptr), ("n", n), ("mapq_ptr", mapq_ptr)):
-        if not 0 <= x < 1 << 64:
-            raise ValueError("%s must fit an unsigned 64-bit integer, not %d" % (name, x))
+    _checks.check_raw_ints((("ptr", ptr), ("n", n), ("mapq_ptr", mapq_ptr)))
     require, exclude, min_mapq = _check_predicate(require, exclude, min_mapq, mapq_ptr != 0)
     ptr, n, mapq_ptr = int(ptr), int(n), int(mapq_ptr)
     out = np.zeros(32, dtype=np.uint64)
@@ -123,19 +114,8 @@ def count_torch_filter(t, require: int = 0, exclude: int = 0, mapq=None, min_map
         if mapq.numel() != t.numel():
             raise ValueError("mapq must have one element per value (%d), not %d" % (t.numel(), mapq.numel()))
     require, exclude, min_mapq = _check_predicate(require, exclude, min_mapq, mapq is not None)
-    given = (("out", out, 32), ("selected", selected, 1))
-    for name, x, numel in given:
-        if x is not None and not (isinstance(x, torch.Tensor) and x.dtype == torch.int64 and x.numel() == numel and x.is_contiguous()):
-            raise ValueError("%s must be a contiguous int64 tensor of %d element%s" % (name, numel, "s" if numel > 1 else ""))
-    if not t.is_cuda:
-        raise ValueError("t must be a CUDA tensor")
-    for name, x in (("mapq", mapq), ("out", out), ("selected", selected)):
-        if x is not None and x.device != t.device:
-            raise ValueError("%s must live on t's device (%s), not on %s" % (name, t.device, x.device))
-    if out is None:
-        out = torch.zeros(32, dtype=torch.int64, device=t.device)
-    if selected is None:
-        selected = torch.zeros(1, dtype=torch.int64, device=t.device)
+    _checks.check_result_pair(out, "selected", selected)
+    out, selected = _checks.place_result_pair(t, out, "selected", selected, others=(("mapq", mapq),))
     lib = _lib.lib()
     with torch.cuda.device(t.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)

@@ -12,15 +12,14 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _checks, _lib
 from .pyflagstats import _as_dict
 
 STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
 
 
 def _check_bit_offset(packed, bit_offset) -> int:
-    if isinstance(bit_offset, bool) or not isinstance(bit_offset, (int, np.integer)):
-        raise ValueError("bit_offset must be an int, not %s" % type(bit_offset).__name__)
+    _checks.check_int("bit_offset", bit_offset)
     if not 0 <= bit_offset < 1 << 63:
         raise ValueError("bit_offset must not be negative (and below 2**63), not %d" % bit_offset)
     if bit_offset and not packed:
@@ -85,16 +84,7 @@ def count_device_ptr_where(ptr: int, n: int, sel_ptr: int, sel_bits: int, sel_of
     Synchronous (``FLAGSTATS_hip_device_u16_where_sync``)."""
     if sel_bits not in (1, 8) or isinstance(sel_bits, bool):
         raise ValueError("sel_bits must be 1 (an LSB-first bitmap) or 8 (one byte per element), not %r" % (sel_bits,))
-    for name, x in (("ptr", ptr), ("n", n), ("sel_ptr", sel_ptr), ("sel_offset", sel_offset)):
-        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
-            raise ValueError("%s must be an int, not %s" % (name, type(x).__name__))
-    if n < 0:
-        raise ValueError("n must not be negative")
-    if sel_offset < 0:
-        raise ValueError("sel_offset must not be negative")
-    for name, x in (("ptr", ptr), ("n", n), ("sel_ptr", sel_ptr), ("sel_offset", sel_offset)):
-        if not 0 <= x < 1 << 64:
-            raise ValueError("%s must fit an unsigned 64-bit integer, not %d" % (name, x))
+    _checks.check_raw_ints((("ptr", ptr), ("n", n), ("sel_ptr", sel_ptr), ("sel_offset", sel_offset)), non_negative=("n", "sel_offset"))
     ptr, n, sel_ptr, sel_offset = int(ptr), int(n), int(sel_ptr), int(sel_offset)
     out = np.zeros(32, dtype=np.uint64)
     selected = ctypes.c_uint64(0)
@@ -136,19 +126,8 @@ def count_torch_where(t, where, out=None, selected=None, store: bool = False, su
             raise ValueError("where must have dtype torch.bool (packed=True: a torch.uint8 bitmap), not %s" % where.dtype)
         if where.numel() != t.numel():
             raise ValueError("where must have one element per value (%d), not %d" % (t.numel(), where.numel()))
-    given = (("out", out, 32), ("selected", selected, 1))
-    for name, x, numel in given:
-        if x is not None and not (isinstance(x, torch.Tensor) and x.dtype == torch.int64 and x.numel() == numel and x.is_contiguous()):
-            raise ValueError("%s must be a contiguous int64 tensor of %d element%s" % (name, numel, "s" if numel > 1 else ""))
-    if not t.is_cuda:
-        raise ValueError("t must be a CUDA tensor")
-    for name, x in (("where", where), ("out", out), ("selected", selected)):
-        if x is not None and x.device != t.device:
-            raise ValueError("%s must live on t's device (%s), not on %s" % (name, t.device, x.device))
-    if out is None:
-        out = torch.zeros(32, dtype=torch.int64, device=t.device)
-    if selected is None:
-        selected = torch.zeros(1, dtype=torch.int64, device=t.device)
+    _checks.check_result_pair(out, "selected", selected)
+    out, selected = _checks.place_result_pair(t, out, "selected", selected, others=(("where", where),))
     lib = _lib.lib()
     with torch.cuda.device(t.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)

@@ -13,7 +13,7 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _checks, _lib
 from .pyflagstats import _as_dict
 
 STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
@@ -95,19 +95,8 @@ def count_torch_ints(t, out=None, high=None, store: bool = False, superset: bool
         raise ValueError("t must have an integer dtype of 2, 4 or 8 bytes, not %s" % t.dtype)
     if t.dim() != 1 or not t.is_contiguous():
         raise ValueError("t must be 1-D and contiguous")
-    given = (("out", out, 32), ("high", high, 1))
-    for name, x, numel in given:
-        if x is not None and not (isinstance(x, torch.Tensor) and x.dtype == torch.int64 and x.numel() == numel and x.is_contiguous()):
-            raise ValueError("%s must be a contiguous int64 tensor of %d element%s" % (name, numel, "s" if numel > 1 else ""))
-    if not t.is_cuda:
-        raise ValueError("t must be a CUDA tensor")
-    for name, x, _ in given:
-        if x is not None and x.device != t.device:
-            raise ValueError("%s must live on t's device (%s), not on %s" % (name, t.device, x.device))
-    if out is None:
-        out = torch.zeros(32, dtype=torch.int64, device=t.device)
-    if high is None:
-        high = torch.zeros(1, dtype=torch.int64, device=t.device)
+    _checks.check_result_pair(out, "high", high)
+    out, high = _checks.place_result_pair(t, out, "high", high)
     lib = _lib.lib()
     with torch.cuda.device(t.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)

@@ -166,6 +166,7 @@ def test_writer_mirror_matches_the_sources():
     hdr = _source("libflagstats_amd", "csrc", "flagstat_segments.h")
     src = re.sub(r"\s+", " ", _source("libflagstats_amd", "csrc", "flagstat_segments.hip"))
     k1 = _source("libflagstats_amd", "csrc", "flagstat_kernels.h")
+    core = re.sub(r"\s+", " ", _source("libflagstats_amd", "csrc", "flagstat_count_core.h"))
     assert int(re.search(r"constexpr int kSegWaveFlags = (\d+);", hdr).group(1)) == so.SEG_UNIT
     assert int(re.search(r"constexpr int kThreads = (\d+);", k1).group(1)) == 64 * so.SEG_WAVES_PER_BLOCK
     assert (1 << int(re.search(r"constexpr int kSegDepth = (\d+);", src).group(1))) - 1 == so.SEG_EPOCH
@@ -179,9 +180,10 @@ def test_writer_mirror_matches_the_sources():
                  "const uint64_t p0 = u_begin * kSegWaveFlags > lo0 ? u_begin * kSegWaveFlags : lo0;",
                  "const uint64_t E = u_end * kSegWaveFlags < hi0 ? u_end * kSegWaveFlags : hi0;",
                  "if (k >= min_units && k > 0) {",
-                 "if (blk == (1u << kSegDepth) - 1u) {",
                  "(mode & 1) && b_ >= p0 && e_ <= E"):
         assert rule in src, rule
+    # the epoch test lives once in the shared end_step, which the chain step calls at the segmented kernel's depth
+    assert core.count("if (blk == (1u << DEPTH) - 1u) {") == 1 and "end_step<kSegDepth>(s, blk);" in src
 
 
 def test_writer_mirror_partitions_the_array():

@@ -69,6 +69,7 @@ def test_step_mirror_matches_the_sources():
     """The mirror restates the launchers' and the kernels' arithmetic: if either changes, this test names what to update."""
     k1h = _source("libflagstats_amd", "csrc", "flagstat_kernels.h")
     k1 = _source("libflagstats_amd", "csrc", "flagstat_kernels.hip")
+    core = _source("libflagstats_amd", "csrc", "flagstat_count_core.h")
     pos = _source("libflagstats_amd", "csrc", "flagstat_pospopcnt.hip")
     threads = int(re.search(r"constexpr int kThreads = (\d+);", k1h).group(1))
     unroll = int(re.search(r"constexpr int kUnroll = (\d+);", k1h).group(1))
@@ -81,8 +82,12 @@ def test_step_mirror_matches_the_sources():
                  "case 25: e = launch_count_t<8, true, false, true, 1>(a, stream);",
                  "case 71: e = launch_count_t<8, true, false, false, 9>(a, stream);"):
         assert case in k1, case
-    assert "if (blk == (1u << DEPTH) - 1u) { flush(s, (1u << DEPTH) - 1u); blk = 0; }" in k1
-    assert "uint32_t blk = (mode & 16) ? (wave & 3u) * %du : 0u;" % STAGGER in k1
+    # (the flush test and the stagger start live once in flagstat_count_core.h: end_step, stagger_start; K1 calls them)
+    assert core.count("if (blk == (1u << DEPTH) - 1u) { flush(s, (1u << DEPTH) - 1u); blk = 0; }") == 1
+    assert "blk = __builtin_amdgcn_readfirstlane(blk); step<DEPTH, STAGE, NT, USTRIDE, HAS_NEXT>(s, v, blk, next, cur); end_step(s, blk);" in k1
+    assert "tree_step<DEPTH>(s, blk, [&]" in k1 and core.count("uint32_t t8a = 0") == 1 and "t8a" not in k1
+    assert core.count("return (wave & 3u) * %du;" % STAGGER) == 1
+    assert "uint32_t blk = (mode & 16) ? stagger_start(wave) : 0u;" in k1
     assert "if (g_epoch_stagger.load()) a.mode |= 16;" in k1
     # the launchers' geometry (K1 keeps it in CountArgs a.*)
     for src, p in ((pos, ""), (k1, "a.")):

@@ -161,13 +161,16 @@ def test_wide_step_mirror_matches_the_sources():
     out of flagstat_wide.hip"""
     k1h = _source("libflagstats_amd", "csrc", "flagstat_kernels.h")
     w = _source("libflagstats_amd", "csrc", "flagstat_wide.hip")
+    core = _source("libflagstats_amd", "csrc", "flagstat_count_core.h")      # the shared device pieces
+    host = _source("libflagstats_amd", "csrc", "flagstat_derived_host.h")    # the shared step split
     threads = int(re.search(r"constexpr int kThreads = (\d+);", k1h).group(1))
     unroll = int(re.search(r"constexpr int kUnroll = (\d+);", k1h).group(1))
     assert threads == 64 * WAVES and threads * unroll * 16 == 2 * STEP_WORDS == 32768     # 32 KiB steps
-    assert "constexpr int kWideStepBytes = kVecPerStep * 16;" in w and "constexpr int VPS = kVecPerStep;" in w
+    assert host.count("constexpr int kStepBytes = fsk::kVecPerStep * 16;") == 1 and "constexpr int VPS = kVecPerStep;" in w
     assert (1 << int(re.search(r"constexpr int kWideDepth = (\d+);", w).group(1))) - 1 == EPOCH
-    assert "if (blk == (1u << kWideDepth) - 1u) { flush(s, (1u << kWideDepth) - 1u); blk = 0; }" in w
-    assert "uint32_t blk = (wave & 3u) * %du;" % STAGGER in w
+    assert core.count("if (blk == (1u << DEPTH) - 1u) { flush(s, (1u << DEPTH) - 1u); blk = 0; }") == 1
+    assert "wide_step<W, ROLL>(s, v, blk, or_even, or_odd, cur, next); end_step<kWideDepth>(s, blk);" in w
+    assert core.count("return (wave & 3u) * %du;" % STAGGER) == 1 and "uint32_t blk = stagger_start(wave);" in w
     for rule in ("const uint64_t base = addr & ~static_cast<uint64_t>(15);",
                  "const uint64_t epv = 16 / W;",
                  "const uint64_t lo = (addr - base) / W, hi = lo + n;",
@@ -178,14 +181,17 @@ def test_wide_step_mirror_matches_the_sources():
                  "uint64_t fast_end = (hi / epv) / vps;",
                  "if (fast_end < fast_begin) fast_end = fast_begin;",
                  "if (static_cast<uint64_t>(grid) > nsteps) grid = static_cast<uint32_t>(nsteps);"):
-        assert rule in w, rule
+        assert host.count(rule) == 1, rule
+    assert "return fsdrv::step_split(address, n, elem_bytes, grid, geo);" in w
     # the kernel's push order: head edge, tail edge, fast steps from b (+G below fast_begin)
     assert "if (fast_begin != 0 && blockIdx.x == 0) edge_step(0);" in w
     assert "if (nsteps > fast_end && nsteps - 1 >= fast_begin && (nsteps - 1) % G == blockIdx.x) edge_step(nsteps - 1);" in w
     assert "uint64_t st = blockIdx.x; if (st < fast_begin) st += G;" in w
     assert w.index("edge_step(0);") < w.index("edge_step(nsteps - 1);") < w.index("if (st < fast_end) {")
     # rolling re-issue at a distance of 6 vectors, each wave a contiguous 8 KiB
-    assert w.count("constexpr int RD = 6;") == 2 and "constexpr int US = 64;" in w
+    assert core.count("constexpr int kRollDistance = 6;") == 1 and core.count("constexpr int kWaveStride = 64;") == 1
+    assert "reissue<ROLL>(u, v, cur, next, kWaveStride, load_vec<true>);" in w and "constexpr int US = kWaveStride;" in w
+    assert "constexpr int RD = kRollDistance;" in w and "for (int u = 0; u < RD; ++u) {" in w
 
 
 def test_wide_geometry_equals_the_step_split():

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Compare two `make -C libflagstats_amd/csrc asm` outputs (flagstat_kernels.s) kernel by kernel: for every kernel present in
-both, the instruction stream between its label and its .Lfunc_end must be the same text, and so must its resource block
-(VGPRs, SGPRs, LDS, scratch).  Proof that a refactoring of the source moved no instruction.
+"""Compare two `make -C libflagstats_amd/csrc asm [UNIT=<file stem>]` outputs (<unit>.s) kernel by kernel: for every kernel
+present in both, the instruction stream between its label and its .Lfunc_end must be the same text, and so must its resource
+block (VGPRs, SGPRs, LDS, scratch).  Proof that a refactoring of the source moved no instruction.  A body that differs under an
+identical descriptor and an equal sequence of mnemonics (same instructions, other register numbers) is reported as RENAMED;
+the exit status is non-zero for it as for any other difference.
 
     python3 tools/kernel_isa_diff.py before.s after.s
 """
@@ -54,9 +56,11 @@ def main():
             continue
         same = a[name] == b[name]
         same_meta = am.get(name) == bm.get(name)
+        renamed = not same and same_meta and [x.split()[0] for x in a[name]] == [y.split()[0] for y in b[name]]
         h = hashlib.sha256("\n".join(b[name]).encode()).hexdigest()[:16]
         print("%-50s %6d instructions / labels, body %s, kernel descriptor %s, sha256(body) %s" % (
-            demangle_hint(name), len(b[name]), "IDENTICAL" if same else "DIFFERS", "identical" if same_meta else "DIFFERS", h))
+            demangle_hint(name), len(b[name]), "IDENTICAL" if same else "RENAMED" if renamed else "DIFFERS",
+            "identical" if same_meta else "DIFFERS", h))
         if not same:
             rc = 1
             for i, (x, y) in enumerate(zip(a[name], b[name])):
