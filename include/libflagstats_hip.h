@@ -195,6 +195,42 @@ int FLAGSTATS_hip_device_u16_filter_sync(const uint16_t* d_array, uint64_t n, ui
 int FLAGSTATS_hip_u16_x64_filter(const uint16_t* array, uint64_t n, uint32_t require, uint32_t exclude, const uint8_t* mapq,
                                  uint32_t min_mapq, uint64_t* out, uint64_t* selected, int flags);
 
+/* ================= filtered segments: samtools' view filter -f / -F / -q per segment =================
+ * Per-contig, per-sample or per-block tables of the reads that pass `-F 0x904 -q 30`: the segmented entries under the filtered
+ * entries' predicate, in one launch.  Segment i is [offsets[i], offsets[i+1]) under the contract of the segmented entries;
+ * pass(j) is that of the filtered entries (an overlapping pair is legal, selects nothing and launches nothing; min_mapq == 0
+ * reads no byte of `mapq`, which may then be NULL).  Row i of out[nseg][32] holds FLAGSTAT_scalar's counters over
+ * {array[j] : j in segment i, pass(j)}, and selected[i] (nseg uint64; the pointer may be NULL: nothing is reported) the number
+ * of such j.  Flags outside every segment count nowhere.
+ * `flags`: bit 0 = store (rows and selected[0 .. nseg) are zeroed in front, every slot of every row is written, empty segments
+ * read 0) instead of +=; bit 1 = superset (slots 0 / 16 = primary paired reads among those that pass, slot 9 = selected[i]
+ * minus slot 25).  nseg == 0 succeeds and touches nothing.
+ * Refused (non-zero, message in FLAGSTATS_hip_last_error, out and selected untouched, nothing launched): require or exclude above
+ * 0xFFFF, min_mapq above 255, a NULL mapq with min_mapq > 0 and n > 0, a NULL array with n > 0, an odd array pointer, flag bits
+ * other than 0 and 1, NULL offsets or rows with nseg > 0, host offsets that decrease or end beyond n, an nseg whose rows cannot be
+ * allocated, an n with n * 2 not a size or too large for a wave's uint32 totals; for the device form also a d_out or d_selected
+ * that is not plain device memory, pointers on different devices, a stream of another device and an allocation shorter than the
+ * call needs (d_array: n * 2 bytes, d_mapq: n bytes when min_mapq > 0, d_offsets: (nseg + 1) * 8, d_out: nseg * 256,
+ * d_selected: nseg * 8).  Device offsets are not checked (that would synchronise): every offset the kernel reads is clamped to
+ * [0, n], so bad offsets give undefined counters and never an access outside the array, the column (read only at bytes of
+ * elements in [0, n)), the rows or the counts. */
+/* DEVICE array, column and offsets, DEVICE d_out[nseg][32] and d_selected[nseg] (uint64); asynchronous on `stream`: ONE kernel
+ * (the store form puts one memset per pointer in front of it), no workspace.  Adds are atomic: launches on several streams may
+ * share d_out and d_selected in the += form. */
+int FLAGSTATS_hip_device_u16_segments_filter(const uint16_t* d_array, uint64_t n, const uint64_t* d_offsets, uint64_t nseg,
+                                             uint32_t require, uint32_t exclude, const uint8_t* d_mapq, uint32_t min_mapq,
+                                             uint64_t* d_out, uint64_t* d_selected, int flags, void* stream);
+/* DEVICE array and column, HOST offsets, HOST out[nseg][32] and selected[nseg]; synchronous */
+int FLAGSTATS_hip_device_u16_segments_filter_sync(const uint16_t* d_array, uint64_t n, const uint64_t* offsets, uint64_t nseg,
+                                                  uint32_t require, uint32_t exclude, const uint8_t* d_mapq, uint32_t min_mapq,
+                                                  uint64_t* out, uint64_t* selected, int flags);
+/* HOST array, column and offsets, HOST out[nseg][32] and selected[nseg]; synchronous.  Only [offsets[0], offsets[nseg]) of array
+ * and column crosses the bus, in the engine's chunks (knob "chunk_flags"), each chunk's slice of the column behind its flags; a
+ * segment that spans chunks is summed on the device. */
+int FLAGSTATS_hip_u16_x64_segments_filter(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint64_t nseg,
+                                          uint32_t require, uint32_t exclude, const uint8_t* mapq, uint32_t min_mapq,
+                                          uint64_t* out, uint64_t* selected, int flags);
+
 /* 64-bit positional popcount in this library's convention: out[16] += bit counts (host array / device array) */
 int FLAGSTATS_hip_pospopcnt_u16_x64(const uint16_t* array, uint64_t n, uint64_t* out);
 int FLAGSTATS_hip_device_pospopcnt_u16(const uint16_t* d_array, uint64_t n, uint64_t* d_out, void* stream);

@@ -3,7 +3,7 @@
 // reference's 32 slots and the two epilogue forms.  Device code only.  Shared by the product kernel and by the measurement
 // build's schedules (flagstat_kernels_tuning.hip, `make tuning`), which differ in HOW a step's vectors are loaded, not in what
 // is done with them (that unit keeps a step of its own: its XOR-only schedules cut into the tree).  The kernels derived from K1
-// -- flagstat_segments.hip, flagstat_wide.hip, flagstat_where.hip, flagstat_filter.hip -- call the same tree_step and end_step
+// -- flagstat_segments.hip, _wide.hip, _where.hip, _filter.hip, _segments_filter.hip -- call the same tree_step and end_step
 // and share, at the end of this file, schedule 71's constants and its re-issue of a vector's registers.
 #ifndef FLAGSTAT_COUNT_CORE_H_
 #define FLAGSTAT_COUNT_CORE_H_
@@ -387,7 +387,7 @@ __device__ __forceinline__ void load_step(uint4 (&v)[kUnroll], const uint4* __re
 }
 
 // ------------------------------------------------------------------ schedule 71, as the kernels derived from K1 run it
-// (flagstat_segments.hip, flagstat_wide.hip, flagstat_where.hip, flagstat_filter.hip)
+// (flagstat_segments.hip, flagstat_wide.hip, flagstat_where.hip, flagstat_filter.hip, flagstat_segments_filter.hip)
 constexpr int kRollDistance = 6;   // a vector's registers are re-issued for the vector six places on: 24 KiB in flight per CU
 constexpr int kWaveStride = 64;    // vectors between a lane's consecutive loads: each wave a contiguous 8 KiB of a step
 
