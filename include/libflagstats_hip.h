@@ -231,6 +231,48 @@ int FLAGSTATS_hip_u16_x64_segments_filter(const uint16_t* array, uint64_t n, con
                                           uint32_t require, uint32_t exclude, const uint8_t* mapq, uint32_t min_mapq,
                                           uint64_t* out, uint64_t* selected, int flags);
 
+/* ================= filtered wide input: -f / -F / -q on a FLAG column held as 4-byte or 8-byte integers =================
+ * The two normal cases at once: the column arrives as int32 or int64 (the wide entries) and the table wanted is that of
+ * `samtools view -F 0x904 -q 30` (the filtered entries).  One pass over the array as it is, no uint16 copy, no mask array.
+ * With f(i) = the low 16 bits of element i (little-endian elements of `elem_bytes` = 4 or 8 bytes, aligned to elem_bytes):
+ *   pass(i) = (f(i) & require) == require && (f(i) & exclude) == 0 && (min_mapq == 0 || mapq[i] >= min_mapq)
+ * (`mapq`: one uint8 per element, at any byte alignment; min_mapq == 0 reads no byte of it and it may then be NULL).
+ *   out      : FLAGSTAT_scalar's 32 counters over {f(i) : pass(i), 0 <= i < n}
+ *   selected : the number of i with pass(i)
+ *   high     : OR of (element & ~0xFFFF), taken as unsigned, over ALL n elements the call reads, passing or not.  The predicate
+ *              sees only the low 16 bits; an element whose low bits fail still reports its high bits: the mask says whether the
+ *              column is a valid FLAG column, not whether the selected reads are.
+ * require & exclude != 0 is legal, as in samtools, and passes nothing: nothing is launched and NO ELEMENT IS READ, so `high` is
+ * then 0 in the store form and untouched in the += form -- it says nothing about the column.  require == exclude == 0 with
+ * min_mapq == 0 is the wide count, selected == n.
+ * `flags`: bit 0 = store (out = counters, all 32 slots written; selected = count; high = mask) instead of out += counters,
+ * selected += count, high |= mask; bit 1 = superset (slots 0 / 16 = primary paired reads among those that pass, slot 9 =
+ * selected minus slot 25).  `selected` / `d_selected` and `high` / `d_high` may each be NULL: that value is not reported.
+ * n == 0 succeeds and touches nothing (the store form writes zeros).
+ * Refused (non-zero, message in FLAGSTATS_hip_last_error, outputs untouched, nothing launched): elem_bytes other than 4 or 8
+ * (2: use the u16 filter entries), an array pointer not aligned to elem_bytes, an n with n * elem_bytes not a size or too large
+ * for a wave's uint32 totals, require or exclude above 0xFFFF, min_mapq above 255, a NULL mapq with min_mapq > 0 and n > 0, a
+ * NULL array with n > 0, flag bits other than 0 and 1, NULL counters; for the device form also a d_out, d_selected or d_high
+ * that is not plain device memory, host memory for d_array or d_mapq, pointers on different devices, a stream of another device
+ * and an allocation shorter than the call needs (d_array: n * elem_bytes bytes, d_mapq: n bytes when min_mapq > 0, d_out: 256,
+ * d_selected: 8, d_high: 8). */
+/* DEVICE array and MAPQ column, DEVICE d_out[32], d_selected[1] and d_high[1] (uint64); asynchronous on `stream`: ONE kernel
+ * (the store form puts one memset per pointer in front of it; one in all when d_selected == d_out + 32 and d_high == d_out + 33),
+ * no workspace.  Adds and ORs are atomic: launches on several streams may share the three in the += form. */
+int FLAGSTATS_hip_device_wide_filter(const void* d_array, uint64_t n, int elem_bytes, uint32_t require, uint32_t exclude,
+                                     const uint8_t* d_mapq, uint32_t min_mapq, uint64_t* d_out, uint64_t* d_selected,
+                                     uint64_t* d_high, int flags, void* stream);
+/* DEVICE array and MAPQ column, HOST out[32], selected[1] and high[1]; synchronous */
+int FLAGSTATS_hip_device_wide_filter_sync(const void* d_array, uint64_t n, int elem_bytes, uint32_t require, uint32_t exclude,
+                                          const uint8_t* d_mapq, uint32_t min_mapq, uint64_t* out, uint64_t* selected,
+                                          uint64_t* high, int flags);
+/* HOST array and MAPQ column, HOST out[32], selected[1] and high[1]; synchronous.  The array crosses the bus as it is in the
+ * engine's chunks (knob "chunk_flags": chunk_flags * 2 bytes of elements each), each chunk's slice of the column behind its
+ * elements; counters, count and mask are summed / ORed on the device. */
+int FLAGSTATS_hip_wide_x64_filter(const void* array, uint64_t n, int elem_bytes, uint32_t require, uint32_t exclude,
+                                  const uint8_t* mapq, uint32_t min_mapq, uint64_t* out, uint64_t* selected, uint64_t* high,
+                                  int flags);
+
 /* 64-bit positional popcount in this library's convention: out[16] += bit counts (host array / device array) */
 int FLAGSTATS_hip_pospopcnt_u16_x64(const uint16_t* array, uint64_t n, uint64_t* out);
 int FLAGSTATS_hip_device_pospopcnt_u16(const uint16_t* d_array, uint64_t n, uint64_t* d_out, void* stream);

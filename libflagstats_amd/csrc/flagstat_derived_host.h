@@ -1,6 +1,6 @@
 // flagstat_derived_host.h -- internal: the host code that the kernels derived from K1 share (flagstat_wide.hip, flagstat_where.hip,
-// flagstat_filter.hip): the launcher's step split and store-form memset, the 33-word device row of a synchronous call, and the
-// bodies of the three entry forms -- on the caller's stream, synchronous over device memory, chunked over host memory.  What
+// flagstat_filter.hip, flagstat_wide_filter.hip): the launcher's step split and store-form memset, the device row of a synchronous
+// call (32 counters and one trailing word, or two: kRowWords / kRowWords2), and the bodies of the three entry forms -- on the caller's stream, synchronous over device memory, chunked over host memory.  What
 // differs between the kernels arrives as arguments and callables: the names of their pointers, the text of their refusals, how
 // a chunk's inputs are copied and launched.  A HIP call that a callable makes goes through FS_HIP_TRY there, so the text of its
 // failure names the caller's own expression.
@@ -70,17 +70,30 @@ inline hipError_t zero_counters(uint64_t* d_out32, uint64_t* d_word, hipStream_t
     return e;
 }
 
+// the same with two trailing words (selected count, then mask): one memset where they are one allocation's 34 words
+inline hipError_t zero_counters(uint64_t* d_out32, uint64_t* d_word, uint64_t* d_word2, hipStream_t stream)
+{
+    if (d_word != d_out32 + 32 || d_word2 != d_out32 + 33) {
+        const hipError_t e = zero_counters(d_out32, d_word, stream);
+        return e == hipSuccess && d_word2 ? hipMemsetAsync(d_word2, 0, sizeof(uint64_t), stream) : e;
+    }
+    return hipMemsetAsync(d_out32, 0, 34 * sizeof(uint64_t), stream);
+}
+
 // ------------------------------------------------------------------ C entry points
-// device counters[32] + the 33rd word of one synchronous call; `what` names the allocation in the text of a failure
+constexpr int kRowWords = 33;    // counters[32] + one trailing word
+constexpr int kRowWords2 = 34;   // counters[32] + two: a count (added), then a mask (ORed)
+
+// device counters[32] + the trailing words of one synchronous call; `what` names the allocation in the text of a failure
 struct Row {
     uint64_t* d = nullptr;
     ~Row()
     {
         if (d) (void)hipFree(d);
     }
-    int alloc(const char* what)
+    int alloc(const char* what, int words = kRowWords)
     {
-        const hipError_t e = hipMalloc(&d, 33 * sizeof(uint64_t));
+        const hipError_t e = hipMalloc(&d, static_cast<size_t>(words) * sizeof(uint64_t));
         if (e != hipSuccess) {
             d = nullptr;
             return fsint::fail_hip(what, e);
@@ -104,6 +117,20 @@ inline void apply(uint64_t* out, uint64_t* word, const uint64_t (&got)[33], int 
     }
 }
 
+// the same with two trailing words: the count is added, the mask is ORed
+inline void apply(uint64_t* out, uint64_t* count, uint64_t* mask, const uint64_t (&got)[kRowWords2], int flags)
+{
+    if (flags & 1) {
+        for (int i = 0; i < 32; ++i) out[i] = got[i];
+        if (count) *count = got[32];
+        if (mask) *mask = got[33];
+    } else {
+        for (int i = 0; i < 32; ++i) out[i] += got[i];
+        if (count) *count += got[32];
+        if (mask) *mask |= got[33];
+    }
+}
+
 // the result of a call over no elements
 inline void store_nothing(uint64_t* out, uint64_t* word, int flags)
 {
@@ -111,6 +138,12 @@ inline void store_nothing(uint64_t* out, uint64_t* word, int flags)
         for (int i = 0; i < 32; ++i) out[i] = 0;
         if (word) *word = 0;
     }
+}
+
+inline void store_nothing(uint64_t* out, uint64_t* word, uint64_t* word2, int flags)
+{
+    store_nothing(out, word, flags);
+    if ((flags & 1) && word2) *word2 = 0;
 }
 
 // an input array of a call: its pointer, the name the refusals use for it, the bytes the call reads from it on
@@ -143,12 +176,20 @@ struct DeviceCall {
 
     int open(const void* d_out, const DeviceWord& word, const Input* in, int inputs, void* stream)
     {
+        return open(d_out, &word, 1, in, inputs, stream);
+    }
+
+    // the same with `nwords` trailing words, each optional
+    int open(const void* d_out, const DeviceWord* words, int nwords, const Input* in, int inputs, void* stream)
+    {
         int dev_out = -1, dev = -1;
         bool plain = false;
         int rc = fsint::device_of_pointer(d_out, "d_out", &dev_out, &plain);
         if (rc) return rc;
         if (!plain) return fsint::fail_text("d_out must be device memory (the counters are added with device atomics)");
-        if (word.p) {
+        for (int k = 0; k < nwords; ++k) {
+            const DeviceWord& word = words[k];
+            if (!word.p) continue;
             rc = fsint::device_of_pointer(word.p, word.name, &dev, &plain);
             if (rc) return rc;
             if (!plain) {
@@ -173,24 +214,29 @@ struct DeviceCall {
 };
 
 // every allocation holds what the call touches of it
-inline int check_extents(const void* d_out, const DeviceWord& word, const Input* in, int inputs)
+inline int check_extents(const void* d_out, const DeviceWord* words, int nwords, const Input* in, int inputs)
 {
     int rc;
     if ((rc = fsint::check_extent(d_out, 32 * sizeof(uint64_t), "d_out"))) return rc;
-    if (word.p && (rc = fsint::check_extent(word.p, sizeof(uint64_t), word.name))) return rc;
+    for (int k = 0; k < nwords; ++k)
+        if (words[k].p && (rc = fsint::check_extent(words[k].p, sizeof(uint64_t), words[k].name))) return rc;
     for (int i = 0; i < inputs; ++i)
         if ((rc = fsint::check_extent(in[i].p, in[i].bytes, in[i].name))) return rc;
     return 0;
+}
+
+inline int check_extents(const void* d_out, const DeviceWord& word, const Input* in, int inputs)
+{
+    return check_extents(d_out, &word, 1, in, inputs);
 }
 
 inline int fits_always(fsint::Engine&) { return 0; }
 
 // The synchronous form over device memory (n > 0, arguments checked): the inputs live on one device (the first one's); under its
 // engine's lock `fits(e)` may still refuse, the extents are checked, then `launch(e, row, s)` counts in the store form into a
-// row of its own on the engine's first stream and the result is applied to the caller's host words.
-template <typename Fits, typename Launch>
-int sync_call(const Input* in, int inputs, const char* row_what, uint64_t* out, uint64_t* word, int flags, WordOp op, Fits&& fits,
-              Launch&& launch)
+// row of its own (WORDS uint64) on the engine's first stream and `apply_fn(got)` takes the result to the caller's host words.
+template <int WORDS, typename Fits, typename Launch, typename Apply>
+int sync_call_row(const Input* in, int inputs, const char* row_what, Fits&& fits, Launch&& launch, Apply&& apply_fn)
 {
     int rc, dev = -1, dev_i = -1;
     rc = fsint::device_of_pointer(in[0].p, in[0].name, &dev);
@@ -211,23 +257,41 @@ int sync_call(const Input* in, int inputs, const char* row_what, uint64_t* out, 
     for (int i = 0; i < inputs; ++i)
         if ((rc = fsint::check_extent(in[i].p, in[i].bytes, in[i].name))) return rc;
     Row row;
-    if ((rc = row.alloc(row_what))) return rc;
-    uint64_t got[33];
+    if ((rc = row.alloc(row_what, WORDS))) return rc;
+    uint64_t got[WORDS];
     hipStream_t s = e.stream[0];
     if ((rc = launch(e, row, s))) return rc;
     FS_HIP_TRY(hipMemcpyAsync(got, row.d, sizeof got, hipMemcpyDeviceToHost, s));
     FS_HIP_TRY(hipStreamSynchronize(s));
-    apply(out, word, got, flags, op);
+    apply_fn(got);
     return 0;
+}
+
+// one trailing word, combined by `op`
+template <typename Fits, typename Launch>
+int sync_call(const Input* in, int inputs, const char* row_what, uint64_t* out, uint64_t* word, int flags, WordOp op, Fits&& fits,
+              Launch&& launch)
+{
+    return sync_call_row<kRowWords>(in, inputs, row_what, fits, launch,
+                                    [&](const uint64_t (&got)[kRowWords]) { apply(out, word, got, flags, op); });
+}
+
+// two trailing words: a count, then a mask
+template <typename Fits, typename Launch>
+int sync_call2(const Input* in, int inputs, const char* row_what, uint64_t* out, uint64_t* count, uint64_t* mask, int flags, Fits&& fits,
+               Launch&& launch)
+{
+    return sync_call_row<kRowWords2>(in, inputs, row_what, fits, launch,
+                                     [&](const uint64_t (&got)[kRowWords2]) { apply(out, count, mask, got, flags); });
 }
 
 // The form over host memory (n > 0, arguments checked): the n elements cross the bus in chunks of `chunk` elements, alternating
 // between the default engine's two streams and staging buffers of `slot_flags` uint16 each (the copy of chunk k + 1 overlaps the
 // kernel on chunk k).  `chunk_fn(e, row, sl, pos, c)` copies the inputs of elements [pos, pos + c) into e.stage[sl] and launches
-// on e.stream[sl]; every chunk's launch adds into the same row.  `fits(e)` may refuse before anything is staged.
-template <typename Fits, typename Chunk>
-int host_call(uint64_t n, uint64_t chunk, uint64_t slot_flags, const char* row_what, uint64_t* out, uint64_t* word, int flags,
-              WordOp op, Fits&& fits, Chunk&& chunk_fn)
+// on e.stream[sl]; every chunk's launch adds into the same row (WORDS uint64).  `fits(e)` may refuse before anything is staged;
+// `apply_fn(got)` takes the result to the caller's host words.
+template <int WORDS, typename Fits, typename Chunk, typename Apply>
+int host_call_row(uint64_t n, uint64_t chunk, uint64_t slot_flags, const char* row_what, Fits&& fits, Chunk&& chunk_fn, Apply&& apply_fn)
 {
     int rc;
     fsint::Engine* ep = fsint::default_engine();
@@ -239,14 +303,14 @@ int host_call(uint64_t n, uint64_t chunk, uint64_t slot_flags, const char* row_w
     if (!guard.ok()) return -1;
     fsint::lz4_gpu_other_use(e);
     Row row;
-    if ((rc = row.alloc(row_what))) return rc;
+    if ((rc = row.alloc(row_what, WORDS))) return rc;
     if ((rc = fsint::engine_second(e))) return rc;
     if ((rc = fits(e))) return rc;
     const int slots = n > chunk ? 2 : 1;
     for (int i = 0; i < slots; ++i)
         if ((rc = fsint::stage_reserve(e, i, slot_flags))) return rc;
     hipStream_t s0 = e.stream[0];
-    FS_HIP_TRY(hipMemsetAsync(row.d, 0, 33 * sizeof(uint64_t), s0));
+    FS_HIP_TRY(hipMemsetAsync(row.d, 0, WORDS * sizeof(uint64_t), s0));
     if (slots == 2 && (rc = fsint::stream_wait_stream(e, e.stream[1], s0))) return rc;
     uint64_t k = 0;
     for (uint64_t pos = 0; pos < n; pos += chunk, ++k) {
@@ -255,12 +319,30 @@ int host_call(uint64_t n, uint64_t chunk, uint64_t slot_flags, const char* row_w
         if ((rc = chunk_fn(e, row, sl, pos, c))) return rc;
     }
     if (slots == 2 && (rc = fsint::stream_wait_stream(e, s0, e.stream[1]))) return rc;
-    uint64_t got[33];
+    uint64_t got[WORDS];
     FS_HIP_TRY(hipMemcpyAsync(got, row.d, sizeof got, hipMemcpyDeviceToHost, s0));
     FS_HIP_TRY(hipStreamSynchronize(s0));
     if (slots == 2) FS_HIP_TRY(hipStreamSynchronize(e.stream[1]));
-    apply(out, word, got, flags, op);
+    apply_fn(got);
     return 0;
+}
+
+// one trailing word, combined by `op`
+template <typename Fits, typename Chunk>
+int host_call(uint64_t n, uint64_t chunk, uint64_t slot_flags, const char* row_what, uint64_t* out, uint64_t* word, int flags,
+              WordOp op, Fits&& fits, Chunk&& chunk_fn)
+{
+    return host_call_row<kRowWords>(n, chunk, slot_flags, row_what, fits, chunk_fn,
+                                    [&](const uint64_t (&got)[kRowWords]) { apply(out, word, got, flags, op); });
+}
+
+// two trailing words: a count, then a mask
+template <typename Fits, typename Chunk>
+int host_call2(uint64_t n, uint64_t chunk, uint64_t slot_flags, const char* row_what, uint64_t* out, uint64_t* count, uint64_t* mask,
+               int flags, Fits&& fits, Chunk&& chunk_fn)
+{
+    return host_call_row<kRowWords2>(n, chunk, slot_flags, row_what, fits, chunk_fn,
+                                     [&](const uint64_t (&got)[kRowWords2]) { apply(out, count, mask, got, flags); });
 }
 
 // host streaming chunk in flags (knob "chunk_flags", at least one vector)

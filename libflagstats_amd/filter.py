@@ -31,6 +31,37 @@ def _check_predicate(require, exclude, min_mapq, has_mapq: bool):
     return int(require), int(exclude), int(min_mapq)
 
 
+def _check_mapq_numpy(mapq, n: int):
+    """a given host MAPQ column is a 1-D ``uint8`` array of ``n`` elements; returns it contiguous (``None`` stays ``None``)"""
+    if mapq is None:
+        return None
+    if not isinstance(mapq, np.ndarray):
+        raise ValueError("mapq must be a numpy.ndarray, not %s" % type(mapq).__name__)
+    if mapq.dtype != np.uint8:
+        raise ValueError("mapq must have dtype uint8, not %s" % mapq.dtype)
+    if mapq.ndim != 1:
+        raise ValueError("mapq must be 1-D, not %d-D" % mapq.ndim)
+    if mapq.size != n:
+        raise ValueError("mapq must have one element per value (%d), not %d" % (n, mapq.size))
+    return np.ascontiguousarray(mapq)
+
+
+def _check_mapq_torch(mapq, n: int) -> None:
+    """a given MAPQ tensor is 1-D, contiguous, ``torch.uint8`` and has ``n`` elements"""
+    import torch
+
+    if mapq is None:
+        return
+    if not isinstance(mapq, torch.Tensor):
+        raise ValueError("mapq must be a torch.Tensor, not %s" % type(mapq).__name__)
+    if mapq.dtype != torch.uint8:
+        raise ValueError("mapq must have dtype torch.uint8, not %s" % mapq.dtype)
+    if mapq.dim() != 1 or not mapq.is_contiguous():
+        raise ValueError("mapq must be 1-D and contiguous")
+    if mapq.numel() != n:
+        raise ValueError("mapq must have one element per value (%d), not %d" % (n, mapq.numel()))
+
+
 def _check_numpy(values, mapq):
     if not isinstance(values, np.ndarray):
         raise ValueError("values must be a numpy.ndarray, not %s" % type(values).__name__)
@@ -38,17 +69,7 @@ def _check_numpy(values, mapq):
         raise ValueError("values must have dtype uint16, not %s" % values.dtype)
     if values.ndim != 1:
         raise ValueError("values must be 1-D, not %d-D" % values.ndim)
-    if mapq is not None:
-        if not isinstance(mapq, np.ndarray):
-            raise ValueError("mapq must be a numpy.ndarray, not %s" % type(mapq).__name__)
-        if mapq.dtype != np.uint8:
-            raise ValueError("mapq must have dtype uint8, not %s" % mapq.dtype)
-        if mapq.ndim != 1:
-            raise ValueError("mapq must be 1-D, not %d-D" % mapq.ndim)
-        if mapq.size != values.size:
-            raise ValueError("mapq must have one element per value (%d), not %d" % (values.size, mapq.size))
-        mapq = np.ascontiguousarray(mapq)
-    return np.ascontiguousarray(values), mapq
+    return np.ascontiguousarray(values), _check_mapq_numpy(mapq, values.size)
 
 
 def counters_filter(values, require: int = 0, exclude: int = 0, mapq=None, min_mapq: int = 0, superset: bool = False):
@@ -104,15 +125,7 @@ def count_torch_filter(t, require: int = 0, exclude: int = 0, mapq=None, min_map
         raise ValueError("t must have dtype int16 or uint16, not %s" % t.dtype)
     if t.dim() != 1 or not t.is_contiguous():
         raise ValueError("t must be 1-D and contiguous")
-    if mapq is not None:
-        if not isinstance(mapq, torch.Tensor):
-            raise ValueError("mapq must be a torch.Tensor, not %s" % type(mapq).__name__)
-        if mapq.dtype != torch.uint8:
-            raise ValueError("mapq must have dtype torch.uint8, not %s" % mapq.dtype)
-        if mapq.dim() != 1 or not mapq.is_contiguous():
-            raise ValueError("mapq must be 1-D and contiguous")
-        if mapq.numel() != t.numel():
-            raise ValueError("mapq must have one element per value (%d), not %d" % (t.numel(), mapq.numel()))
+    _check_mapq_torch(mapq, t.numel())
     require, exclude, min_mapq = _check_predicate(require, exclude, min_mapq, mapq is not None)
     _checks.check_result_pair(out, "selected", selected)
     out, selected = _checks.place_result_pair(t, out, "selected", selected, others=(("mapq", mapq),))

@@ -32,6 +32,18 @@ def _check_values(values) -> np.ndarray:
     return np.ascontiguousarray(values)
 
 
+def _check_tensor(t) -> None:
+    """``t`` is a 1-D contiguous integer tensor of 2-, 4- or 8-byte elements (where it lives is place_result_pair's business)"""
+    import torch
+
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("t must be a torch.Tensor, not %s" % type(t).__name__)
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool or t.element_size() not in (2, 4, 8):
+        raise ValueError("t must have an integer dtype of 2, 4 or 8 bytes, not %s" % t.dtype)
+    if t.dim() != 1 or not t.is_contiguous():
+        raise ValueError("t must be 1-D and contiguous")
+
+
 def high_bits_message(high: int) -> str:
     return "values outside 0..65535: bits 0x%X set above bit 15" % high
 
@@ -89,12 +101,7 @@ def count_torch_ints(t, out=None, high=None, store: bool = False, superset: bool
     mask as a signed 64-bit number: compare with 0, or take ``int(high) & (2**64 - 1)``."""
     import torch
 
-    if not isinstance(t, torch.Tensor):
-        raise ValueError("t must be a torch.Tensor, not %s" % type(t).__name__)
-    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool or t.element_size() not in (2, 4, 8):
-        raise ValueError("t must have an integer dtype of 2, 4 or 8 bytes, not %s" % t.dtype)
-    if t.dim() != 1 or not t.is_contiguous():
-        raise ValueError("t must be 1-D and contiguous")
+    _check_tensor(t)
     _checks.check_result_pair(out, "high", high)
     out, high = _checks.place_result_pair(t, out, "high", high)
     lib = _lib.lib()
