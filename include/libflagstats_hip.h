@@ -64,7 +64,19 @@ int FLAGSTATS_u16_x64(const uint16_t* array, uint64_t n, uint64_t* out);
  * 65th stream takes the least recently used one's (after a device-wide wait), and raising the knob "blocks_per_cu" replaces a
  * stream's workspace at its next call.  Plain launches never notice.  A launch CAPTURED into a graph holds its stream's
  * workspace pointer: the graph stays valid while its stream stays among the 64 most recently used and "blocks_per_cu" is not
- * raised; after either, replaying it touches freed memory -- capture it again instead. */
+ * raised; after either, replaying it touches freed memory -- capture it again instead.
+ * Capture and replay are tested (tests/test_gpu_graphs.py, torch.cuda.graph in both capture error modes) for this entry, _store,
+ * _superset, device_pospopcnt_u16, device_u16_segments, _where, _filter, _segments_filter, device_wide and device_wide_filter,
+ * and for the torch layers on top of them: one call or all of them in one graph, after one plain call on the device (the first
+ * call creates the device's engine, which is no stream work).  A captured launch freezes its pointers, n, its grid and the form
+ * the knobs chose at capture time (epilogue form, the segments policy); it reads arrays, selections, MAPQ bytes and device
+ * offsets at replay time, so a replay counts what the buffers hold then.  The store forms' zeroes are part of the graph (while
+ * the stream is capturing they come from a small kernel, not a memset node: memset nodes were seen to write stale bytes when
+ * replayed on ROCm 7.0).  Replay-stream contract: a captured launch of the entries with a workspace uses the workspace of
+ * the stream it was captured on, without a lock -- replay the graph on that stream, or order every replay against that stream's
+ * other work (and against other graphs captured on it); two of them running at once corrupt each other's counters.
+ * NOT tested under capture: the all-reduce forms, the sessions, a graph replayed after its stream's workspace was evicted or
+ * "blocks_per_cu" raised (see above), and graphs running concurrently over one captured workspace. */
 int FLAGSTATS_hip_device_u16(const uint16_t* d_array, uint64_t n, uint64_t* d_out, void* stream);
 /* same, but d_out[32] = counters (all 32 slots written, never-written slots as 0): one query per call with no zeroing
  * launch in front; used by the multi-GPU step before its all-reduce. */
@@ -124,10 +136,11 @@ int FLAGSTATS_hip_u16_x64_segments(const uint16_t* array, uint64_t n, const uint
  * of another device and an allocation shorter than n * elem_bytes (d_out: 256, d_high: 8) bytes from the pointer on. */
 /* DEVICE array, DEVICE d_out[32] and d_high[1] (uint64); asynchronous on `stream`: ONE kernel (the store form puts one memset
  * per pointer in front of it; one in all when d_high == d_out + 32).  No per-stream workspace is kept, so a captured launch
- * holds no pointer of the library's (the caveat of FLAGSTATS_hip_device_u16); capturing this entry into a graph is untested,
- * though: it queries its pointers (hipPointerGetAttributes, hipMemGetAddressRange) and creates the device's engine on a first
- * call, so make one plain call before capturing.  Adds and ORs are atomic: launches on several streams may share d_out and
- * d_high in the += form. */
+ * holds no pointer of the library's (the caveat of FLAGSTATS_hip_device_u16) and may be replayed on any stream.  Capture into a
+ * graph is tested for both widths and both layouts of d_high (see FLAGSTATS_hip_device_u16); the entry queries its pointers
+ * (hipPointerGetAttributes, hipMemGetAddressRange: neither disturbs a capture) and creates the device's engine on a first call, so
+ * make one plain call before capturing.  Adds and ORs are atomic: launches on several streams may share d_out and d_high in
+ * the += form. */
 int FLAGSTATS_hip_device_wide(const void* d_array, uint64_t n, int elem_bytes, uint64_t* d_out, uint64_t* d_high, int flags,
                               void* stream);
 /* DEVICE array, HOST out[32] and high[1]; synchronous */

@@ -61,12 +61,12 @@ inline hipError_t step_split(uint64_t address, uint64_t n, int elem_bytes, uint3
 }
 
 // the store form's zeroes in front of a launch: the counters and the optional 33rd word (mask, selected count), in one memset
-// where they are one allocation's 33 words
+// where they are one allocation's 33 words (fsk_zero_words: hipMemsetAsync, or a kernel while the stream is being captured)
 inline hipError_t zero_counters(uint64_t* d_out32, uint64_t* d_word, hipStream_t stream)
 {
     const bool together = d_word == d_out32 + 32;
-    hipError_t e = hipMemsetAsync(d_out32, 0, (together ? 33 : 32) * sizeof(uint64_t), stream);
-    if (e == hipSuccess && d_word && !together) e = hipMemsetAsync(d_word, 0, sizeof(uint64_t), stream);
+    hipError_t e = fsk_zero_words(d_out32, together ? 33 : 32, stream);
+    if (e == hipSuccess && d_word && !together) e = fsk_zero_words(d_word, 1, stream);
     return e;
 }
 
@@ -75,9 +75,9 @@ inline hipError_t zero_counters(uint64_t* d_out32, uint64_t* d_word, uint64_t* d
 {
     if (d_word != d_out32 + 32 || d_word2 != d_out32 + 33) {
         const hipError_t e = zero_counters(d_out32, d_word, stream);
-        return e == hipSuccess && d_word2 ? hipMemsetAsync(d_word2, 0, sizeof(uint64_t), stream) : e;
+        return e == hipSuccess && d_word2 ? fsk_zero_words(d_word2, 1, stream) : e;
     }
-    return hipMemsetAsync(d_out32, 0, 34 * sizeof(uint64_t), stream);
+    return fsk_zero_words(d_out32, 34, stream);
 }
 
 // ------------------------------------------------------------------ C entry points

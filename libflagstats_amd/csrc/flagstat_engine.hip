@@ -808,7 +808,7 @@ int count_device_async(Engine& e, const uint16_t* d_array, uint64_t n, uint64_t*
 {
     const int base = op & OP_BASE_MASK;
     if (n == 0) {
-        if (base == OP_FLAGSTAT_STORE) HIP_TRY(hipMemsetAsync(d_out, 0, 32 * sizeof(uint64_t), s));
+        if (base == OP_FLAGSTAT_STORE) HIP_TRY(fsk_zero_words(d_out, 32, s));
         return 0;
     }
     if (!d_array) return fail_text("NULL array with n > 0");

@@ -69,6 +69,8 @@ void fsk_warm(void);                      // loads K1 / K2's code object without
 hipError_t fsk_launch(const uint16_t* d_array, uint64_t n, uint32_t grid, int variant, uint64_t* d_partials,
                       uint32_t* d_ticket, uint64_t* d_out32, hipStream_t stream, uint64_t* signal_word = nullptr,
                       uint64_t signal_value = 0);
+// the zeroing kernel of fsk_zero_words below (flagstat_zero.hip); weak: a host-only build of the engine links without it
+hipError_t fsk_launch_zero_words(uint64_t* d_words, uint64_t nwords, hipStream_t stream) __attribute__((weak));
 int fsk_variant_supported(int variant);   // K1 schedule compiled into this build?
 // measurement build only (defined in flagstat_kernels_tuning.hip, `make tuning`; NULL in the product library -- callers
 // check fsk_tuning_build() first).  Dynamic schedule policy (variant bit 7): first_pct = share of the steps in the static
@@ -98,6 +100,26 @@ hipError_t fsk_clock_probe(uint64_t* d_out, uint32_t grid, uint64_t ticks, hipSt
 // on-device input makers (flagstat_generate.hip)
 hipError_t fsk_generate(uint16_t* d_array, uint64_t n, int kind, uint64_t seed, uint32_t mask, uint64_t first_index,
                         hipStream_t stream);
+}
+
+// d_words[0 .. nwords) = 0 on `stream`, what the store forms put in front of their kernel.  A plain launch takes hipMemsetAsync.
+// While `stream` is being captured into a graph a kernel zeroes the words instead: a memset NODE does not survive replays on the
+// HIP runtime this was tested with (ROCm 7.0) -- once other work had run between two replays the node filled its range with a
+// stale 16-byte pattern (two addresses) instead of zeros, and every counter added on top of it was wrong
+// (tests/test_gpu_graphs.py: each store form, replayed once more after its result words were overwritten; a captured
+// hipMemsetAsync alone, without this library, shows the same).
+inline hipError_t fsk_zero_words(uint64_t* d_words, uint64_t nwords, hipStream_t stream)
+{
+    if (nwords == 0) return hipSuccess;
+    if (fsk_launch_zero_words) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(stream, &cap) != hipSuccess) {
+            (void)hipGetLastError();
+            cap = hipStreamCaptureStatusNone;
+        }
+        if (cap == hipStreamCaptureStatusActive) return fsk_launch_zero_words(d_words, nwords, stream);
+    }
+    return hipMemsetAsync(d_words, 0, nwords * sizeof(uint64_t), stream);
 }
 
 #endif

@@ -16,7 +16,7 @@ extern "C" {
 // Counts the intersection of every segment i = [d_offsets[i], d_offsets[i+1]) (i < nseg, global flag indices) with the global
 // flag range [base, base + m), whose m flags d_chunk holds (any 2-byte alignment), and adds it to d_out[i * 32 + slot]
 // (uint64, plain device memory) with relaxed agent-scope atomics; asynchronous on `stream`.
-//   mode bit 0: store form -- d_out[0 .. nseg * 32) is zeroed first (one hipMemsetAsync on `stream`), so every slot of every
+//   mode bit 0: store form -- d_out[0 .. nseg * 32) is zeroed first (fsk_zero_words on `stream`: one hipMemsetAsync, a kernel while capturing), so every slot of every
 //               segment is written; segments that lie inside one wave's range are then stored with plain stores
 //   mode bit 1: superset slots (0 / 16 primary paired reads, 9 = the piece's length minus its fail-QC reads)
 // Bounds: every offset the kernel reads is clamped to [base, base + m] and a segment whose end lies before its begin is

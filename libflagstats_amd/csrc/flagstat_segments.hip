@@ -254,7 +254,7 @@ extern "C" hipError_t fsk_launch_segments(const uint16_t* d_chunk, uint64_t base
     const uintptr_t addr = reinterpret_cast<uintptr_t>(d_chunk);
     if (addr & 1u) return hipErrorInvalidValue;
     if (mode & 1) {
-        const hipError_t e = hipMemsetAsync(d_out, 0, nseg * 32 * sizeof(uint64_t), stream);
+        const hipError_t e = fsk_zero_words(d_out, nseg * 32, stream);
         if (e != hipSuccess) return e;
     }
     if (m == 0) return hipSuccess;

@@ -15,7 +15,7 @@ extern "C" {
 //   pass(j) = (flag[j] & require) == require && (flag[j] & exclude) == 0 && (min_mapq == 0 || mapq[j] >= min_mapq),
 // are counted into d_out[i * 32 + slot] and their number is added to d_selected[i] (nseg uint64; may be NULL: nothing
 // reported), both plain device memory, with relaxed agent-scope atomics; one kernel, asynchronous on `stream`, no workspace.
-//   mode bit 0: store form -- d_out[0 .. nseg * 32) and d_selected[0 .. nseg) are zeroed first (hipMemsetAsync on `stream`), so
+//   mode bit 0: store form -- d_out[0 .. nseg * 32) and d_selected[0 .. nseg) are zeroed first (fsk_zero_words on `stream`: hipMemsetAsync, a kernel while capturing), so
 //               every slot of every segment is written; segments that lie inside one wave's range are then stored with plain
 //               stores, rows and selected alike
 //   mode bit 1: superset slots (0 / 16 primary paired reads among those that pass, 9 = the piece's passing flags minus its

@@ -320,8 +320,8 @@ extern "C" hipError_t fsk_launch_segments_filter(const uint16_t* d_chunk, const 
         if (!wave_totals_fit(nunits, g)) return hipErrorInvalidValue;
     }
     if (mode & 1) {
-        hipError_t e = hipMemsetAsync(d_out, 0, nseg * 32 * sizeof(uint64_t), stream);
-        if (e == hipSuccess && d_selected) e = hipMemsetAsync(d_selected, 0, nseg * sizeof(uint64_t), stream);
+        hipError_t e = fsk_zero_words(d_out, nseg * 32, stream);
+        if (e == hipSuccess && d_selected) e = fsk_zero_words(d_selected, nseg, stream);
         if (e != hipSuccess) return e;
     }
     // a bit both required and excluded: no flag passes (samtools accepts the pair); the kernel's test assumes a disjoint pair
