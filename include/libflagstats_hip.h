@@ -66,7 +66,8 @@ int FLAGSTATS_u16_x64(const uint16_t* array, uint64_t n, uint64_t* out);
  * workspace pointer: the graph stays valid while its stream stays among the 64 most recently used and "blocks_per_cu" is not
  * raised; after either, replaying it touches freed memory -- capture it again instead.
  * Capture and replay are tested (tests/test_gpu_graphs.py, torch.cuda.graph in both capture error modes) for this entry, _store,
- * _superset, device_pospopcnt_u16, device_u16_segments, _where, _filter, _segments_filter, device_wide and device_wide_filter,
+ * _superset, device_pospopcnt_u16, device_u16_segments, _where, _filter, _segments_filter, device_wide and device_wide_filter
+ * (tests/test_gpu_segments_wide.py: device_wide_segments),
  * and for the torch layers on top of them: one call or all of them in one graph, after one plain call on the device (the first
  * call creates the device's engine, which is no stream work).  A captured launch freezes its pointers, n, its grid and the form
  * the knobs chose at capture time (epilogue form, the segments policy); it reads arrays, selections, MAPQ bytes and device
@@ -285,6 +286,39 @@ int FLAGSTATS_hip_device_wide_filter_sync(const void* d_array, uint64_t n, int e
 int FLAGSTATS_hip_wide_x64_filter(const void* array, uint64_t n, int elem_bytes, uint32_t require, uint32_t exclude,
                                   const uint8_t* mapq, uint32_t min_mapq, uint64_t* out, uint64_t* selected, uint64_t* high,
                                   int flags);
+
+/* ================= wide input per segment: a row and a high mask for every segment of an int32 / int64 column =================
+ * The union of the segmented and the wide entries: segment i (i < nseg) is [offsets[i], offsets[i+1]) of an array of 4-byte or
+ * 8-byte little-endian elements (aligned to elem_bytes), read as it is.  With f(j) = the low 16 bits of element j,
+ *   out[i * 32 + slot] : FLAGSTAT_scalar's 32 counters over {f(j) : offsets[i] <= j < offsets[i+1]}
+ *   high[i]            : OR over the elements j of segment i of (element & ~0xFFFF), taken as unsigned; 0 for an empty segment
+ * so a non-zero mask names the segment that holds the out-of-range element.  Elements before offsets[0], after offsets[nseg]
+ * and the bytes around the array enter no counter and no mask.  `high` / `d_high` may be NULL: no mask is reported.
+ * `flags`: bit 0 = store (every slot of every row and every high[i] written; empty segments read 0) instead of out += counters,
+ * high |= mask; bit 1 = superset (slots 0 / 16, and slot 9 = the segment's length minus its slot 25).  nseg == 0 succeeds and
+ * touches nothing.
+ * DEVICE offsets are clamped to [0, n] and not checked for order, as documented for FLAGSTATS_hip_device_u16_segments: malformed
+ * offsets give undefined rows and masks, never an access outside the array, d_out[nseg][32] or d_high[nseg].  HOST offsets are
+ * validated first (non-decreasing, offsets[nseg] <= n); on failure `out` and `high` are left untouched.
+ * Refused (non-zero, message in FLAGSTATS_hip_last_error, outputs untouched, nothing launched): elem_bytes other than 4 or 8 (2:
+ * use the u16 segments entries), flag bits other than 0 and 1, an array pointer not aligned to elem_bytes, a NULL array with
+ * n > 0, NULL offsets or out with nseg > 0, an nseg whose counters are not a size; for the device form also a d_out or d_high
+ * that is not plain device memory, pointers on different devices, a stream of another device and an allocation shorter than the
+ * call needs (d_array: n * elem_bytes bytes, d_offsets: (nseg + 1) * 8, d_out: nseg * 256, d_high: nseg * 8). */
+/* DEVICE array and offsets, DEVICE d_out[nseg][32] and d_high[nseg] (uint64); asynchronous on `stream`: ONE kernel (the store
+ * form puts one memset per pointer in front of it; one in all when d_high == d_out + nseg * 32), no workspace, so a captured
+ * launch holds no pointer of the library's.  Adds and ORs are atomic: launches on several streams may share d_out and d_high in
+ * the += form. */
+int FLAGSTATS_hip_device_wide_segments(const void* d_array, uint64_t n, int elem_bytes, const uint64_t* d_offsets, uint64_t nseg,
+                                       uint64_t* d_out, uint64_t* d_high, int flags, void* stream);
+/* DEVICE array, HOST offsets, HOST out[nseg][32] and high[nseg]; synchronous */
+int FLAGSTATS_hip_device_wide_segments_sync(const void* d_array, uint64_t n, int elem_bytes, const uint64_t* offsets,
+                                            uint64_t nseg, uint64_t* out, uint64_t* high, int flags);
+/* HOST array and offsets, HOST out[nseg][32] and high[nseg]; synchronous.  Only [offsets[0], offsets[nseg]) crosses the bus, as
+ * it is, in the engine's chunks (knob "chunk_flags": chunk_flags * 2 bytes of elements each); a segment that spans chunks is
+ * summed and ORed on the device. */
+int FLAGSTATS_hip_wide_x64_segments(const void* array, uint64_t n, int elem_bytes, const uint64_t* offsets, uint64_t nseg,
+                                    uint64_t* out, uint64_t* high, int flags);
 
 /* 64-bit positional popcount in this library's convention: out[16] += bit counts (host array / device array) */
 int FLAGSTATS_hip_pospopcnt_u16_x64(const uint16_t* array, uint64_t n, uint64_t* out);

@@ -94,6 +94,12 @@ SIGNATURES = {
     "FLAGSTATS_hip_u16_x64_segments_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                                              ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
                                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    "FLAGSTATS_hip_device_wide_segments": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+                                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "FLAGSTATS_hip_device_wide_segments_sync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p,
+                                                               ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    "FLAGSTATS_hip_wide_x64_segments": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
     "FLAGSTATS_hip_available": (ctypes.c_int, []),
     "FLAGSTATS_hip_device_count": (ctypes.c_int, []),
     "FLAGSTATS_hip_ctx_create": (ctypes.c_void_p, [ctypes.c_int]),
@@ -178,7 +184,7 @@ SIGNATURES = {
 }
 
 # internal launchers the tests and tests/perf drive directly (csrc/flagstat_wide.h, csrc/flagstat_where.h, csrc/flagstat_filter.h,
-# csrc/flagstat_segments_filter.h, csrc/flagstat_wide_filter.h); not part of the public headers, so kept apart from SIGNATURES, which mirrors those
+# csrc/flagstat_segments_filter.h, csrc/flagstat_wide_filter.h, csrc/flagstat_segments_wide.h); not part of the public headers, so kept apart from SIGNATURES, which mirrors those
 INTERNAL_SIGNATURES = {
     "fsk_launch_wide": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                        ctypes.c_uint32, ctypes.c_void_p]),
@@ -194,6 +200,9 @@ INTERNAL_SIGNATURES = {
     "fsk_launch_segments_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
                                                   ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p]),
+    "fsk_launch_segments_wide": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+                                                ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32,
+                                                ctypes.c_void_p]),
 }
 
 _lib = None

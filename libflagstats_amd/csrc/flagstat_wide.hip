@@ -35,41 +35,19 @@ namespace fsk {
 
 constexpr int kWideDepth = 8;        // chain depth as K1: epochs of 255 steps
 
-// narrow_out, wide_tree, load_guarded_wide and wave_or_lane63 are flagstat_wide_device.h's (shared with flagstat_wide_filter.hip)
+// narrow_out, wide_tree, wide_step_with, load_guarded_wide and wave_or_lane63 are flagstat_wide_device.h's (shared with
+// flagstat_wide_filter.hip and flagstat_segments_wide.hip)
 
-// One step: 8 vectors of 16 B per lane = 32 / W inputs of 4 flags each.
+// One step (wide_step_with) under this kernel's load schedule.
 // ROLL 0: the vectors are in v[].  ROLL 1, 2: K1's schedule 71 -- vector u's registers are re-issued for vector u + 6 of the same
 // step (`cur`) or, ROLL 1 only, u - 2 of the next one (`next`): 6 loads = 24 KiB per CU in flight.
 template <int W, int ROLL>
 __device__ __forceinline__ void wide_step(Lane<kWideDepth>& s, uint4 (&v)[kUnroll], uint32_t blk, uint32_t& or_even, uint32_t& or_odd,
                                           const uint4* __restrict__ cur, const uint4* __restrict__ next)
 {
-    constexpr int NIN = 32 / W;
-    uint32_t T[NIN], F[NIN], S[NIN];
-    uint32_t held = 0;       // W = 8: the even vector's P until the odd one's arrives
-#pragma unroll
-    for (int u = 0; u < kUnroll; ++u) {
-        uint32_t p0, p1 = 0;
-        __builtin_amdgcn_sched_barrier(0);
-        narrow_out<W>(v[u], p0, p1, or_even, or_odd);
+    wide_step_with<W>(s, v, blk, or_even, or_odd, [&](int u) __attribute__((always_inline)) {
         reissue<ROLL>(u, v, cur, next, kWaveStride, load_vec<true>);
-        __builtin_amdgcn_sched_barrier(0);
-        if (W == 8 && (u & 1) == 0) {
-            held = p0;
-            continue;
-        }
-        const uint32_t a = W == 4 ? p0 : held, b = W == 4 ? p1 : p0;   // flags 0,1 and 2,3
-        const uint32_t L = perm(b, a, 0x05040100u), H = perm(b, a, 0x07060302u);
-        const int i = W == 4 ? u : u / 2;
-        uint32_t q, k;
-        front4(L, H, T[i], q, k);
-        F[i] = T[i] & perm(0u, 0xFF00FF00u, q);
-        S[i] = perm(0u, 0x84428140u, q) & (k | 0x3F3F3F3Fu);
-    }
-    const uint32_t ct = wide_tree(T, s.t1, s.t2, s.t4, s.t8);
-    const uint32_t cf = wide_tree(F, s.f1, s.f2, s.f4, s.f8);
-    const uint32_t cs = wide_tree(S, s.s1, s.s2, s.s4, s.s8);
-    chain_push<0, kWideDepth>(s, blk, ct, cf, cs);
+    });
 }
 
 template <int W, int ROLL>

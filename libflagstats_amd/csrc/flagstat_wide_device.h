@@ -1,7 +1,7 @@
 // flagstat_wide_device.h -- internal, device code only: what the kernels over 4-byte and 8-byte elements share
-// (flagstat_wide.hip, flagstat_wide_filter.hip): the read-out of a loaded vector into the pair dword P and the mask accumulators,
-// the short carry-save tree of a step with 8 or 4 inputs, the guarded loader of an edge step and the OR over a wave.  How the
-// pieces fit is written out at the top of flagstat_wide.hip.
+// (flagstat_wide.hip, flagstat_wide_filter.hip, flagstat_segments_wide.hip): the read-out of a loaded vector into the pair dword P
+// and the mask accumulators, the short carry-save tree of a step with 8 or 4 inputs, the unfiltered step built from them (wide_step_with), the
+// guarded loader of an edge step and the OR over a wave.  How the pieces fit is written out at the top of flagstat_wide.hip.
 #ifndef FLAGSTAT_WIDE_DEVICE_H_
 #define FLAGSTAT_WIDE_DEVICE_H_
 
@@ -52,6 +52,42 @@ __device__ __forceinline__ uint32_t wide_tree(uint32_t (&x)[N], uint32_t& p1, ui
     wide_level<N / 4>(x, p4);
     wide_level<(N >= 8 ? N / 8 : 1)>(x, p8);
     return x[0];
+}
+
+// One step: 8 vectors of 16 B per lane = 32 / W inputs of 4 flags each, ONE weight-16 push into the lane's chain at `blk`.
+// `reissue_vec(u)` is the caller's re-issue of vector u's registers right after they have been read out, between the two
+// sched_barriers of a rolling schedule (K1's schedule 71 through reissue(), at the caller's stride between a lane's consecutive
+// loads: kWaveStride in flagstat_wide.hip, kSegRowVecs in flagstat_segments_wide.hip), or nothing when the vectors are all in v[].
+template <int W, int DEPTH, typename Reissue>
+__device__ __forceinline__ void wide_step_with(Lane<DEPTH>& s, uint4 (&v)[kUnroll], uint32_t blk, uint32_t& or_even, uint32_t& or_odd,
+                                               Reissue&& reissue_vec)
+{
+    constexpr int NIN = 32 / W;
+    uint32_t T[NIN], F[NIN], S[NIN];
+    uint32_t held = 0;       // W = 8: the even vector's P until the odd one's arrives
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+        uint32_t p0, p1 = 0;
+        __builtin_amdgcn_sched_barrier(0);
+        narrow_out<W>(v[u], p0, p1, or_even, or_odd);
+        reissue_vec(u);
+        __builtin_amdgcn_sched_barrier(0);
+        if (W == 8 && (u & 1) == 0) {
+            held = p0;
+            continue;
+        }
+        const uint32_t a = W == 4 ? p0 : held, b = W == 4 ? p1 : p0;   // flags 0,1 and 2,3
+        const uint32_t L = perm(b, a, 0x05040100u), H = perm(b, a, 0x07060302u);
+        const int i = W == 4 ? u : u / 2;
+        uint32_t q, k;
+        front4(L, H, T[i], q, k);
+        F[i] = T[i] & perm(0u, 0xFF00FF00u, q);
+        S[i] = perm(0u, 0x84428140u, q) & (k | 0x3F3F3F3Fu);
+    }
+    const uint32_t ct = wide_tree(T, s.t1, s.t2, s.t4, s.t8);
+    const uint32_t cf = wide_tree(F, s.f1, s.f2, s.f4, s.f8);
+    const uint32_t cs = wide_tree(S, s.s1, s.s2, s.s4, s.s8);
+    chain_push<0, DEPTH>(s, blk, ct, cf, cs);
 }
 
 // Vector j of the 16-byte grid holds element positions [j * 16 / W, (j + 1) * 16 / W); positions in [lo, hi) are the caller's
