@@ -320,6 +320,58 @@ int FLAGSTATS_hip_device_wide_segments_sync(const void* d_array, uint64_t n, int
 int FLAGSTATS_hip_wide_x64_segments(const void* array, uint64_t n, int elem_bytes, const uint64_t* offsets, uint64_t nseg,
                                     uint64_t* out, uint64_t* high, int flags);
 
+/* ================= filtered wide input per segment: -f / -F / -q for every segment of an int32 / int64 column =================
+ * The last corner of the grid {uint16, wide} x {whole array, per segment} x {no predicate, filter}: the per-contig, per-sample or
+ * per-block table of the reads passing `-F 0x904 -q 30`, straight from a FLAG column held as 4-byte or 8-byte little-endian
+ * integers (aligned to elem_bytes), in one pass and one launch.  Segment i (i < nseg) is [offsets[i], offsets[i+1]).  With
+ * f(j) = the low 16 bits of element j and
+ *   pass(j) = (f(j) & require) == require && (f(j) & exclude) == 0 && (min_mapq == 0 || mapq[j] >= min_mapq)
+ * (`mapq`: one uint8 per element of the whole array, at any byte alignment; min_mapq == 0 reads no byte of it and it may then
+ * be NULL):
+ *   out[i * 32 + slot] : FLAGSTAT_scalar's 32 counters over {f(j) : pass(j), offsets[i] <= j < offsets[i+1]}
+ *   selected[i]        : the number of j in segment i with pass(j)
+ *   high[i]            : OR of (element & ~0xFFFF), taken as unsigned, over EVERY element of segment i and of no other, passing
+ *                        or not -- FLAGSTATS_hip_device_wide_filter's meaning per segment: the mask says whether the segment is
+ *                        part of a valid FLAG column, and names the segment that holds an out-of-range element
+ * Elements before offsets[0], after offsets[nseg] and the bytes around the array enter no counter, no count and no mask; empty
+ * segments read 0.  `selected` / `d_selected` and `high` / `d_high` may each be NULL: that value is not reported.
+ * require & exclude != 0 is legal and passes nothing: nothing is launched and NO ELEMENT IS READ, so in the store form rows,
+ * counts and masks are 0 and in the += form they are untouched -- `high` then says nothing about the column.
+ * `flags`: bit 0 = store (every slot of every row, every selected[i] and every high[i] written) instead of out += counters,
+ * selected += count, high |= mask; bit 1 = superset (slots 0 / 16 = primary paired reads among those that pass, slot 9 =
+ * selected[i] minus slot 25).  nseg == 0 succeeds and touches nothing.
+ * DEVICE offsets are clamped to [0, n] and not checked for order, as documented for FLAGSTATS_hip_device_u16_segments: malformed
+ * offsets give undefined rows, counts and masks, never an access outside the array, the column or the outputs.  HOST offsets are
+ * validated first (non-decreasing, offsets[nseg] <= n); on failure the outputs are left untouched.
+ * Refused (non-zero, message in FLAGSTATS_hip_last_error, outputs untouched, nothing launched): elem_bytes other than 4 or 8 (2:
+ * use the u16 segmented filter entries), require or exclude above 0xFFFF, min_mapq above 255, flag bits other than 0 and 1, NULL
+ * offsets or out with nseg > 0, an nseg whose counters are not a size, a NULL array with n > 0, a NULL mapq with min_mapq > 0
+ * and n > 0, an array pointer not aligned to elem_bytes, an n with n * elem_bytes not a size or too large for a wave's uint32
+ * totals; for the device form also a d_out, d_selected or d_high that is not plain device memory, host memory for d_array,
+ * d_mapq or d_offsets, pointers on different devices, a stream of another device and an allocation shorter than the call needs
+ * (d_array: n * elem_bytes bytes, d_mapq: n bytes when min_mapq > 0, d_offsets: (nseg + 1) * 8, d_out: nseg * 256, d_selected:
+ * nseg * 8, d_high: nseg * 8). */
+/* DEVICE array, MAPQ column and offsets, DEVICE d_out[nseg][32], d_selected[nseg] and d_high[nseg] (uint64); asynchronous on
+ * `stream`: ONE kernel (the store form puts one memset per pointer in front of it; one in all when d_selected == d_out + nseg *
+ * 32 and d_high == d_selected + nseg), no workspace, so a captured launch holds no pointer of the library's.  Adds and ORs are
+ * atomic: launches on several streams may share the three in the += form. */
+int FLAGSTATS_hip_device_wide_segments_filter(const void* d_array, uint64_t n, int elem_bytes, const uint64_t* d_offsets,
+                                              uint64_t nseg, uint32_t require, uint32_t exclude, const uint8_t* d_mapq,
+                                              uint32_t min_mapq, uint64_t* d_out, uint64_t* d_selected, uint64_t* d_high,
+                                              int flags, void* stream);
+/* DEVICE array and MAPQ column, HOST offsets, HOST out[nseg][32], selected[nseg] and high[nseg]; synchronous */
+int FLAGSTATS_hip_device_wide_segments_filter_sync(const void* d_array, uint64_t n, int elem_bytes, const uint64_t* offsets,
+                                                   uint64_t nseg, uint32_t require, uint32_t exclude, const uint8_t* d_mapq,
+                                                   uint32_t min_mapq, uint64_t* out, uint64_t* selected, uint64_t* high,
+                                                   int flags);
+/* HOST array, MAPQ column and offsets, HOST out[nseg][32], selected[nseg] and high[nseg]; synchronous.  Only [offsets[0],
+ * offsets[nseg]) of the array and of the column crosses the bus, in the engine's chunks (knob "chunk_flags": chunk_flags * 2
+ * bytes of elements each, a chunk's slice of the column behind them); a segment that spans chunks is summed and ORed on the
+ * device. */
+int FLAGSTATS_hip_wide_x64_segments_filter(const void* array, uint64_t n, int elem_bytes, const uint64_t* offsets, uint64_t nseg,
+                                           uint32_t require, uint32_t exclude, const uint8_t* mapq, uint32_t min_mapq,
+                                           uint64_t* out, uint64_t* selected, uint64_t* high, int flags);
+
 /* 64-bit positional popcount in this library's convention: out[16] += bit counts (host array / device array) */
 int FLAGSTATS_hip_pospopcnt_u16_x64(const uint16_t* array, uint64_t n, uint64_t* out);
 int FLAGSTATS_hip_device_pospopcnt_u16(const uint16_t* d_array, uint64_t n, uint64_t* d_out, void* stream);

@@ -21,7 +21,9 @@ Only what the path needs:
                      reads that pass and the mask of bits seen above bit 15, in one pass
 * ``segments_wide``  rows of counters and one high-bit mask per CSR segment of an int32 / int64 (or 16-bit) array or
                      tensor, in one launch
-* ``dist``           shard + single all-reduce for multi-GPU runs
+* ``segments_wide_filter`` the filter per segment of an int32 / int64 (or 16-bit) array or tensor in place: rows of counters,
+                     the number of reads that pass and one high-bit mask per CSR segment, in one launch
+* ``dist``          shard + single all-reduce for multi-GPU runs
 
 The hot path has no CPU fallback: importing the compute entry points without the
 built extension raises.
@@ -47,6 +49,12 @@ from .segments_wide import (  # noqa: F401
     counters_segments_ints,
     flagstats_segments_ints,
 )
+from .segments_wide_filter import (  # noqa: F401
+    count_segments_device_ptr_ints_filter,
+    count_segments_torch_ints_filter,
+    counters_segments_ints_filter,
+    flagstats_segments_ints_filter,
+)
 from .where import count_device_ptr_where, count_torch_where, counters_where, flagstats_where  # noqa: F401
 from .wide import count_device_ptr_ints, count_torch_ints, counters_ints, flagstats_ints  # noqa: F401
 from .wide_filter import (  # noqa: F401
@@ -62,4 +70,6 @@ __all__ = ["flagstats", "flagstats_x64", "SAM_FLAG_NAMES", "flagstats_segments",
            "count_torch_where", "counters_filter", "flagstats_filter", "count_device_ptr_filter", "count_torch_filter",
            "flagstats_segments_filter", "count_segments_device_ptr_filter", "count_segments_torch_filter", "segment_filter_dicts",
            "counters_ints_filter", "flagstats_ints_filter", "count_device_ptr_ints_filter", "count_torch_ints_filter",
-           "counters_segments_ints", "flagstats_segments_ints", "count_segments_device_ptr_ints", "count_segments_torch_ints"]
+           "counters_segments_ints", "flagstats_segments_ints", "count_segments_device_ptr_ints", "count_segments_torch_ints",
+           "counters_segments_ints_filter", "flagstats_segments_ints_filter", "count_segments_device_ptr_ints_filter",
+           "count_segments_torch_ints_filter"]

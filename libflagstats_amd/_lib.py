@@ -100,6 +100,18 @@ SIGNATURES = {
                                                                ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
     "FLAGSTATS_hip_wide_x64_segments": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    "FLAGSTATS_hip_device_wide_segments_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p,
+                                                                 ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                                                 ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                                 ctypes.c_int, ctypes.c_void_p]),
+    "FLAGSTATS_hip_device_wide_segments_filter_sync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p,
+                                                                      ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                                                      ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                                      ctypes.c_int]),
+    "FLAGSTATS_hip_wide_x64_segments_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p,
+                                                              ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                                              ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                              ctypes.c_int]),
     "FLAGSTATS_hip_available": (ctypes.c_int, []),
     "FLAGSTATS_hip_device_count": (ctypes.c_int, []),
     "FLAGSTATS_hip_ctx_create": (ctypes.c_void_p, [ctypes.c_int]),
@@ -184,7 +196,7 @@ SIGNATURES = {
 }
 
 # internal launchers the tests and tests/perf drive directly (csrc/flagstat_wide.h, csrc/flagstat_where.h, csrc/flagstat_filter.h,
-# csrc/flagstat_segments_filter.h, csrc/flagstat_wide_filter.h, csrc/flagstat_segments_wide.h); not part of the public headers, so kept apart from SIGNATURES, which mirrors those
+# csrc/flagstat_segments_filter.h, csrc/flagstat_wide_filter.h, csrc/flagstat_segments_wide.h, csrc/flagstat_segments_wide_filter.h); not part of the public headers, so kept apart from SIGNATURES, which mirrors those
 INTERNAL_SIGNATURES = {
     "fsk_launch_wide": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                        ctypes.c_uint32, ctypes.c_void_p]),
@@ -203,6 +215,10 @@ INTERNAL_SIGNATURES = {
     "fsk_launch_segments_wide": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
                                                 ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32,
                                                 ctypes.c_void_p]),
+    "fsk_launch_segments_wide_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
+                                                       ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32,
+                                                       ctypes.c_void_p]),
 }
 
 _lib = None

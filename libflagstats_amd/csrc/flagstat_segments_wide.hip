@@ -35,6 +35,7 @@
 #include "flagstat_segments.h"
 #include "flagstat_segments_shared.h"
 #include "flagstat_segments_wide.h"
+#include "flagstat_segments_wide_device.h"
 #include "flagstat_wide_device.h"
 
 namespace fsk {
@@ -52,64 +53,15 @@ __device__ __forceinline__ void segw_step_and_count(Lane<kSegWideDepth>& s, uint
     end_step<kSegWideDepth>(s, blk);
 }
 
-// the elements of vector x (grid positions q .. q + 16 / W - 1) that lie in [b, e); every dword of the others becomes 0
-template <int W>
-__device__ __forceinline__ uint4 mask_vec_wide(uint4 x, uint64_t q, uint64_t b, uint64_t e)
-{
-    constexpr uint32_t EPV = 16 / W;
-    const uint32_t lk = b > q ? static_cast<uint32_t>(b - q < EPV ? b - q : EPV) : 0u;  // first kept element
-    const uint32_t hk = e > q ? static_cast<uint32_t>(e - q < EPV ? e - q : EPV) : 0u;  // one past the last
-    auto keep = [&](uint32_t k) { return k >= lk && k < hk ? 0xFFFFFFFFu : 0u; };
-    if constexpr (W == 4) {
-        x.x &= keep(0);
-        x.y &= keep(1);
-        x.z &= keep(2);
-        x.w &= keep(3);
-    } else {
-        const uint32_t k0 = keep(0), k1 = keep(1);
-        x.x &= k0;
-        x.y &= k0;
-        x.z &= k1;
-        x.w &= k1;
-    }
-    return x;
-}
-
 // the piece [b, e) of the unit starting at grid position w0 (its 8 rows in v[]) into the lane counters and the lane's mask
-// accumulators; only dwords of elements inside the piece reach either
+// accumulators; only dwords of elements inside the piece reach either (count_piece_wide_with of flagstat_segments_wide_device.h,
+// nothing done to the planes)
 template <int W>
 __device__ __forceinline__ void count_piece_wide(uint32_t (&acc)[kInternal], uint32_t& or_even, uint32_t& or_odd, const uint4 (&v)[kUnroll],
                                                  uint64_t w0, uint64_t b, uint64_t e, uint32_t lane)
 {
-    constexpr int RPG = W / 2;                     // rows per count_planes call (8 flags): 2 at W = 4, 4 at W = 8
-    constexpr uint64_t RE = 1024 / W;              // elements per row
-    constexpr uint32_t EPV = 16 / W;
-    constexpr uint32_t sel = 0x05010400u;          // narrow_out's: two flag-carrying dwords a, b -> P = [a.b0, b.b0, a.b1, b.b1]
-#pragma unroll
-    for (int g = 0; g < kUnroll / RPG; ++g) {
-        const uint64_t g0 = w0 + static_cast<uint64_t>(g) * (RPG * RE);
-        if (g0 + RPG * RE <= b || g0 >= e) continue;  // wave-uniform
-        uint32_t P[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int i = 0; i < RPG; ++i) {
-            const uint64_t r0 = g0 + static_cast<uint64_t>(i) * RE;
-            if (r0 + RE <= b || r0 >= e) continue;  // wave-uniform: a row outside the piece counts as zeros
-            uint4 x = v[g * RPG + i];
-            if (r0 < b || r0 + RE > e) x = mask_vec_wide<W>(x, r0 + EPV * lane, b, e);
-            if constexpr (W == 4) {
-                or_even |= x.x | x.y | x.z | x.w;
-                P[2 * i] = perm(x.y, x.x, sel);
-                P[2 * i + 1] = perm(x.w, x.z, sel);
-            } else {
-                or_even |= x.x | x.z;
-                or_odd |= x.y | x.w;
-                P[i] = perm(x.z, x.x, sel);
-            }
-        }
-        const uint32_t L0 = perm(P[1], P[0], 0x05040100u), H0 = perm(P[1], P[0], 0x07060302u);
-        const uint32_t L1 = perm(P[3], P[2], 0x05040100u), H1 = perm(P[3], P[2], 0x07060302u);
-        count_planes(acc, L0, H0, L1, H1);
-    }
+    count_piece_wide_with<W>(acc, or_even, or_odd, v, w0, b, e, lane,
+                             [](int, uint32_t&, uint32_t&, uint32_t&, uint32_t&) __attribute__((always_inline)) {});
 }
 
 // the wave's counters of the piece of segment s it holds -> out[s][32], and the piece's mask -> high[s]

@@ -1,7 +1,8 @@
 // flagstat_wide_device.h -- internal, device code only: what the kernels over 4-byte and 8-byte elements share
-// (flagstat_wide.hip, flagstat_wide_filter.hip, flagstat_segments_wide.hip): the read-out of a loaded vector into the pair dword P
-// and the mask accumulators, the short carry-save tree of a step with 8 or 4 inputs, the unfiltered step built from them (wide_step_with), the
-// guarded loader of an edge step and the OR over a wave.  How the pieces fit is written out at the top of flagstat_wide.hip.
+// (flagstat_wide.hip, flagstat_wide_filter.hip, flagstat_segments_wide.hip, flagstat_segments_wide_filter.hip): the read-out of a
+// loaded vector into the pair dword P and the mask accumulators, the short carry-save tree of a step with 8 or 4 inputs, the
+// unfiltered step built from them (wide_step_with), the guarded loader of an edge step, the zeroing of a vector's elements outside
+// a range and the OR over a wave.  How the pieces fit is written out at the top of flagstat_wide.hip.
 #ifndef FLAGSTAT_WIDE_DEVICE_H_
 #define FLAGSTAT_WIDE_DEVICE_H_
 
@@ -110,6 +111,29 @@ __device__ __forceinline__ uint4 load_guarded_wide(const uint4* __restrict__ a0,
         }
     }
     return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// the elements of vector x (grid positions q .. q + 16 / W - 1) that lie in [b, e); every dword of the others becomes 0
+template <int W>
+__device__ __forceinline__ uint4 mask_vec_wide(uint4 x, uint64_t q, uint64_t b, uint64_t e)
+{
+    constexpr uint32_t EPV = 16 / W;
+    const uint32_t lk = b > q ? static_cast<uint32_t>(b - q < EPV ? b - q : EPV) : 0u;  // first kept element
+    const uint32_t hk = e > q ? static_cast<uint32_t>(e - q < EPV ? e - q : EPV) : 0u;  // one past the last
+    auto keep = [&](uint32_t k) { return k >= lk && k < hk ? 0xFFFFFFFFu : 0u; };
+    if constexpr (W == 4) {
+        x.x &= keep(0);
+        x.y &= keep(1);
+        x.z &= keep(2);
+        x.w &= keep(3);
+    } else {
+        const uint32_t k0 = keep(0), k1 = keep(1);
+        x.x &= k0;
+        x.y &= k0;
+        x.z &= k1;
+        x.w &= k1;
+    }
+    return x;
 }
 
 // OR of x over the 64 lanes of a wave, valid in lane 63 only (the DPP steps of wave_sum_lane63 with | for +; lanes a step does
