@@ -67,7 +67,7 @@ int FLAGSTATS_u16_x64(const uint16_t* array, uint64_t n, uint64_t* out);
  * raised; after either, replaying it touches freed memory -- capture it again instead.
  * Capture and replay are tested (tests/test_gpu_graphs.py, torch.cuda.graph in both capture error modes) for this entry, _store,
  * _superset, device_pospopcnt_u16, device_u16_segments, _where, _filter, _segments_filter, device_wide and device_wide_filter
- * (tests/test_gpu_segments_wide.py: device_wide_segments),
+ * (tests/test_gpu_segments_wide.py: device_wide_segments; tests/test_gpu_segments_where.py: device_u16_segments_where),
  * and for the torch layers on top of them: one call or all of them in one graph, after one plain call on the device (the first
  * call creates the device's engine, which is no stream work).  A captured launch freezes its pointers, n, its grid and the form
  * the knobs chose at capture time (epilogue form, the segments policy); it reads arrays, selections, MAPQ bytes and device
@@ -244,6 +244,44 @@ int FLAGSTATS_hip_device_u16_segments_filter_sync(const uint16_t* d_array, uint6
 int FLAGSTATS_hip_u16_x64_segments_filter(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint64_t nseg,
                                           uint32_t require, uint32_t exclude, const uint8_t* mapq, uint32_t min_mapq,
                                           uint64_t* out, uint64_t* selected, int flags);
+
+/* ================= selected elements per segment: the bitmap or byte mask under CSR segments =================
+ * Per-contig, per-sample, per-read-group or per-block tables over the rows that a mask picks -- an Arrow validity bitmap, the
+ * result of an upstream query, a deduplication or region mask: the segmented entries under the `where` entries' selection, in one
+ * launch, instead of one `where` launch per segment or a compaction in front.  Segment i is [offsets[i], offsets[i+1]) under the
+ * contract of the segmented entries.  The selection is indexed by ARRAY ELEMENT, not by segment: element j of the array is bit
+ * (sel_bits == 1, LSB-first bitmap, any sel_offset) or byte (sel_bits == 8, any non-zero byte selects) sel_offset + j of `sel`,
+ * as in the `where` entries.  Row i of out[nseg][32] holds FLAGSTAT_scalar's counters over {array[j] : j in segment i, sel(j)},
+ * and selected[i] (nseg uint64; the pointer may be NULL: nothing is reported) the number of such j.  Flags outside every segment
+ * count nowhere, selected or not.  Only bytes of `sel` that hold the bit or byte of an element of [0, n) are ever read.
+ * `flags`: bit 0 = store (rows and selected[0 .. nseg) are zeroed in front, every slot of every row and every selected[i] is
+ * written, empty segments and segments with nothing selected read 0) instead of +=; bit 1 = superset (slots 0 / 16 = primary
+ * paired reads among the selected, slot 9 = selected[i] minus slot 25).  nseg == 0 succeeds and touches nothing.
+ * Refused (non-zero, message in FLAGSTATS_hip_last_error, out and selected untouched, nothing launched): sel_bits other than 1 or
+ * 8, flag bits other than 0 and 1, NULL offsets or rows with nseg > 0, a NULL array or selection with n > 0 and nseg > 0, an odd
+ * array pointer, an n with n * 2 not a size, a sel_offset + n that is no index, host offsets that decrease or end beyond n, an nseg
+ * whose rows cannot be allocated, an n too large for a wave's uint32 totals; for the device forms also a d_out or d_selected that
+ * is not plain device memory, pointers on different devices, a stream of another device and an allocation shorter than the call
+ * needs (d_array: n * 2 bytes, d_sel: from d_sel up to the last byte that holds an element's bit or byte, d_offsets:
+ * (nseg + 1) * 8, d_out: nseg * 256, d_selected: nseg * 8).  Device offsets are not checked (that would synchronise): every
+ * offset the kernel reads is clamped to [0, n], so bad offsets give undefined counters and never an access outside the array,
+ * the selection's bytes of elements, the rows or the counts. */
+/* DEVICE array, selection and offsets, DEVICE d_out[nseg][32] and d_selected[nseg] (uint64); asynchronous on `stream`: ONE kernel
+ * (the store form puts one memset per pointer in front of it), no workspace, so a captured launch holds no pointer of the
+ * library's; make one plain call before capturing.  Adds are atomic: launches on several streams may share d_out and
+ * d_selected in the += form. */
+int FLAGSTATS_hip_device_u16_segments_where(const uint16_t* d_array, uint64_t n, const uint64_t* d_offsets, uint64_t nseg,
+                                            const void* d_sel, uint64_t sel_offset, int sel_bits, uint64_t* d_out,
+                                            uint64_t* d_selected, int flags, void* stream);
+/* DEVICE array and selection, HOST offsets, HOST out[nseg][32] and selected[nseg]; synchronous */
+int FLAGSTATS_hip_device_u16_segments_where_sync(const uint16_t* d_array, uint64_t n, const uint64_t* offsets, uint64_t nseg,
+                                                 const void* d_sel, uint64_t sel_offset, int sel_bits, uint64_t* out,
+                                                 uint64_t* selected, int flags);
+/* HOST array, selection and offsets, HOST out[nseg][32] and selected[nseg]; synchronous.  Only [offsets[0], offsets[nseg]) of the
+ * array and the selection bytes that cover it cross the bus, in the engine's chunks (knob "chunk_flags"), each chunk's slice of
+ * the selection behind its flags; a segment that spans chunks is summed on the device. */
+int FLAGSTATS_hip_u16_x64_segments_where(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint64_t nseg, const void* sel,
+                                         uint64_t sel_offset, int sel_bits, uint64_t* out, uint64_t* selected, int flags);
 
 /* ================= filtered wide input: -f / -F / -q on a FLAG column held as 4-byte or 8-byte integers =================
  * The two normal cases at once: the column arrives as int32 or int64 (the wide entries) and the table wanted is that of

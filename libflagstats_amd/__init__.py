@@ -17,6 +17,8 @@ Only what the path needs:
                      (FLAG bits required and excluded, a MAPQ threshold), with no mask array
 * ``segments_filter`` the filter per segment: rows of counters and the number of reads that pass, for
                      every CSR segment in one launch
+* ``segments_where`` the mask or bitmap per segment: rows of counters and the number of selected reads, for every CSR
+                     segment in one launch (the selection is indexed by array element)
 * ``wide_filter``    the filter on int32 / int64 (and 16-bit) arrays and tensors in place: counters, the number of
                      reads that pass and the mask of bits seen above bit 15, in one pass
 * ``segments_wide``  rows of counters and one high-bit mask per CSR segment of an int32 / int64 (or 16-bit) array or
@@ -55,6 +57,12 @@ from .segments_wide_filter import (  # noqa: F401
     counters_segments_ints_filter,
     flagstats_segments_ints_filter,
 )
+from .segments_where import (  # noqa: F401
+    count_segments_device_ptr_where,
+    count_segments_torch_where,
+    counters_segments_where,
+    flagstats_segments_where,
+)
 from .where import count_device_ptr_where, count_torch_where, counters_where, flagstats_where  # noqa: F401
 from .wide import count_device_ptr_ints, count_torch_ints, counters_ints, flagstats_ints  # noqa: F401
 from .wide_filter import (  # noqa: F401
@@ -72,4 +80,5 @@ __all__ = ["flagstats", "flagstats_x64", "SAM_FLAG_NAMES", "flagstats_segments",
            "counters_ints_filter", "flagstats_ints_filter", "count_device_ptr_ints_filter", "count_torch_ints_filter",
            "counters_segments_ints", "flagstats_segments_ints", "count_segments_device_ptr_ints", "count_segments_torch_ints",
            "counters_segments_ints_filter", "flagstats_segments_ints_filter", "count_segments_device_ptr_ints_filter",
-           "count_segments_torch_ints_filter"]
+           "count_segments_torch_ints_filter", "counters_segments_where", "flagstats_segments_where",
+           "count_segments_device_ptr_where", "count_segments_torch_where"]

@@ -41,7 +41,6 @@
 
 namespace fsk {
 
-constexpr int kSegFilterDepth = 8;                 // chain depth as K1: epochs of 255 units
 constexpr int kSegRowBytes = kSegRowVecs * 8;      // MAPQ bytes of a row
 
 // K1's step at the default schedule over one unit, the predicate applied in the per-vector front: vector u's registers and its
@@ -101,41 +100,6 @@ __device__ __forceinline__ void count_piece_filter(uint32_t (&acc)[kInternal], u
         H1 &= M1;
         count_planes(acc, L0, H0, L1, H1);
     }
-}
-
-// the wave's counters of the piece of segment s it holds -> out[s][32], and its passing count -> selected[s]
-__device__ __forceinline__ void segf_emit(Lane<kSegFilterDepth>& st, uint32_t& blk, uint32_t& cnt, uint32_t* red, uint64_t* __restrict__ out,
-                                          uint64_t* __restrict__ selected, uint64_t s, bool plain, int mode, uint32_t lane)
-{
-    if (blk) {
-        flush(st, blk);
-        blk = 0;
-    }
-    uint32_t w[kInternal + 1];
-#pragma unroll
-    for (int c = 0; c < kInternal; ++c) {
-        w[c] = wave_sum_lane63(st.acc[c]);
-        st.acc[c] = 0;
-    }
-    w[kInternal] = wave_sum_lane63(cnt);
-    cnt = 0;
-    if (lane == 63) {
-#pragma unroll
-        for (int c = 0; c <= kInternal; ++c) red[c] = w[c];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (lane < 32 || (lane == 32 && selected != nullptr)) {
-        const uint64_t passing = red[kInternal];
-        const uint64_t add = lane < 32 ? seg_slot_value(red, lane, mode, passing) : passing;
-        uint64_t* o = lane < 32 ? out + s * 32 + lane : selected + s;
-        if (plain)
-            *o = add;  // store form, the whole segment in this wave: all 32 slots and the count
-        else if (add)
-            (void)__hip_atomic_fetch_add(o, add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __builtin_amdgcn_wave_barrier();  // red[] is rewritten by the next segment's totals only after every lane has read it
 }
 
 // a0: 16-B aligned-down base; the chunk's flags occupy grid positions [lo0, hi0) and are global flags [base, base + hi0 - lo0).
@@ -282,25 +246,8 @@ __global__ __launch_bounds__(kThreads) void flagstat_segments_filter(const uint4
 }  // namespace fsk
 
 // ------------------------------------------------------------------ launcher
-namespace {
-
-// a wave's totals are uint32: every wave must own fewer than 2^32 flags
-bool wave_totals_fit(uint64_t nunits, uint32_t g)
-{
-    const uint64_t waves = static_cast<uint64_t>(g) * (fsk::kThreads / 64);
-    return (nunits + waves - 1) / waves < (1ull << 32) / fsk::kSegWaveFlags;
-}
-
-// units and workgroups of a launch over m > 0 flags at `addr` with at most `grid` workgroups
-void launch_shape(uintptr_t addr, uint64_t m, uint32_t grid, uint64_t* lo0, uint64_t* nunits, uint32_t* g)
-{
-    *lo0 = (addr & 15u) / 2;
-    *nunits = (*lo0 + m + fsk::kSegWaveFlags - 1) / fsk::kSegWaveFlags;
-    const uint64_t want = (*nunits + 3) / 4;  // one unit per wave at least
-    *g = want < grid ? static_cast<uint32_t>(want) : grid;
-}
-
-}  // namespace
+using fsseg::launch_shape;
+using fsseg::wave_totals_fit;
 
 extern "C" hipError_t fsk_launch_segments_filter(const uint16_t* d_chunk, const uint8_t* d_mapq_chunk, uint64_t base, uint64_t m,
                                                  const uint64_t* d_offsets, uint64_t nseg, uint32_t require, uint32_t exclude,
@@ -347,6 +294,7 @@ extern "C" hipError_t fsk_launch_segments_filter(const uint16_t* d_chunk, const 
 using fsint::DeviceGuard;
 using fsint::Engine;
 using fsint::fail_text;
+using fsseg::apply_both;
 using fsseg::seg_grid;
 
 namespace {
@@ -378,13 +326,6 @@ int segf_fits(const uint16_t* array, uint64_t n, uint32_t grid)
     if (!wave_totals_fit(nunits, g))
         return fail_text("n is too large for this grid: a wave's uint32 totals could overflow (split the array)");
     return 0;
-}
-
-// rows, then selected counts, of a synchronous call into the caller's host words
-void apply_both(uint64_t* out, uint64_t* selected, const fsseg::HostRows& got, uint64_t nseg, int flags)
-{
-    fsseg::apply(out, got.p.get(), nseg * 32, flags);
-    if (selected) fsseg::apply(selected, got.p.get() + nseg * 32, nseg, flags);
 }
 
 }  // namespace

@@ -22,6 +22,7 @@ namespace fsk {
 
 constexpr int kSegRowVecs = 64;                    // vectors per row (one per lane)
 constexpr int kSegUnitVecs = kSegWaveFlags / 8;    // 512 vectors per unit
+constexpr int kSegFilterDepth = 8;                 // chain depth of the selecting kernels, as K1: epochs of 255 units
 
 // Per-flag form: 8 flags on their byte planes (L: FLAG bits 0-7, H: bits 8-15; 4 flags per dword) straight into the 21 lane
 // counters (T bits 0-7, F bits 0-7, S bits 0-2 and 6-7).
@@ -70,6 +71,42 @@ __device__ __forceinline__ uint64_t seg_slot_value(const uint32_t* tot, uint32_t
         if (slot == 9 && !fail) add = len - (static_cast<uint64_t>(tot[16]) + tot[18]);
     }
     return add;
+}
+
+// the selecting kernels (flagstat_segments_filter.hip, flagstat_segments_where.hip): the wave's counters of the piece of segment s
+// it holds -> out[s][32], and its passing (selected) count -> selected[s]
+__device__ __forceinline__ void segf_emit(Lane<kSegFilterDepth>& st, uint32_t& blk, uint32_t& cnt, uint32_t* red, uint64_t* __restrict__ out,
+                                          uint64_t* __restrict__ selected, uint64_t s, bool plain, int mode, uint32_t lane)
+{
+    if (blk) {
+        flush(st, blk);
+        blk = 0;
+    }
+    uint32_t w[kInternal + 1];
+#pragma unroll
+    for (int c = 0; c < kInternal; ++c) {
+        w[c] = wave_sum_lane63(st.acc[c]);
+        st.acc[c] = 0;
+    }
+    w[kInternal] = wave_sum_lane63(cnt);
+    cnt = 0;
+    if (lane == 63) {
+#pragma unroll
+        for (int c = 0; c <= kInternal; ++c) red[c] = w[c];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane < 32 || (lane == 32 && selected != nullptr)) {
+        const uint64_t passing = red[kInternal];
+        const uint64_t add = lane < 32 ? seg_slot_value(red, lane, mode, passing) : passing;
+        uint64_t* o = lane < 32 ? out + s * 32 + lane : selected + s;
+        if (plain)
+            *o = add;  // store form, the whole segment in this wave: all 32 slots and the count
+        else if (add)
+            (void)__hip_atomic_fetch_add(o, add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __builtin_amdgcn_wave_barrier();  // red[] is rewritten by the next segment's totals only after every lane has read it
 }
 
 // grid position of offset i: clamped to the chunk [base, base + m]
@@ -237,6 +274,29 @@ inline void apply(uint64_t* out, const uint64_t* got, uint64_t words, int flags)
         std::memcpy(out, got, words * sizeof(uint64_t));
     else
         for (uint64_t i = 0; i < words; ++i) out[i] += got[i];
+}
+
+// rows, then selected counts, of a synchronous call into the caller's host words
+inline void apply_both(uint64_t* out, uint64_t* selected, const fsseg::HostRows& got, uint64_t nseg, int flags)
+{
+    fsseg::apply(out, got.p.get(), nseg * 32, flags);
+    if (selected) fsseg::apply(selected, got.p.get() + nseg * 32, nseg, flags);
+}
+
+// a wave's totals are uint32: every wave must own fewer than 2^32 flags
+inline bool wave_totals_fit(uint64_t nunits, uint32_t g)
+{
+    const uint64_t waves = static_cast<uint64_t>(g) * (fsk::kThreads / 64);
+    return (nunits + waves - 1) / waves < (1ull << 32) / fsk::kSegWaveFlags;
+}
+
+// units and workgroups of a launch over m > 0 uint16 flags at `addr` with at most `grid` workgroups
+inline void launch_shape(uintptr_t addr, uint64_t m, uint32_t grid, uint64_t* lo0, uint64_t* nunits, uint32_t* g)
+{
+    *lo0 = (addr & 15u) / 2;
+    *nunits = (*lo0 + m + fsk::kSegWaveFlags - 1) / fsk::kSegWaveFlags;
+    const uint64_t want = (*nunits + 3) / 4;  // one unit per wave at least
+    *g = want < grid ? static_cast<uint32_t>(want) : grid;
 }
 
 }  // namespace fsseg

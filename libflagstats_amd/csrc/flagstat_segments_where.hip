@@ -1,0 +1,487 @@
+// flagstat_segments_where.hip -- selected-elements segmented flagstat: per CSR segment of a uint16 FLAG array, the 32 counters of
+// the flags that a selection picks and how many it picks, in one launch.  The selection is indexed by ARRAY ELEMENT, under the two
+// encodings of the `where` entries: an LSB-first bitmap (Arrow's validity layout) that may start at any bit, or one byte per
+// element (any non-zero byte selects).
+// The segmented kernel (flagstat_segments.hip) with the `where` kernel's bitmap selection (flagstat_where.hip) in front of the
+// count.
+//
+// Byte form: no kernel of its own.  pass4<true> (flagstat_filter_device.h) with require == exclude == 0 and min_mapq == 1 is
+// exactly "any non-zero byte selects": the FLAG test passes every flag (x1 == x2 == 0, bit 7 of q stays clear), and of the MAPQ
+// test bit 7 of a byte is w7 | t2_7 (k == 0x80808080 turns the majority into an OR) with t2 = (w | 0x80) - 1: byte 0 gives 0x7F
+// and has bit 7 clear in both; bytes 1..127 set bit 7 of t2; bytes 128..255 set bit 7 of w.  So the launcher hands the mask,
+// from the byte of the chunk's element 0 on, to fsk::flagstat_segments_filter<true> as its MAPQ column
+// (fsk_launch_segments_filter), whose loaders touch only bytes of elements.
+//
+// Work split, walk, window and emission.  The segmented kernels', unchanged (tests/segments_oracle.WriterSplit mirrors them):
+// units of 4096 flags on the 16-byte grid of the array's aligned-down base, every wave a writer over a contiguous run of units,
+// lane l of a row takes vector row * 64 + l, the 64-ary search for a writer's first segment, the window of 64 offsets, plain
+// stores in the store form for rows that lie inside one writer (flagstat_segments_shared.h; the emission is segf_emit's).
+//
+// Selection.  Addressed like the `where` kernel's: the launcher hands over a base `sel` such that the 8 bits of grid vector j
+// start at bit `sh` of sel[j] (sh == 0: one byte per vector; otherwise two bytes funnelled together: FUNNEL).  A zero flag
+// counts in no slot, so selecting is zeroing the flags that are not selected: the 256-entry table in LDS maps 8 selection bits
+// to the four v_perm_b32 selectors of the split with 0x0C (-> 0x00) for every flag not selected (flagstat_where_device.h).
+//   * chain regime (a run of at least `min_units` whole units in one segment): K1's tree_step / end_step with the `where`
+//     kernel's front: split_out_selected under the table entry, the entry of the next vector looked up (and its popcount added
+//     to the 22nd lane counter) while this one is counted, the selection byte of a vector issued one vector ahead of it through
+//     reissue.  Every position of such a unit is an element of the segment.  The entry carried between steps is primed from the
+//     run's first vector every time the walk enters a chain run: after a per-flag unit or a skipped stretch nothing is carried.
+//   * per-flag regime: the unit's 8 rows and their 8 selection bytes are loaded at once (through guarded loaders that read only
+//     bytes holding a bit of [lo0, hi0) when the unit is the array's ragged first or last) and brought to bit 0.  Per piece and
+//     row the selection bits are ANDed with the piece's valid_bits; the result is the table index (one ds_read_b128 and no VALU
+//     op, against 10 VALU ops for two nibble_mask and four ANDs) that zeroes the flags in front of count_planes, and its
+//     popcount is the selected count.  A selected element of a neighbouring segment, of a gap or of the bytes around the array
+//     is cleared there and counts nowhere.
+// The table is built by the workgroup's 256 threads and the barrier behind it is passed before any wave returns early.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <mutex>
+
+#include "../../include/libflagstats_hip.h"
+#include "flagstat_count_core.h"
+#include "flagstat_derived_host.h"
+#include "flagstat_engine.h"
+#include "flagstat_filter_device.h"
+#include "flagstat_segments.h"
+#include "flagstat_segments_filter.h"
+#include "flagstat_segments_shared.h"
+#include "flagstat_segments_where.h"
+#include "flagstat_where.h"
+#include "flagstat_where_device.h"
+
+namespace fsk {
+
+// K1's step at the default schedule over one unit, the bitmap's selection applied in the split: `entry` is the table entry of
+// the vector counted next (on entry: vector 0's; on exit, HAS_NEXT: the next unit's vector 0's).  Vector u's registers are
+// re-issued for vector u + 6 of the same unit (`cur`) or u - 2 of the next (`next`), its selection byte one vector further on.
+template <bool FUNNEL, bool HAS_NEXT>
+__device__ __forceinline__ void segw_step_and_count(Lane<kSegFilterDepth>& s, uint4 (&v)[kUnroll], uint32_t (&m)[kUnroll], uint4& entry,
+                                                    const uint4* __restrict__ lut, uint32_t& blk, uint32_t sh, uint32_t& cnt,
+                                                    const uint4* cur, const uint4* next, const uint8_t* scur, const uint8_t* snext)
+{
+    constexpr int ROLL = HAS_NEXT ? 1 : 2;
+    blk = __builtin_amdgcn_readfirstlane(blk);
+    tree_step<kSegFilterDepth>(s, blk, [&](int uu, uint32_t& L0, uint32_t& H0, uint32_t& L1, uint32_t& H1) __attribute__((always_inline)) {
+        __builtin_amdgcn_sched_barrier(0);
+        split_out_selected(v[uu], entry, L0, H0, L1, H1);
+        if (uu + 1 < kUnroll || HAS_NEXT) entry = lookup(lut, m[(uu + 1) % kUnroll], sh, cnt);
+        reissue<ROLL, 1>(uu, m, scur, snext, kSegRowVecs, load_sel<1, FUNNEL>);
+        reissue<ROLL>(uu, v, cur, next, kSegRowVecs, load_vec<true>);
+        __builtin_amdgcn_sched_barrier(0);
+    });
+    end_step<kSegFilterDepth>(s, blk);
+}
+
+// the selected flags of the piece [b, e), out of the unit starting at grid position w0 (its 8 rows in v[], their selection bits
+// at bit 0 of m[]), into the lane counters and the lane's selected count
+__device__ __forceinline__ void count_piece_where(uint32_t (&acc)[kInternal], uint32_t& cnt, const uint4* __restrict__ lut,
+                                                  const uint4 (&v)[kUnroll], const uint32_t (&m)[kUnroll], uint64_t w0, uint64_t b,
+                                                  uint64_t e, uint32_t lane)
+{
+#pragma unroll
+    for (int r = 0; r < kUnroll; ++r) {
+        const uint64_t r0 = w0 + static_cast<uint64_t>(r) * 512u;
+        if (r0 + 512u <= b || r0 >= e) continue;  // wave-uniform
+        uint32_t vb = 0xFFu;                      // bit k: flag k of this lane's vector lies in the piece
+        if (r0 < b || r0 + 512u > e) vb = valid_bits(r0 / 8u + lane, b, e);
+        const uint32_t bits = m[r] & vb;          // ... and is selected
+        cnt += __builtin_popcount(bits);
+        const uint4 entry = lut[bits];
+        uint32_t L0, H0, L1, H1;
+        split_out_selected(v[r], entry, L0, H0, L1, H1);
+        count_planes(acc, L0, H0, L1, H1);
+    }
+}
+
+// a0: 16-B aligned-down base; the chunk's flags occupy grid positions [lo0, hi0) and are global flags [base, base + hi0 - lo0).
+// sel, shift: the chunk's selection on the same grid (the 8 bits of grid vector j start at bit `shift` of sel[j]; FUNNEL:
+// shift != 0).  nunits = ceil(hi0 / 4096).  mode: bit 0 store form (out[] and selected[] zeroed in front), bit 1 superset.
+// selected may be nullptr.
+template <bool FUNNEL>
+__global__ __launch_bounds__(kThreads) void flagstat_segments_where(const uint4* __restrict__ a0, const uint8_t* __restrict__ sel,
+                                                                    uint32_t shift, uint64_t lo0, uint64_t hi0, uint64_t base,
+                                                                    const uint64_t* __restrict__ off, uint64_t nseg,
+                                                                    uint64_t* __restrict__ out, uint64_t* __restrict__ selected, int mode,
+                                                                    uint64_t nunits, uint32_t min_units)
+{
+    static_assert(kThreads == 256, "one thread per table entry");
+    __shared__ uint4 lut[256];
+    __shared__ uint32_t red_all[kThreads / 64][24];
+    lut[threadIdx.x] = selector_entry(threadIdx.x);
+    __syncthreads();  // the only workgroup barrier: behind it waves return and walk on their own
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = threadIdx.x >> 6;
+    const uint64_t waves = static_cast<uint64_t>(gridDim.x) * (kThreads / 64);
+    const uint64_t gw = static_cast<uint64_t>(blockIdx.x) * (kThreads / 64) + wave;
+    const uint64_t u_begin = gw * nunits / waves, u_end = (gw + 1) * nunits / waves;
+    const uint64_t p0 = u_begin * kSegWaveFlags > lo0 ? u_begin * kSegWaveFlags : lo0;  // this writer: grid positions [p0, E)
+    const uint64_t E = u_end * kSegWaveFlags < hi0 ? u_end * kSegWaveFlags : hi0;
+    if (p0 >= E) return;
+    uint32_t* red = red_all[wave];
+
+    SegWalk sw{off, nseg, base, hi0 - lo0, lo0, lane, 0, 0, 0};
+    uint64_t s = sw.first_segment(p0);
+    if (s >= nseg) return;
+    sw.load_window(s);
+
+    const uint32_t sh = FUNNEL ? __builtin_amdgcn_readfirstlane(shift) : 0u;
+    Lane<kSegFilterDepth> st;
+    lane_init(st);
+    uint32_t blk = 0;
+    uint32_t cnt = 0;   // selected flags of this lane in segment s not yet emitted
+    bool open = false;  // st and cnt hold counts of segment s not yet emitted
+    uint64_t sb = 0, se = 0;
+    auto emit = [&](uint64_t seg, uint64_t b_, uint64_t e_) {
+        segf_emit(st, blk, cnt, red, out, selected, seg, (mode & 1) && b_ >= p0 && e_ <= E, mode, lane);
+    };
+
+    uint64_t u = p0 / kSegWaveFlags;
+    while (s < nseg && u < u_end) {
+        sw.bounds(s, sb, se);
+        const uint64_t w0 = u * kSegWaveFlags;
+        const uint64_t x = w0 > p0 ? w0 : p0;
+        // (the order of these tests: flagstat_segments_filter.hip)
+        if (sb >= E) break;
+        if (se <= sb || se <= x) {  // empty (or, with malformed offsets, reversed or behind)
+            ++s;
+            continue;
+        }
+        if (sb >= w0 + kSegWaveFlags) {  // flags before the segment belong to none: skip whole units unread
+            u = sb / kSegWaveFlags;
+            continue;
+        }
+        const uint64_t seg_e = se < E ? se : E;
+        if (sb <= w0 && w0 >= lo0) {
+            const uint64_t k = (seg_e - w0) / kSegWaveFlags;  // whole units of segment s from here on
+            if (k >= min_units && k > 0) {
+                const uint4* p = a0 + u * kSegUnitVecs + lane;
+                const uint8_t* ps = sel + u * kSegUnitVecs + lane;
+                uint4 v[kUnroll];
+                uint32_t m[kUnroll];
+                // the first kRollDistance vectors, the selection bytes one vector ahead of them
+                m[0] = load_sel<1, FUNNEL>(ps);
+#pragma unroll
+                for (int r = 0; r < kRollDistance; ++r) {
+                    m[r + 1] = load_sel<1, FUNNEL>(ps + (r + 1) * kSegRowVecs);
+                    v[r] = load_vec<true>(p + r * kSegRowVecs);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                // entering a chain run: whatever came before (a per-flag unit, a skipped stretch, another run) left no entry
+                uint4 entry = lookup(lut, m[0], sh, cnt);
+                for (uint64_t i = 1; i < k; ++i) {
+                    const uint4* pn = p + kSegUnitVecs;
+                    const uint8_t* psn = ps + kSegUnitVecs;
+                    segw_step_and_count<FUNNEL, true>(st, v, m, entry, lut, blk, sh, cnt, p, pn, ps, psn);
+                    p = pn;
+                    ps = psn;
+                }
+                segw_step_and_count<FUNNEL, false>(st, v, m, entry, lut, blk, sh, cnt, p, nullptr, ps, nullptr);
+                u += k;
+                open = true;
+                if (u * kSegWaveFlags >= se) {
+                    emit(s, sb, se);
+                    open = false;
+                    ++s;
+                }
+                continue;
+            }
+        }
+        // per-flag unit: its 8 rows and their selection bits loaded at once, then every segment piece in it
+        uint4 v[kUnroll];
+        uint32_t m[kUnroll];
+        const uint64_t j0 = u * kSegUnitVecs + lane;
+        if (w0 >= lo0 && w0 + kSegWaveFlags <= hi0) {
+#pragma unroll
+            for (int r = 0; r < kUnroll; ++r) {
+                v[r] = load_vec<true>(a0 + j0 + r * kSegRowVecs);
+                m[r] = __builtin_amdgcn_ubfe(load_sel<1, FUNNEL>(sel + j0 + r * kSegRowVecs), sh, 8);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < kUnroll; ++r) {
+                v[r] = load_guarded(a0, j0 + r * kSegRowVecs, lo0, hi0);
+                m[r] = load_sel_guarded<1>(sel, sh, j0 + r * kSegRowVecs, lo0, hi0);
+            }
+        }
+        const uint64_t w1 = w0 + kSegWaveFlags;
+        uint64_t xx = x;
+        for (;;) {
+            // s < nseg, sb < se, se > xx, sb < w1; the piece [b, e) lies inside [p0, E) and so inside [lo0, hi0)
+            const uint64_t b = sb > xx ? sb : xx, e = se < w1 ? se : w1;
+            count_piece_where(st.acc, cnt, lut, v, m, w0, b, e, lane);
+            open = true;
+            if (e < se) break;  // segment s goes on in the next unit
+            emit(s, sb, se);
+            open = false;
+            ++s;
+            xx = e;
+            bool more = false;
+            while (s < nseg) {
+                sw.bounds(s, sb, se);
+                if (sb >= E) break;  // (as in the outer walk: before the empty test)
+                if (se <= sb || se <= xx) {
+                    ++s;
+                    continue;
+                }
+                more = sb < w1;
+                break;
+            }
+            if (!more) break;
+        }
+        ++u;
+    }
+    if (open) emit(s, sb, se);  // this writer's range ends inside segment s
+}
+
+}  // namespace fsk
+
+// ------------------------------------------------------------------ launcher
+using fsdrv::where_extent;
+using fsseg::launch_shape;
+using fsseg::wave_totals_fit;
+
+// Host-side geometry.  Grid position q is element q - lo0 of the chunk and so bit or byte sel_offset + q - lo0 of d_sel.
+// Bytes: that is base[q] with base = d_sel + sel_offset - lo0.  Bitmap: bit q + (bit0 - 8) with bit0 = sel_offset + 8 - lo0 >= 1,
+// so the 8 bits of grid vector j start at bit bit0 & 7 of byte j of base = d_sel + (bit0 >> 3) - 1 (fsk_launch_where's
+// arithmetic with lo0 for lo; the chunk's position in the array is folded into sel_offset by the caller).
+extern "C" hipError_t fsk_segments_where_geometry(uint64_t address, uint64_t m, uint64_t sel_offset, int sel_bits, uint32_t grid,
+                                                  uint64_t* geo)
+{
+    if ((sel_bits != 1 && sel_bits != 8) || grid == 0 || geo == nullptr) return hipErrorInvalidValue;
+    for (int i = 0; i < 7; ++i) geo[i] = 0;
+    if ((address & 1u) || m > (~0ull - 64) / 2) return hipErrorInvalidValue;
+    if (m == 0) return hipSuccess;
+    if (sel_offset > ~0ull - 64 - m) return hipErrorInvalidValue;  // sel_offset + m must be an index
+    uint64_t lo0 = 0, nunits = 0;
+    uint32_t g = 0;
+    launch_shape(static_cast<uintptr_t>(address), m, grid, &lo0, &nunits, &g);
+    if (!wave_totals_fit(nunits, g)) return hipErrorInvalidValue;
+    uint64_t first, bytes;
+    where_extent(m, sel_offset, sel_bits, &first, &bytes);
+    geo[0] = lo0;
+    geo[1] = nunits;
+    geo[2] = g;
+    if (sel_bits == 8) {
+        geo[3] = sel_offset - lo0;
+        geo[4] = 0;
+    } else {
+        const uint64_t bit0 = sel_offset + 8 - lo0;
+        geo[3] = (bit0 >> 3) - 1;
+        geo[4] = bit0 & 7;
+    }
+    geo[5] = first;
+    geo[6] = first + bytes;
+    return hipSuccess;
+}
+
+extern "C" hipError_t fsk_launch_segments_where(const uint16_t* d_chunk, const void* d_sel, uint64_t sel_offset, int sel_bits,
+                                                uint64_t base, uint64_t m, const uint64_t* d_offsets, uint64_t nseg, uint64_t* d_out,
+                                                uint64_t* d_selected, int mode, uint32_t grid, hipStream_t stream)
+{
+    if ((sel_bits != 1 && sel_bits != 8) || (mode & ~3) || grid == 0) return hipErrorInvalidValue;
+    if (nseg == 0) return hipSuccess;
+    if (d_out == nullptr || d_offsets == nullptr || (m && (d_chunk == nullptr || d_sel == nullptr))) return hipErrorInvalidValue;
+    const uintptr_t addr = reinterpret_cast<uintptr_t>(d_chunk);
+    uint64_t geo[7];
+    hipError_t e = fsk_segments_where_geometry(addr, m, sel_offset, sel_bits, grid, geo);
+    if (e != hipSuccess) return e;
+    if (sel_bits == 8)  // the mask is the filtered kernel's MAPQ column (see the top), which that launcher takes from element 0 on
+        return fsk_launch_segments_filter(d_chunk, static_cast<const uint8_t*>(d_sel) + sel_offset, base, m, d_offsets, nseg, 0u, 0u, 1u,
+                                          d_out, d_selected, mode, grid, stream);
+    const uint8_t* sel = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(d_sel) + geo[3]);
+    if (mode & 1) {
+        e = fsk_zero_words(d_out, nseg * 32, stream);
+        if (e == hipSuccess && d_selected) e = fsk_zero_words(d_selected, nseg, stream);
+        if (e != hipSuccess) return e;
+    }
+    if (m == 0) return hipSuccess;
+    const uint4* a0 = reinterpret_cast<const uint4*>(addr & ~static_cast<uintptr_t>(15));
+    const uint64_t lo0 = geo[0], hi0 = lo0 + m, nunits = geo[1];
+    const uint32_t shift = static_cast<uint32_t>(geo[4]);
+    uint32_t min_units = 0, blocks_per_cu = 0;
+    fsk_segments_policy(&min_units, &blocks_per_cu);
+    const dim3 gd(static_cast<uint32_t>(geo[2])), bd(fsk::kThreads);
+    if (shift == 0)
+        hipLaunchKernelGGL((fsk::flagstat_segments_where<false>), gd, bd, 0, stream, a0, sel, 0u, lo0, hi0, base, d_offsets, nseg, d_out,
+                           d_selected, mode & 3, nunits, min_units);
+    else
+        hipLaunchKernelGGL((fsk::flagstat_segments_where<true>), gd, bd, 0, stream, a0, sel, shift, lo0, hi0, base, d_offsets, nseg, d_out,
+                           d_selected, mode & 3, nunits, min_units);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ C entry points (include/libflagstats_hip.h)
+using fsint::DeviceGuard;
+using fsint::Engine;
+using fsint::fail_text;
+using fsseg::apply_both;
+using fsseg::seg_grid;
+
+namespace {
+
+// what every form refuses before it touches the GPU (nseg > 0 from the NULL checks on): segf_args' and where_args' refusals
+int segw_args(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint64_t nseg, const void* sel, uint64_t sel_offset, int sel_bits,
+              const void* out, int flags, const char* null_text)
+{
+    if (sel_bits != 1 && sel_bits != 8) return fail_text("sel_bits must be 1 (an LSB-first bitmap) or 8 (one byte per element)");
+    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
+    if (nseg == 0) return 0;
+    if (!offsets || !out) return fail_text(null_text);
+    if (nseg > fsseg::kMaxSegments / 2) return fail_text("nseg is too large: its counters cannot be allocated");   // 33 words each
+    if (n && !array) return fail_text("NULL array with n > 0");
+    if (n && !sel) return fail_text("NULL selection with n > 0");
+    if (reinterpret_cast<uintptr_t>(array) & 1u) return fail_text("array must be 2-byte aligned");
+    if (n > (~0ull - 64) / 2) return fail_text("n * 2 is not a size");
+    if (sel_offset > ~0ull - 64 - n) return fail_text("sel_offset + n is not an index");
+    return 0;
+}
+
+int segw_fits(const uint16_t* array, uint64_t n, uint32_t grid)
+{
+    if (n == 0) return 0;
+    uint64_t lo0 = 0, nunits = 0;
+    uint32_t g = 0;
+    launch_shape(reinterpret_cast<uintptr_t>(array), n, grid, &lo0, &nunits, &g);
+    if (!wave_totals_fit(nunits, g))
+        return fail_text("n is too large for this grid: a wave's uint32 totals could overflow (split the array)");
+    return 0;
+}
+
+// the bytes of d_sel a call over the whole array needs, from d_sel itself on (n > 0)
+uint64_t sel_bytes(uint64_t n, uint64_t sel_offset, int sel_bits)
+{
+    uint64_t first = 0, bytes = 0;
+    where_extent(n, sel_offset, sel_bits, &first, &bytes);
+    return first + bytes;
+}
+
+}  // namespace
+
+extern "C" {
+
+int FLAGSTATS_hip_device_u16_segments_where(const uint16_t* d_array, uint64_t n, const uint64_t* d_offsets, uint64_t nseg,
+                                            const void* d_sel, uint64_t sel_offset, int sel_bits, uint64_t* d_out, uint64_t* d_selected,
+                                            int flags, void* stream)
+{
+    FS_ENTRY();
+    int rc = segw_args(d_array, n, d_offsets, nseg, d_sel, sel_offset, sel_bits, d_out, flags, "NULL d_offsets or d_out with nseg > 0");
+    if (rc || nseg == 0) return rc;
+    const fsdrv::DeviceWord word{d_selected, "d_selected", "the counts are added with device atomics"};
+    const fsdrv::Input in[] = {{d_offsets, "d_offsets", (nseg + 1) * sizeof(uint64_t)},
+                               {d_array, "d_array", n * 2},
+                               {d_sel, "d_sel", n ? sel_bytes(n, sel_offset, sel_bits) : 0}};
+    const int inputs = n ? 3 : 1;
+    fsdrv::DeviceCall call;
+    if ((rc = call.open(d_out, word, in, inputs, stream))) return rc;
+    const uint32_t grid = seg_grid(*call.e);
+    if ((rc = segw_fits(d_array, n, grid))) return rc;
+    if ((rc = fsint::check_extent(d_out, nseg * 32 * sizeof(uint64_t), "d_out"))) return rc;
+    if (d_selected && (rc = fsint::check_extent(d_selected, nseg * sizeof(uint64_t), "d_selected"))) return rc;
+    for (int i = 0; i < inputs; ++i)
+        if ((rc = fsint::check_extent(in[i].p, in[i].bytes, in[i].name))) return rc;
+    FS_HIP_TRY(fsk_launch_segments_where(d_array, d_sel, sel_offset, sel_bits, 0, n, d_offsets, nseg, d_out, d_selected, flags & 3, grid,
+                                         call.s));
+    return 0;
+}
+
+int FLAGSTATS_hip_device_u16_segments_where_sync(const uint16_t* d_array, uint64_t n, const uint64_t* offsets, uint64_t nseg,
+                                                 const void* d_sel, uint64_t sel_offset, int sel_bits, uint64_t* out, uint64_t* selected,
+                                                 int flags)
+{
+    FS_ENTRY();
+    int rc = segw_args(d_array, n, offsets, nseg, d_sel, sel_offset, sel_bits, out, flags, "NULL offsets or out with nseg > 0");
+    if (rc || nseg == 0) return rc;
+    Engine* ep = nullptr;
+    if (n) {
+        int dev = -1, dev_s = -1;
+        if ((rc = fsint::device_of_pointer(d_array, "d_array", &dev))) return rc;
+        if ((rc = fsint::device_of_pointer(d_sel, "d_sel", &dev_s))) return rc;
+        if (dev_s != dev) return fsdrv::fail_devices("d_sel", "d_array");
+        ep = fsint::engine_for_device(dev);
+    } else {
+        ep = fsint::default_engine();
+    }
+    if (!ep) return -1;
+    Engine& e = *ep;
+    std::lock_guard<std::mutex> lk(e.mu);
+    if (fsint::engine_alive(e)) return -1;
+    DeviceGuard guard(e.device);
+    if (!guard.ok()) return -1;
+    const uint32_t grid = seg_grid(e);
+    if ((rc = segw_fits(d_array, n, grid))) return rc;
+    fsseg::SegBuffers buf;     // rows, then the selected counts
+    fsseg::HostRows got;
+    if ((rc = buf.alloc(nseg, 33)) || (rc = got.alloc(nseg, 33))) return rc;
+    if ((rc = fsseg::check_host_offsets(offsets, nseg, n))) return rc;
+    if (n && (rc = fsint::check_extent(d_array, n * sizeof(uint16_t), "d_array"))) return rc;
+    if (n && (rc = fsint::check_extent(d_sel, sel_bytes(n, sel_offset, sel_bits), "d_sel"))) return rc;
+    hipStream_t s = e.stream[0];
+    FS_HIP_TRY(hipMemcpyAsync(buf.off, offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    FS_HIP_TRY(fsk_launch_segments_where(d_array, d_sel, sel_offset, sel_bits, 0, n, buf.off, nseg, buf.cnt, buf.cnt + nseg * 32,
+                                         1 | (flags & 2), grid, s));
+    FS_HIP_TRY(hipMemcpyAsync(got.p.get(), buf.cnt, got.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    FS_HIP_TRY(hipStreamSynchronize(s));
+    apply_both(out, selected, got, nseg, flags);
+    return 0;
+}
+
+int FLAGSTATS_hip_u16_x64_segments_where(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint64_t nseg, const void* sel,
+                                         uint64_t sel_offset, int sel_bits, uint64_t* out, uint64_t* selected, int flags)
+{
+    FS_ENTRY();
+    int rc = segw_args(array, n, offsets, nseg, sel, sel_offset, sel_bits, out, flags, "NULL offsets or out with nseg > 0");
+    if (rc || nseg == 0) return rc;
+    Engine* ep = fsint::default_engine();
+    if (!ep) return -1;
+    Engine& e = *ep;
+    std::lock_guard<std::mutex> lk(e.mu);
+    if (fsint::engine_alive(e)) return -1;
+    DeviceGuard guard(e.device);
+    if (!guard.ok()) return -1;
+    fsint::lz4_gpu_other_use(e);
+    fsseg::SegBuffers buf;     // rows, then the selected counts
+    fsseg::HostRows got;
+    if ((rc = buf.alloc(nseg, 33)) || (rc = got.alloc(nseg, 33))) return rc;
+    if ((rc = fsseg::check_host_offsets(offsets, nseg, n))) return rc;
+    if ((rc = fsint::engine_second(e))) return rc;
+    // only what some segment covers crosses the bus: [offsets[0], offsets[nseg]) of the array and the selection bytes that cover
+    // it, in chunks of "chunk_flags", alternating between the engine's two streams and staging buffers; a chunk's slice of the
+    // selection rides in the same staging buffer, behind the flags -- a bitmap slice from the byte that holds the chunk's first bit
+    // (the launch then starts (sel_offset + pos) & 7 bits into it); every chunk's launch adds its pieces to the same device rows
+    // and counts
+    const uint64_t chunk = fsdrv::chunk_flags();
+    const uint64_t first = offsets[0], last = offsets[nseg];
+    const uint64_t cap = last - first < chunk ? (last - first ? last - first : 1) : chunk;   // flags of the largest chunk
+    const uint64_t sel_cap = sel_bits == 1 ? (cap + 7) / 8 + 1 : cap;                        // bytes of its slice
+    const int slots = last - first > chunk ? 2 : 1;
+    for (int i = 0; i < slots; ++i)
+        if ((rc = fsint::stage_reserve(e, i, cap + (sel_cap + 1) / 2))) return rc;
+    hipStream_t s0 = e.stream[0];
+    FS_HIP_TRY(hipMemsetAsync(buf.cnt, 0, nseg * 33 * sizeof(uint64_t), s0));
+    FS_HIP_TRY(hipMemcpyAsync(buf.off, offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s0));
+    if (slots == 2 && (rc = fsint::stream_wait_stream(e, e.stream[1], s0))) return rc;
+    const uint32_t grid = seg_grid(e);
+    const int mode = flags & 2;
+    const uint8_t* sel_src = static_cast<const uint8_t*>(sel);
+    uint64_t k = 0;
+    for (uint64_t pos = first; pos < last; pos += chunk, ++k) {
+        const int sl = static_cast<int>(k % static_cast<uint64_t>(slots));
+        const uint64_t c = last - pos < chunk ? last - pos : chunk;
+        uint64_t sel_first, sel_len;
+        where_extent(c, sel_offset + pos, sel_bits, &sel_first, &sel_len);
+        uint8_t* d_sel = reinterpret_cast<uint8_t*>(e.stage[sl] + cap);
+        FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], array + pos, c * sizeof(uint16_t), hipMemcpyHostToDevice, e.stream[sl]));
+        FS_HIP_TRY(hipMemcpyAsync(d_sel, sel_src + sel_first, sel_len, hipMemcpyHostToDevice, e.stream[sl]));
+        FS_HIP_TRY(fsk_launch_segments_where(e.stage[sl], d_sel, sel_bits == 1 ? (sel_offset + pos) & 7 : 0, sel_bits, pos, c, buf.off, nseg,
+                                             buf.cnt, buf.cnt + nseg * 32, mode, grid, e.stream[sl]));
+    }
+    if (slots == 2 && (rc = fsint::stream_wait_stream(e, s0, e.stream[1]))) return rc;
+    FS_HIP_TRY(hipMemcpyAsync(got.p.get(), buf.cnt, got.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s0));
+    FS_HIP_TRY(hipStreamSynchronize(s0));
+    if (slots == 2) FS_HIP_TRY(hipStreamSynchronize(e.stream[1]));
+    apply_both(out, selected, got, nseg, flags);
+    return 0;
+}
+
+}  // extern "C"

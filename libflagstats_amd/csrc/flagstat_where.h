@@ -29,4 +29,17 @@ hipError_t fsk_launch_where(const uint16_t* d_array, uint64_t n, const void* d_s
 hipError_t fsk_where_geometry(uint64_t address, uint64_t n, uint64_t sel_offset, int sel_bits, uint32_t grid, uint64_t* geo);
 }
 
+namespace fsdrv {
+
+// the bytes of the selection that hold an element's bit or byte: [first, first + bytes) from `sel` on (n > 0).  The device
+// entries check the allocation from `sel` itself up to first + bytes: only `sel` is known to be device memory, and an offset at
+// or past the allocation's end would otherwise name an address the runtime cannot vouch for
+inline void where_extent(uint64_t n, uint64_t sel_offset, int sel_bits, uint64_t* first, uint64_t* bytes)
+{
+    *first = sel_bits == 1 ? sel_offset >> 3 : sel_offset;
+    *bytes = (sel_bits == 1 ? ((sel_offset + n - 1) >> 3) + 1 : sel_offset + n) - *first;
+}
+
+}  // namespace fsdrv
+
 #endif

@@ -57,6 +57,35 @@ def _check_numpy(values, where, packed, bit_offset):
     return np.ascontiguousarray(values), np.ascontiguousarray(where), bit_offset
 
 
+def _check_torch(t, where, packed, bit_offset) -> int:
+    """the tensor and its selection as the torch entries take them (devices are checked by the caller); the bit offset"""
+    import torch
+
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("t must be a torch.Tensor, not %s" % type(t).__name__)
+    if t.dtype not in (torch.int16, torch.uint16):
+        raise ValueError("t must have dtype int16 or uint16, not %s" % t.dtype)
+    if t.dim() != 1 or not t.is_contiguous():
+        raise ValueError("t must be 1-D and contiguous")
+    if not isinstance(where, torch.Tensor):
+        raise ValueError("where must be a torch.Tensor, not %s" % type(where).__name__)
+    if where.dim() != 1 or not where.is_contiguous():
+        raise ValueError("where must be 1-D and contiguous")
+    bit_offset = _check_bit_offset(packed, bit_offset)
+    if packed:
+        if where.dtype != torch.uint8:
+            raise ValueError("where must have dtype torch.uint8 with packed=True (an LSB-first bitmap), not %s" % where.dtype)
+        need = _packed_bytes(t.numel(), bit_offset)
+        if where.numel() < need:
+            raise ValueError("where holds %d bytes, %d values from bit %d on need %d" % (where.numel(), t.numel(), bit_offset, need))
+    else:
+        if where.dtype != torch.bool:
+            raise ValueError("where must have dtype torch.bool (packed=True: a torch.uint8 bitmap), not %s" % where.dtype)
+        if where.numel() != t.numel():
+            raise ValueError("where must have one element per value (%d), not %d" % (t.numel(), where.numel()))
+    return bit_offset
+
+
 def counters_where(values, where, packed: bool = False, bit_offset: int = 0, superset: bool = False):
     """``(uint64[32] counters, int selected)`` of the elements of the 1-D ``uint16`` host array ``values`` that ``where``
     selects: a ``bool`` array of the same length, or (``packed=True``) a ``uint8`` LSB-first bitmap of at least
@@ -104,28 +133,7 @@ def count_torch_where(t, where, out=None, selected=None, store: bool = False, su
     ``store=False`` adds into both; ``store=True`` overwrites both."""
     import torch
 
-    if not isinstance(t, torch.Tensor):
-        raise ValueError("t must be a torch.Tensor, not %s" % type(t).__name__)
-    if t.dtype not in (torch.int16, torch.uint16):
-        raise ValueError("t must have dtype int16 or uint16, not %s" % t.dtype)
-    if t.dim() != 1 or not t.is_contiguous():
-        raise ValueError("t must be 1-D and contiguous")
-    if not isinstance(where, torch.Tensor):
-        raise ValueError("where must be a torch.Tensor, not %s" % type(where).__name__)
-    if where.dim() != 1 or not where.is_contiguous():
-        raise ValueError("where must be 1-D and contiguous")
-    bit_offset = _check_bit_offset(packed, bit_offset)
-    if packed:
-        if where.dtype != torch.uint8:
-            raise ValueError("where must have dtype torch.uint8 with packed=True (an LSB-first bitmap), not %s" % where.dtype)
-        need = _packed_bytes(t.numel(), bit_offset)
-        if where.numel() < need:
-            raise ValueError("where holds %d bytes, %d values from bit %d on need %d" % (where.numel(), t.numel(), bit_offset, need))
-    else:
-        if where.dtype != torch.bool:
-            raise ValueError("where must have dtype torch.bool (packed=True: a torch.uint8 bitmap), not %s" % where.dtype)
-        if where.numel() != t.numel():
-            raise ValueError("where must have one element per value (%d), not %d" % (t.numel(), where.numel()))
+    bit_offset = _check_torch(t, where, packed, bit_offset)
     _checks.check_result_pair(out, "selected", selected)
     out, selected = _checks.place_result_pair(t, out, "selected", selected, others=(("where", where),))
     lib = _lib.lib()
