@@ -3,7 +3,10 @@
 //   pass(j) = (flag[j] & require) == require && (flag[j] & exclude) == 0 && (min_mapq == 0 || mapq[j] >= min_mapq).
 // The segmented kernel (flagstat_segments.hip) with the filter kernel's predicate (flagstat_filter.hip) in front of the count.
 //
-// Work split and walk.  The segmented kernel's, unchanged (tests/segments_oracle.WriterSplit mirrors both): units of 4096 flags
+// Work split and walk.  The segmented kernels' (tests/segments_oracle.WriterSplit mirrors them) -- but this kernel keeps its own
+// copy of the walk that flagstat_segments, flagstat_segments_wide and flagstat_segments_where take from flagstat_segments_shared.h
+// (seg_walk<UE>): in the shared form it was 7 % slower on ~1,000-flag segments (profiles/r18/ab_flagstat_segments_filter.log).  A
+// change to the walk is made there and here.  Units of 4096 flags
 // on the 16-byte grid of the array's aligned-down base, every wave a writer over a contiguous run of units, the 64-ary search
 // for its first segment, the window of 64 offsets, plain stores in the store form for rows that lie inside one writer.  The
 // pieces shared with that kernel live in flagstat_segments_shared.h, those shared with the filter kernel in
@@ -22,13 +25,12 @@
 //     piece bounds, there is no separate masking of the vector -- and keeps them out of the passing count: a zero-filled or
 //     foreign position passes every predicate without `require` bits.
 //
-// Emission.  The number of passing flags is a 22nd lane counter, reduced and reset with the 21 at a segment end; it is the
+// Emission (seg_emit<true, false> of flagstat_segments_shared.h).  The number of passing flags is a 22nd lane counter, reduced and
+// reset with the 21 at a segment end; it is the
 // `len` of the superset slot 9, and lane 32 of the instruction that writes the row's 32 slots writes selected[s]: a plain
 // store where the row is stored plainly, else a relaxed agent-scope atomic add.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <mutex>
 
 #include "../../include/libflagstats_hip.h"
 #include "flagstat_count_core.h"
@@ -137,8 +139,9 @@ __global__ __launch_bounds__(kThreads) void flagstat_segments_filter(const uint4
     uint32_t cnt = 0;   // passing flags of this lane in segment s not yet emitted
     bool open = false;  // st and cnt hold counts of segment s not yet emitted
     uint64_t sb = 0, se = 0;
+    uint32_t none = 0;  // no mask
     auto emit = [&](uint64_t seg, uint64_t b_, uint64_t e_) {
-        segf_emit(st, blk, cnt, red, out, selected, seg, (mode & 1) && b_ >= p0 && e_ <= E, mode, lane);
+        seg_emit<true, false>(st, blk, cnt, none, none, red, out, selected, nullptr, seg, 0, (mode & 1) && b_ >= p0 && e_ <= E, mode, lane);
     };
 
     uint64_t u = p0 / kSegWaveFlags;
@@ -146,9 +149,7 @@ __global__ __launch_bounds__(kThreads) void flagstat_segments_filter(const uint4
         sw.bounds(s, sb, se);
         const uint64_t w0 = u * kSegWaveFlags;
         const uint64_t x = w0 > p0 ? w0 : p0;
-        // A segment that begins at or past this writer's end is not its business, nor (monotone offsets) is any later one.  This
-        // test comes first: a launch on one chunk of a longer array (the host form) clamps every later segment to an empty one
-        // at the chunk's end, and stepping through those one by one would cost the chunk's last writer O(nseg) per launch.
+        // (the order of these tests is seg_walk's in flagstat_segments_shared.h, for its reasons)
         if (sb >= E) break;
         if (se <= sb || se <= x) {  // empty (or, with malformed offsets, reversed or behind)
             ++s;
@@ -246,9 +247,6 @@ __global__ __launch_bounds__(kThreads) void flagstat_segments_filter(const uint4
 }  // namespace fsk
 
 // ------------------------------------------------------------------ launcher
-using fsseg::launch_shape;
-using fsseg::wave_totals_fit;
-
 extern "C" hipError_t fsk_launch_segments_filter(const uint16_t* d_chunk, const uint8_t* d_mapq_chunk, uint64_t base, uint64_t m,
                                                  const uint64_t* d_offsets, uint64_t nseg, uint32_t require, uint32_t exclude,
                                                  uint32_t min_mapq, uint64_t* d_out, uint64_t* d_selected, int mode, uint32_t grid,
@@ -263,8 +261,8 @@ extern "C" hipError_t fsk_launch_segments_filter(const uint16_t* d_chunk, const 
     uint64_t lo0 = 0, nunits = 0;
     uint32_t g = 0;
     if (m) {
-        launch_shape(addr, m, grid, &lo0, &nunits, &g);
-        if (!wave_totals_fit(nunits, g)) return hipErrorInvalidValue;
+        fsseg::launch_shape(addr, m, fsk::kSegWaveFlags, grid, &lo0, &nunits, &g);
+        if (!fsseg::wave_totals_fit(nunits, g, fsk::kSegWaveFlags)) return hipErrorInvalidValue;
     }
     if (mode & 1) {
         hipError_t e = fsk_zero_words(d_out, nseg * 32, stream);
@@ -291,11 +289,9 @@ extern "C" hipError_t fsk_launch_segments_filter(const uint16_t* d_chunk, const 
 }
 
 // ------------------------------------------------------------------ C entry points (include/libflagstats_hip.h)
-using fsint::DeviceGuard;
+// The bodies of the three forms are fsseg's (flagstat_segments_shared.h): 33 words per segment, the rows, then the selected counts.
 using fsint::Engine;
 using fsint::fail_text;
-using fsseg::apply_both;
-using fsseg::seg_grid;
 
 namespace {
 
@@ -317,17 +313,6 @@ int segf_args(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint64
     return 0;
 }
 
-int segf_fits(const uint16_t* array, uint64_t n, uint32_t grid)
-{
-    if (n == 0) return 0;
-    uint64_t lo0 = 0, nunits = 0;
-    uint32_t g = 0;
-    launch_shape(reinterpret_cast<uintptr_t>(array), n, grid, &lo0, &nunits, &g);
-    if (!wave_totals_fit(nunits, g))
-        return fail_text("n is too large for this grid: a wave's uint32 totals could overflow (split the array)");
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -341,18 +326,14 @@ int FLAGSTATS_hip_device_u16_segments_filter(const uint16_t* d_array, uint64_t n
     if (rc || nseg == 0) return rc;
     const fsdrv::DeviceWord word{d_selected, "d_selected", "the counts are added with device atomics"};
     const fsdrv::Input in[] = {{d_offsets, "d_offsets", (nseg + 1) * sizeof(uint64_t)}, {d_array, "d_array", n * 2}, {d_mapq, "d_mapq", n}};
-    const int inputs = n ? (min_mapq ? 3 : 2) : 1;
-    fsdrv::DeviceCall call;
-    if ((rc = call.open(d_out, word, in, inputs, stream))) return rc;
-    const uint32_t grid = seg_grid(*call.e);
-    if ((rc = segf_fits(d_array, n, grid))) return rc;
-    if ((rc = fsint::check_extent(d_out, nseg * 32 * sizeof(uint64_t), "d_out"))) return rc;
-    if (d_selected && (rc = fsint::check_extent(d_selected, nseg * sizeof(uint64_t), "d_selected"))) return rc;
-    for (int i = 0; i < inputs; ++i)
-        if ((rc = fsint::check_extent(in[i].p, in[i].bytes, in[i].name))) return rc;
-    FS_HIP_TRY(fsk_launch_segments_filter(d_array, d_mapq, 0, n, d_offsets, nseg, require, exclude, min_mapq, d_out, d_selected, flags & 3,
-                                          grid, call.s));
-    return 0;
+    return fsseg::device_call(
+        d_out, &word, 1, in, n ? (min_mapq ? 3 : 2) : 1, nseg, stream,
+        [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWaveFlags, grid); },
+        [&](uint32_t grid, hipStream_t s) {
+            FS_HIP_TRY(fsk_launch_segments_filter(d_array, d_mapq, 0, n, d_offsets, nseg, require, exclude, min_mapq, d_out, d_selected,
+                                                  flags & 3, grid, s));
+            return 0;
+        });
 }
 
 int FLAGSTATS_hip_device_u16_segments_filter_sync(const uint16_t* d_array, uint64_t n, const uint64_t* offsets, uint64_t nseg,
@@ -362,40 +343,16 @@ int FLAGSTATS_hip_device_u16_segments_filter_sync(const uint16_t* d_array, uint6
     FS_ENTRY();
     int rc = segf_args(d_array, n, offsets, nseg, require, exclude, d_mapq, min_mapq, out, flags, "NULL offsets or out with nseg > 0");
     if (rc || nseg == 0) return rc;
-    Engine* ep = nullptr;
-    if (n) {
-        int dev = -1, dev_q = -1;
-        if ((rc = fsint::device_of_pointer(d_array, "d_array", &dev))) return rc;
-        if (min_mapq) {
-            if ((rc = fsint::device_of_pointer(d_mapq, "d_mapq", &dev_q))) return rc;
-            if (dev_q != dev) return fsdrv::fail_devices("d_mapq", "d_array");
-        }
-        ep = fsint::engine_for_device(dev);
-    } else {
-        ep = fsint::default_engine();
-    }
-    if (!ep) return -1;
-    Engine& e = *ep;
-    std::lock_guard<std::mutex> lk(e.mu);
-    if (fsint::engine_alive(e)) return -1;
-    DeviceGuard guard(e.device);
-    if (!guard.ok()) return -1;
-    const uint32_t grid = seg_grid(e);
-    if ((rc = segf_fits(d_array, n, grid))) return rc;
-    fsseg::SegBuffers buf;     // rows, then the selected counts
-    fsseg::HostRows got;
-    if ((rc = buf.alloc(nseg, 33)) || (rc = got.alloc(nseg, 33))) return rc;
-    if ((rc = fsseg::check_host_offsets(offsets, nseg, n))) return rc;
-    if (n && (rc = fsint::check_extent(d_array, n * sizeof(uint16_t), "d_array"))) return rc;
-    if (n && min_mapq && (rc = fsint::check_extent(d_mapq, n, "d_mapq"))) return rc;
-    hipStream_t s = e.stream[0];
-    FS_HIP_TRY(hipMemcpyAsync(buf.off, offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    FS_HIP_TRY(fsk_launch_segments_filter(d_array, d_mapq, 0, n, buf.off, nseg, require, exclude, min_mapq, buf.cnt, buf.cnt + nseg * 32,
-                                          1 | (flags & 2), grid, s));
-    FS_HIP_TRY(hipMemcpyAsync(got.p.get(), buf.cnt, got.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    FS_HIP_TRY(hipStreamSynchronize(s));
-    apply_both(out, selected, got, nseg, flags);
-    return 0;
+    const fsdrv::Input in[] = {{d_array, "d_array", n * sizeof(uint16_t)}, {d_mapq, "d_mapq", n}};
+    return fsseg::sync_call(
+        in, n ? (min_mapq ? 2 : 1) : 0, n, offsets, nseg, 33,
+        [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWaveFlags, grid); },
+        [&](fsseg::SegBuffers& buf, uint32_t grid, hipStream_t s) {
+            FS_HIP_TRY(fsk_launch_segments_filter(d_array, d_mapq, 0, n, buf.off, nseg, require, exclude, min_mapq, buf.cnt,
+                                                  buf.cnt + nseg * 32, 1 | (flags & 2), grid, s));
+            return 0;
+        },
+        [&](const fsseg::HostRows& got) { fsseg::apply_both(out, selected, got, nseg, flags); });
 }
 
 int FLAGSTATS_hip_u16_x64_segments_filter(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint64_t nseg, uint32_t require,
@@ -405,52 +362,21 @@ int FLAGSTATS_hip_u16_x64_segments_filter(const uint16_t* array, uint64_t n, con
     FS_ENTRY();
     int rc = segf_args(array, n, offsets, nseg, require, exclude, mapq, min_mapq, out, flags, "NULL offsets or out with nseg > 0");
     if (rc || nseg == 0) return rc;
-    Engine* ep = fsint::default_engine();
-    if (!ep) return -1;
-    Engine& e = *ep;
-    std::lock_guard<std::mutex> lk(e.mu);
-    if (fsint::engine_alive(e)) return -1;
-    DeviceGuard guard(e.device);
-    if (!guard.ok()) return -1;
-    fsint::lz4_gpu_other_use(e);
-    fsseg::SegBuffers buf;     // rows, then the selected counts
-    fsseg::HostRows got;
-    if ((rc = buf.alloc(nseg, 33)) || (rc = got.alloc(nseg, 33))) return rc;
-    if ((rc = fsseg::check_host_offsets(offsets, nseg, n))) return rc;
-    if ((rc = fsint::engine_second(e))) return rc;
-    // only what some segment covers crosses the bus: [offsets[0], offsets[nseg]) of the array and of the column, in chunks of
-    // "chunk_flags", alternating between the engine's two streams and staging buffers; a chunk's slice of the MAPQ column rides
-    // in the same staging buffer, behind the flags; every chunk's launch adds its pieces to the same device rows and counts.
-    // An overlapping pair selects nothing: nothing is moved.
-    const uint64_t chunk = fsdrv::chunk_flags();
-    const uint64_t first = offsets[0], last = (require & exclude) ? first : offsets[nseg];
-    const uint64_t cap = last - first < chunk ? (last - first ? last - first : 1) : chunk;   // flags of the largest chunk
-    const uint64_t mapq_cap = min_mapq ? cap : 0;                                            // bytes of its MAPQ slice
-    const int slots = last - first > chunk ? 2 : 1;
-    for (int i = 0; i < slots; ++i)
-        if ((rc = fsint::stage_reserve(e, i, cap + (mapq_cap + 1) / 2))) return rc;
-    hipStream_t s0 = e.stream[0];
-    FS_HIP_TRY(hipMemsetAsync(buf.cnt, 0, nseg * 33 * sizeof(uint64_t), s0));
-    FS_HIP_TRY(hipMemcpyAsync(buf.off, offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s0));
-    if (slots == 2 && (rc = fsint::stream_wait_stream(e, e.stream[1], s0))) return rc;
-    const uint32_t grid = seg_grid(e);
+    // a chunk's slice of the MAPQ column rides in the same staging buffer, behind the flags.  An overlapping pair selects
+    // nothing: nothing is moved.
     const int mode = flags & 2;
-    uint64_t k = 0;
-    for (uint64_t pos = first; pos < last; pos += chunk, ++k) {
-        const int sl = static_cast<int>(k % static_cast<uint64_t>(slots));
-        const uint64_t c = last - pos < chunk ? last - pos : chunk;
-        uint8_t* d_mapq = reinterpret_cast<uint8_t*>(e.stage[sl] + cap);
-        FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], array + pos, c * sizeof(uint16_t), hipMemcpyHostToDevice, e.stream[sl]));
-        if (min_mapq) FS_HIP_TRY(hipMemcpyAsync(d_mapq, mapq + pos, c, hipMemcpyHostToDevice, e.stream[sl]));
-        FS_HIP_TRY(fsk_launch_segments_filter(e.stage[sl], d_mapq, pos, c, buf.off, nseg, require, exclude, min_mapq, buf.cnt,
-                                              buf.cnt + nseg * 32, mode, grid, e.stream[sl]));
-    }
-    if (slots == 2 && (rc = fsint::stream_wait_stream(e, s0, e.stream[1]))) return rc;
-    FS_HIP_TRY(hipMemcpyAsync(got.p.get(), buf.cnt, got.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s0));
-    FS_HIP_TRY(hipStreamSynchronize(s0));
-    if (slots == 2) FS_HIP_TRY(hipStreamSynchronize(e.stream[1]));
-    apply_both(out, selected, got, nseg, flags);
-    return 0;
+    return fsseg::host_call(
+        n, offsets, nseg, 33, fsdrv::chunk_flags(), [&] { return (require & exclude) ? offsets[0] : offsets[nseg]; },
+        [&](uint64_t cap) { return cap + ((min_mapq ? cap : 0) + 1) / 2; },
+        [&](Engine& e, fsseg::SegBuffers& buf, int sl, uint64_t pos, uint64_t c, uint64_t cap, uint32_t grid) {
+            uint8_t* d_mapq = reinterpret_cast<uint8_t*>(e.stage[sl] + cap);
+            FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], array + pos, c * sizeof(uint16_t), hipMemcpyHostToDevice, e.stream[sl]));
+            if (min_mapq) FS_HIP_TRY(hipMemcpyAsync(d_mapq, mapq + pos, c, hipMemcpyHostToDevice, e.stream[sl]));
+            FS_HIP_TRY(fsk_launch_segments_filter(e.stage[sl], d_mapq, pos, c, buf.off, nseg, require, exclude, min_mapq, buf.cnt,
+                                                  buf.cnt + nseg * 32, mode, grid, e.stream[sl]));
+            return 0;
+        },
+        [&](const fsseg::HostRows& got) { fsseg::apply_both(out, selected, got, nseg, flags); });
 }
 
 }  // extern "C"

@@ -1,7 +1,10 @@
-// flagstat_segments_shared.h -- internal: what the segmented kernels share (flagstat_segments.hip, flagstat_segments_filter.hip).
-// Device code: the geometry of a wave's unit, the per-flag count of a vector, the clamped grid position of an offset, the walk
-// of a writer over the segments that intersect it (64-ary search, 64-offset window) and the map from a wave's 21 totals to the 32
-// slots of a row.  Host code: the checks and buffers of the synchronous entries over host offsets.
+// flagstat_segments_shared.h -- internal: what the five segmented kernels share (flagstat_segments.hip, flagstat_segments_filter.hip,
+// flagstat_segments_wide.hip, flagstat_segments_wide_filter.hip, flagstat_segments_where.hip).
+// Device code: the geometry of a wave's unit, the per-flag count of a vector, the clamped grid position of an offset, the search
+// and window over the offsets (SegWalk), the walk of a writer over the segments that intersect it (seg_walk<UE>: the kernels hand in
+// their chain run, their unit load, their piece count and their emission), the map from a wave's 21 totals to the 32 slots of a
+// row and the one emission (seg_emit<COUNT, MASK>).  Host code: launch_shape / wave_totals_fit / fits, the checks and buffers over
+// host offsets, and the bodies of the three entry forms (device_call, sync_call, host_call).
 // (Product library only: the entries check allocation extents, which the host-stub build does not have.)
 #ifndef FLAGSTAT_SEGMENTS_SHARED_H_
 #define FLAGSTAT_SEGMENTS_SHARED_H_
@@ -12,16 +15,19 @@
 #include <cstdio>
 #include <cstring>
 #include <memory>
+#include <mutex>
 #include <new>
 
 #include "flagstat_count_core.h"
+#include "flagstat_derived_host.h"
 #include "flagstat_engine.h"
 #include "flagstat_segments.h"
+#include "flagstat_wide_device.h"
 
 namespace fsk {
 
 constexpr int kSegRowVecs = 64;                    // vectors per row (one per lane)
-constexpr int kSegUnitVecs = kSegWaveFlags / 8;    // 512 vectors per unit
+constexpr int kSegUnitVecs = kSegWaveFlags / 8;    // 512 vectors per unit, 8 KiB, at every element size
 constexpr int kSegFilterDepth = 8;                 // chain depth of the selecting kernels, as K1: epochs of 255 units
 
 // Per-flag form: 8 flags on their byte planes (L: FLAG bits 0-7, H: bits 8-15; 4 flags per dword) straight into the 21 lane
@@ -73,38 +79,76 @@ __device__ __forceinline__ uint64_t seg_slot_value(const uint32_t* tot, uint32_t
     return add;
 }
 
-// the selecting kernels (flagstat_segments_filter.hip, flagstat_segments_where.hip): the wave's counters of the piece of segment s
-// it holds -> out[s][32], and its passing (selected) count -> selected[s]
-__device__ __forceinline__ void segf_emit(Lane<kSegFilterDepth>& st, uint32_t& blk, uint32_t& cnt, uint32_t* red, uint64_t* __restrict__ out,
-                                          uint64_t* __restrict__ selected, uint64_t s, bool plain, int mode, uint32_t lane)
+// The wave's counters of the piece of segment s it holds -> out[s][32]: the chain is flushed, the 21 lane counters are summed
+// over the wave (DPP) and reset, lane 63 hands the totals over through red[] and lanes 0-31 of one instruction write the row.
+// COUNT: the passing count is summed, handed over and reset with them (red[21]); it is the `len` of the superset slot 9 in
+// place of the piece's length, and lane 32 writes it to selected[s] (which may be nullptr).  MASK: the two mask accumulators are
+// ORed over the wave and reset (red[21], red[22], one further on with COUNT) and the lane behind the count's -- 32, or 33 with
+// COUNT -- writes high[s] (which may be nullptr).  Plain stores where the row is stored plainly (store form, the whole segment in
+// this wave), else relaxed agent-scope atomics (add, add, OR) issued only for non-zero values.  A kernel without a count or a
+// mask passes any lvalue for cnt, or_even and or_odd: they are not touched.
+template <bool COUNT, bool MASK, int DEPTH>
+__device__ __forceinline__ void seg_emit(Lane<DEPTH>& st, uint32_t& blk, uint32_t& cnt, uint32_t& or_even, uint32_t& or_odd, uint32_t* red,
+                                         uint64_t* __restrict__ out, uint64_t* __restrict__ selected, uint64_t* __restrict__ high, uint64_t s,
+                                         uint64_t len, bool plain, int mode, uint32_t lane)
 {
+    constexpr int kSums = kInternal + (COUNT ? 1 : 0);   // red[0 .. kSums): sums; red[kSums], red[kSums + 1]: the mask
+    constexpr uint32_t kMaskLane = COUNT ? 33u : 32u;
     if (blk) {
         flush(st, blk);
         blk = 0;
     }
     uint32_t w[kInternal + 1];
 #pragma unroll
-    for (int c = 0; c < kInternal; ++c) {
-        w[c] = wave_sum_lane63(st.acc[c]);
-        st.acc[c] = 0;
+    for (int i = 0; i < kInternal; ++i) {
+        w[i] = wave_sum_lane63(st.acc[i]);
+        st.acc[i] = 0;
     }
-    w[kInternal] = wave_sum_lane63(cnt);
-    cnt = 0;
+    if constexpr (COUNT) {
+        w[kInternal] = wave_sum_lane63(cnt);
+        cnt = 0;
+    }
+    uint32_t we = 0, wo = 0;
+    if constexpr (MASK) {
+        we = wave_or_lane63(or_even & 0xFFFF0000u);   // the even-dword stream: bits 16-31 of every element
+        wo = wave_or_lane63(or_odd);                   // W = 8: bits 32-63
+        or_even = 0;
+        or_odd = 0;
+    }
     if (lane == 63) {
 #pragma unroll
-        for (int c = 0; c <= kInternal; ++c) red[c] = w[c];
+        for (int i = 0; i < kSums; ++i) red[i] = w[i];
+        if constexpr (MASK) {
+            red[kSums] = we;
+            red[kSums + 1] = wo;
+        }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (lane < 32 || (lane == 32 && selected != nullptr)) {
-        const uint64_t passing = red[kInternal];
-        const uint64_t add = lane < 32 ? seg_slot_value(red, lane, mode, passing) : passing;
-        uint64_t* o = lane < 32 ? out + s * 32 + lane : selected + s;
+    bool adds = lane < 32;
+    if constexpr (COUNT) adds = adds || (lane == 32 && selected != nullptr);
+    if (adds) {
+        uint64_t add;
+        uint64_t* o;
+        if constexpr (COUNT) {
+            const uint64_t passing = red[kInternal];
+            add = lane < 32 ? seg_slot_value(red, lane, mode, passing) : passing;
+            o = lane < 32 ? out + s * 32 + lane : selected + s;
+        } else {
+            add = seg_slot_value(red, lane, mode, len);
+            o = out + s * 32 + lane;
+        }
         if (plain)
-            *o = add;  // store form, the whole segment in this wave: all 32 slots and the count
+            *o = add;
         else if (add)
             (void)__hip_atomic_fetch_add(o, add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else if (MASK && lane == kMaskLane && high != nullptr) {
+        const uint64_t m = (static_cast<uint64_t>(red[kSums + 1]) << 32) | red[kSums];
+        if (plain)
+            high[s] = m;
+        else if (m)
+            (void)__hip_atomic_fetch_or(high + s, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __builtin_amdgcn_wave_barrier();  // red[] is rewritten by the next segment's totals only after every lane has read it
 }
@@ -176,6 +220,106 @@ struct SegWalk {
         return lo - 1;
     }
 };
+
+// The walk of one wave -- a writer -- over the segments that intersect its run of units, for every segmented kernel.  UE:
+// grid positions per unit (kSegWaveFlags, or kSegWideUnitBytes / W).  a chunk's elements occupy grid positions [lo0, hi0) and
+// are global elements [base, base + hi0 - lo0); nunits = ceil(hi0 / UE); mode bit 0: store form.  Every lane of the wave is
+// active in every call it makes.  The kernel keeps its own state (the lane's chain and counters, its passing count or mask
+// accumulators, its row registers, its filter or table) and hands in, as always-inline callables:
+//   chain(u, k)       count the k whole units from unit u, all of one segment, through its carry-save chain
+//   load(u, whole)    load the 8 rows of unit u, and what rides with them, for the per-piece count: with plain loads if `whole`
+//                     (the unit lies wholly inside [lo0, hi0)), else through its guarded loaders
+//   piece(w0, b, e)   count the piece [b, e) of the unit loaded last, which starts at grid position w0
+//   emit(s, len, plain)  add what it holds to row s and reset it: len is the length of the piece of s this writer holds, plain
+//                     says the whole segment lies in this writer and the launch is in the store form
+template <uint64_t UE, typename Chain, typename Load, typename Piece, typename Emit>
+__device__ __forceinline__ void seg_walk(uint64_t lo0, uint64_t hi0, uint64_t base, const uint64_t* __restrict__ off, uint64_t nseg, int mode,
+                                         uint64_t nunits, uint32_t min_units, Chain&& chain, Load&& load, Piece&& piece, Emit&& emit_fn)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = threadIdx.x >> 6;
+    const uint64_t waves = static_cast<uint64_t>(gridDim.x) * (kThreads / 64);
+    const uint64_t gw = static_cast<uint64_t>(blockIdx.x) * (kThreads / 64) + wave;
+    const uint64_t u_begin = gw * nunits / waves, u_end = (gw + 1) * nunits / waves;
+    const uint64_t p0 = u_begin * UE > lo0 ? u_begin * UE : lo0;  // this writer: grid positions [p0, E)
+    const uint64_t E = u_end * UE < hi0 ? u_end * UE : hi0;
+    if (p0 >= E) return;
+
+    SegWalk sw{off, nseg, base, hi0 - lo0, lo0, lane, 0, 0, 0};
+    uint64_t s = sw.first_segment(p0);
+    if (s >= nseg) return;
+    sw.load_window(s);
+
+    bool open = false;  // the kernel's state holds counts of segment s not yet emitted
+    uint64_t sb = 0, se = 0;
+    auto emit = [&](uint64_t seg, uint64_t b_, uint64_t e_) __attribute__((always_inline)) {
+        const uint64_t pb = b_ > p0 ? b_ : p0, pe = e_ < E ? e_ : E;
+        emit_fn(seg, pe - pb, (mode & 1) && b_ >= p0 && e_ <= E);
+    };
+
+    uint64_t u = p0 / UE;
+    while (s < nseg && u < u_end) {
+        sw.bounds(s, sb, se);
+        const uint64_t w0 = u * UE;
+        const uint64_t x = w0 > p0 ? w0 : p0;
+        // A segment that begins at or past this writer's end is not its business, nor (monotone offsets) is any later one.  This
+        // test comes first: a launch on one chunk of a longer array (the host form) clamps every later segment to an empty one
+        // at the chunk's end, and stepping through those one by one would cost the chunk's last writer O(nseg) per launch.
+        if (sb >= E) break;
+        if (se <= sb || se <= x) {  // empty (or, with malformed offsets, reversed or behind)
+            ++s;
+            continue;
+        }
+        if (sb >= w0 + UE) {  // elements before the segment belong to none: skip whole units unread
+            u = sb / UE;
+            continue;
+        }
+        const uint64_t seg_e = se < E ? se : E;
+        if (sb <= w0 && w0 >= lo0) {
+            const uint64_t k = (seg_e - w0) / UE;  // whole units of segment s from here on
+            if (k >= min_units && k > 0) {
+                chain(u, k);
+                u += k;
+                open = true;
+                if (u * UE >= se) {
+                    emit(s, sb, se);
+                    open = false;
+                    ++s;
+                }
+                continue;
+            }
+        }
+        // per-piece unit: its 8 rows loaded at once, then every segment piece in it
+        load(u, w0 >= lo0 && w0 + UE <= hi0);
+        const uint64_t w1 = w0 + UE;
+        uint64_t xx = x;
+        for (;;) {
+            // s < nseg, sb < se, se > xx, sb < w1; the piece [b, e) lies inside [p0, E) and so inside [lo0, hi0)
+            const uint64_t b = sb > xx ? sb : xx, e = se < w1 ? se : w1;
+            piece(w0, b, e);
+            open = true;
+            if (e < se) break;  // segment s goes on in the next unit
+            emit(s, sb, se);
+            open = false;
+            ++s;
+            xx = e;
+            bool more = false;
+            while (s < nseg) {
+                sw.bounds(s, sb, se);
+                if (sb >= E) break;  // (as in the outer walk: before the empty test)
+                if (se <= sb || se <= xx) {
+                    ++s;
+                    continue;
+                }
+                more = sb < w1;
+                break;
+            }
+            if (!more) break;
+        }
+        ++u;
+    }
+    if (open) emit(s, sb, se);  // this writer's range ends inside segment s
+}
 
 }  // namespace fsk
 
@@ -283,20 +427,159 @@ inline void apply_both(uint64_t* out, uint64_t* selected, const fsseg::HostRows&
     if (selected) fsseg::apply(selected, got.p.get() + nseg * 32, nseg, flags);
 }
 
-// a wave's totals are uint32: every wave must own fewer than 2^32 flags
-inline bool wave_totals_fit(uint64_t nunits, uint32_t g)
+// the masks of a call's result into the caller's host words: stored (flags bit 0) or ORed
+inline void apply_masks(uint64_t* high, const uint64_t* got, uint64_t nseg, int flags)
 {
-    const uint64_t waves = static_cast<uint64_t>(g) * (fsk::kThreads / 64);
-    return (nunits + waves - 1) / waves < (1ull << 32) / fsk::kSegWaveFlags;
+    if (!high) return;
+    for (uint64_t i = 0; i < nseg; ++i) high[i] = (flags & 1) ? got[i] : (high[i] | got[i]);
 }
 
-// units and workgroups of a launch over m > 0 uint16 flags at `addr` with at most `grid` workgroups
-inline void launch_shape(uintptr_t addr, uint64_t m, uint32_t grid, uint64_t* lo0, uint64_t* nunits, uint32_t* g)
+// a wave's totals are uint32: every wave must own fewer than 2^32 elements (ue: elements per unit)
+inline bool wave_totals_fit(uint64_t nunits, uint32_t g, uint64_t ue)
 {
-    *lo0 = (addr & 15u) / 2;
-    *nunits = (*lo0 + m + fsk::kSegWaveFlags - 1) / fsk::kSegWaveFlags;
+    const uint64_t waves = static_cast<uint64_t>(g) * (fsk::kThreads / 64);
+    return (nunits + waves - 1) / waves < (1ull << 32) / ue;
+}
+
+// units and workgroups of a launch over m > 0 elements at `addr` with at most `grid` workgroups; ue: elements per 8 KiB unit
+// (fsk::kSegWaveFlags, or fsk::kSegWideUnitBytes / W), so an element has W = 8192 / ue bytes
+inline void launch_shape(uintptr_t addr, uint64_t m, uint64_t ue, uint32_t grid, uint64_t* lo0, uint64_t* nunits, uint32_t* g)
+{
+    const uint64_t W = fsk::kSegUnitVecs * 16 / ue;
+    *lo0 = (addr & 15u) / W;
+    *nunits = (*lo0 + m + ue - 1) / ue;
     const uint64_t want = (*nunits + 3) / 4;  // one unit per wave at least
     *g = want < grid ? static_cast<uint32_t>(want) : grid;
+}
+
+// what the entries of the kernels with a fit check refuse once the grid is known
+inline int fits(const void* array, uint64_t n, uint64_t ue, uint32_t grid)
+{
+    if (n == 0) return 0;
+    uint64_t lo0 = 0, nunits = 0;
+    uint32_t g = 0;
+    launch_shape(reinterpret_cast<uintptr_t>(array), n, ue, grid, &lo0, &nunits, &g);
+    if (!wave_totals_fit(nunits, g, ue))
+        return fsint::fail_text("n is too large for this grid: a wave's uint32 totals could overflow (split the array)");
+    return 0;
+}
+
+// ------------------------------------------------------------------ the bodies of the three entry forms, for all five units
+// What differs between the units arrives as arguments and callables (the pattern of flagstat_derived_host.h): the unit's own
+// argument check runs in front; its trailing words (none, selected, high, or both), its inputs with the names its refusals use,
+// its fit check, its words per segment (32 / 33 / 34), how a chunk's extra column is staged, its launch and how its result is
+// applied.  A HIP call that a callable makes goes through FS_HIP_TRY there, so the text of its failure names the caller's own
+// expression.
+
+// On the caller's stream (nseg > 0, arguments checked): d_out and the trailing words are plain device memory on one device with
+// every input; `fits(grid)` may still refuse; every allocation holds what the call touches of it; then `launch(grid, s)`.
+template <typename Fits, typename Launch>
+int device_call(const void* d_out, const fsdrv::DeviceWord* words, int nwords, const fsdrv::Input* in, int inputs, uint64_t nseg,
+                void* stream, Fits&& fits_fn, Launch&& launch)
+{
+    int rc;
+    fsdrv::DeviceCall call;
+    if ((rc = call.open(d_out, words, nwords, in, inputs, stream))) return rc;
+    const uint32_t grid = seg_grid(*call.e);
+    if ((rc = fits_fn(grid))) return rc;
+    if ((rc = fsint::check_extent(d_out, nseg * 32 * sizeof(uint64_t), "d_out"))) return rc;
+    for (int k = 0; k < nwords; ++k)
+        if (words[k].p && (rc = fsint::check_extent(words[k].p, nseg * sizeof(uint64_t), words[k].name))) return rc;
+    for (int i = 0; i < inputs; ++i)
+        if ((rc = fsint::check_extent(in[i].p, in[i].bytes, in[i].name))) return rc;
+    return launch(grid, call.s);
+}
+
+// Synchronous over device memory and host offsets (nseg > 0, arguments checked): the inputs (none if n == 0) live on one device,
+// the first one's; under its engine's lock `fits(grid)` may still refuse; rows of `words` uint64 per segment and the offsets get
+// device buffers of their own, the offsets are checked and copied, `launch(buf, grid, s)` counts in the store form on the
+// engine's first stream and `apply_fn(got)` takes the result to the caller's host words.
+template <typename Fits, typename Launch, typename Apply>
+int sync_call(const fsdrv::Input* in, int inputs, uint64_t n, const uint64_t* offsets, uint64_t nseg, uint64_t words, Fits&& fits_fn,
+              Launch&& launch, Apply&& apply_fn)
+{
+    int rc, dev = -1, dev_i = -1;
+    fsint::Engine* ep = nullptr;
+    if (inputs) {
+        if ((rc = fsint::device_of_pointer(in[0].p, in[0].name, &dev))) return rc;
+        for (int i = 1; i < inputs; ++i) {
+            if ((rc = fsint::device_of_pointer(in[i].p, in[i].name, &dev_i))) return rc;
+            if (dev_i != dev) return fsdrv::fail_devices(in[i].name, in[0].name);
+        }
+        ep = fsint::engine_for_device(dev);
+    } else {
+        ep = fsint::default_engine();
+    }
+    if (!ep) return -1;
+    fsint::Engine& e = *ep;
+    std::lock_guard<std::mutex> lk(e.mu);
+    if (fsint::engine_alive(e)) return -1;
+    fsint::DeviceGuard guard(e.device);
+    if (!guard.ok()) return -1;
+    const uint32_t grid = seg_grid(e);
+    if ((rc = fits_fn(grid))) return rc;
+    SegBuffers buf;
+    HostRows got;
+    if ((rc = buf.alloc(nseg, words)) || (rc = got.alloc(nseg, words))) return rc;
+    if ((rc = check_host_offsets(offsets, nseg, n))) return rc;
+    for (int i = 0; i < inputs; ++i)
+        if ((rc = fsint::check_extent(in[i].p, in[i].bytes, in[i].name))) return rc;
+    hipStream_t s = e.stream[0];
+    FS_HIP_TRY(hipMemcpyAsync(buf.off, offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    if ((rc = launch(buf, grid, s))) return rc;
+    FS_HIP_TRY(hipMemcpyAsync(got.p.get(), buf.cnt, got.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    FS_HIP_TRY(hipStreamSynchronize(s));
+    apply_fn(got);
+    return 0;
+}
+
+// Over host memory (nseg > 0, arguments checked): only what some segment covers crosses the bus -- the elements [offsets[0], last)
+// in chunks of `chunk` elements, alternating between the default engine's two streams and staging buffers (the copy of chunk
+// k + 1 overlaps the kernel on chunk k).  `last_fn()` is offsets[nseg], or offsets[0] where the unit knows that nothing is selected;
+// it is asked only once the rows are allocated and the offsets checked (an absurd nseg is refused before offsets[nseg] is read).
+// `slot_flags(cap)` is the size of a staging slot in uint16 for chunks of at most `cap` elements; `chunk_fn(e, buf, sl, pos, c,
+// cap, grid)` copies the inputs of elements [pos, pos + c) into e.stage[sl] and launches on e.stream[sl]; every chunk's launch
+// adds the pieces of the segments it holds to the same device rows (`words` uint64 per segment, zeroed in front).
+template <typename Last, typename SlotFlags, typename Chunk, typename Apply>
+int host_call(uint64_t n, const uint64_t* offsets, uint64_t nseg, uint64_t words, uint64_t chunk, Last&& last_fn, SlotFlags&& slot_flags,
+              Chunk&& chunk_fn, Apply&& apply_fn)
+{
+    int rc;
+    fsint::Engine* ep = fsint::default_engine();
+    if (!ep) return -1;
+    fsint::Engine& e = *ep;
+    std::lock_guard<std::mutex> lk(e.mu);
+    if (fsint::engine_alive(e)) return -1;
+    fsint::DeviceGuard guard(e.device);
+    if (!guard.ok()) return -1;
+    fsint::lz4_gpu_other_use(e);
+    SegBuffers buf;
+    HostRows got;
+    if ((rc = buf.alloc(nseg, words)) || (rc = got.alloc(nseg, words))) return rc;
+    if ((rc = check_host_offsets(offsets, nseg, n))) return rc;
+    if ((rc = fsint::engine_second(e))) return rc;
+    const uint64_t first = offsets[0], last = last_fn();
+    const uint64_t cap = last - first < chunk ? (last - first ? last - first : 1) : chunk;   // elements of the largest chunk
+    const int slots = last - first > chunk ? 2 : 1;
+    for (int i = 0; i < slots; ++i)
+        if ((rc = fsint::stage_reserve(e, i, slot_flags(cap)))) return rc;
+    hipStream_t s0 = e.stream[0];
+    FS_HIP_TRY(hipMemsetAsync(buf.cnt, 0, nseg * words * sizeof(uint64_t), s0));
+    FS_HIP_TRY(hipMemcpyAsync(buf.off, offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s0));
+    if (slots == 2 && (rc = fsint::stream_wait_stream(e, e.stream[1], s0))) return rc;
+    const uint32_t grid = seg_grid(e);
+    uint64_t k = 0;
+    for (uint64_t pos = first; pos < last; pos += chunk, ++k) {
+        const int sl = static_cast<int>(k % static_cast<uint64_t>(slots));
+        const uint64_t c = last - pos < chunk ? last - pos : chunk;
+        if ((rc = chunk_fn(e, buf, sl, pos, c, cap, grid))) return rc;
+    }
+    if (slots == 2 && (rc = fsint::stream_wait_stream(e, s0, e.stream[1]))) return rc;
+    FS_HIP_TRY(hipMemcpyAsync(got.p.get(), buf.cnt, got.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s0));
+    FS_HIP_TRY(hipStreamSynchronize(s0));
+    if (slots == 2) FS_HIP_TRY(hipStreamSynchronize(e.stream[1]));
+    apply_fn(got);
+    return 0;
 }
 
 }  // namespace fsseg

@@ -12,10 +12,11 @@
 // from the byte of the chunk's element 0 on, to fsk::flagstat_segments_filter<true> as its MAPQ column
 // (fsk_launch_segments_filter), whose loaders touch only bytes of elements.
 //
-// Work split, walk, window and emission.  The segmented kernels', unchanged (tests/segments_oracle.WriterSplit mirrors them):
+// Work split, walk, window and emission.  The segmented kernels' shared ones (tests/segments_oracle.WriterSplit mirrors them):
 // units of 4096 flags on the 16-byte grid of the array's aligned-down base, every wave a writer over a contiguous run of units,
 // lane l of a row takes vector row * 64 + l, the 64-ary search for a writer's first segment, the window of 64 offsets, plain
-// stores in the store form for rows that lie inside one writer (flagstat_segments_shared.h; the emission is segf_emit's).
+// stores in the store form for rows that lie inside one writer (seg_walk<kSegWaveFlags> and seg_emit<true, false> of
+// flagstat_segments_shared.h).
 //
 // Selection.  Addressed like the `where` kernel's: the launcher hands over a base `sel` such that the 8 bits of grid vector j
 // start at bit `sh` of sel[j] (sh == 0: one byte per vector; otherwise two bytes funnelled together: FUNNEL).  A zero flag
@@ -35,8 +36,6 @@
 // The table is built by the workgroup's 256 threads and the barrier behind it is passed before any wave returns early.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <mutex>
 
 #include "../../include/libflagstats_hip.h"
 #include "flagstat_count_core.h"
@@ -111,135 +110,67 @@ __global__ __launch_bounds__(kThreads) void flagstat_segments_where(const uint4*
     lut[threadIdx.x] = selector_entry(threadIdx.x);
     __syncthreads();  // the only workgroup barrier: behind it waves return and walk on their own
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = threadIdx.x >> 6;
-    const uint64_t waves = static_cast<uint64_t>(gridDim.x) * (kThreads / 64);
-    const uint64_t gw = static_cast<uint64_t>(blockIdx.x) * (kThreads / 64) + wave;
-    const uint64_t u_begin = gw * nunits / waves, u_end = (gw + 1) * nunits / waves;
-    const uint64_t p0 = u_begin * kSegWaveFlags > lo0 ? u_begin * kSegWaveFlags : lo0;  // this writer: grid positions [p0, E)
-    const uint64_t E = u_end * kSegWaveFlags < hi0 ? u_end * kSegWaveFlags : hi0;
-    if (p0 >= E) return;
-    uint32_t* red = red_all[wave];
-
-    SegWalk sw{off, nseg, base, hi0 - lo0, lo0, lane, 0, 0, 0};
-    uint64_t s = sw.first_segment(p0);
-    if (s >= nseg) return;
-    sw.load_window(s);
-
+    uint32_t* red = red_all[threadIdx.x >> 6];
     const uint32_t sh = FUNNEL ? __builtin_amdgcn_readfirstlane(shift) : 0u;
     Lane<kSegFilterDepth> st;
     lane_init(st);
     uint32_t blk = 0;
-    uint32_t cnt = 0;   // selected flags of this lane in segment s not yet emitted
-    bool open = false;  // st and cnt hold counts of segment s not yet emitted
-    uint64_t sb = 0, se = 0;
-    auto emit = [&](uint64_t seg, uint64_t b_, uint64_t e_) {
-        segf_emit(st, blk, cnt, red, out, selected, seg, (mode & 1) && b_ >= p0 && e_ <= E, mode, lane);
-    };
-
-    uint64_t u = p0 / kSegWaveFlags;
-    while (s < nseg && u < u_end) {
-        sw.bounds(s, sb, se);
-        const uint64_t w0 = u * kSegWaveFlags;
-        const uint64_t x = w0 > p0 ? w0 : p0;
-        // (the order of these tests: flagstat_segments_filter.hip)
-        if (sb >= E) break;
-        if (se <= sb || se <= x) {  // empty (or, with malformed offsets, reversed or behind)
-            ++s;
-            continue;
-        }
-        if (sb >= w0 + kSegWaveFlags) {  // flags before the segment belong to none: skip whole units unread
-            u = sb / kSegWaveFlags;
-            continue;
-        }
-        const uint64_t seg_e = se < E ? se : E;
-        if (sb <= w0 && w0 >= lo0) {
-            const uint64_t k = (seg_e - w0) / kSegWaveFlags;  // whole units of segment s from here on
-            if (k >= min_units && k > 0) {
-                const uint4* p = a0 + u * kSegUnitVecs + lane;
-                const uint8_t* ps = sel + u * kSegUnitVecs + lane;
-                uint4 v[kUnroll];
-                uint32_t m[kUnroll];
-                // the first kRollDistance vectors, the selection bytes one vector ahead of them
-                m[0] = load_sel<1, FUNNEL>(ps);
+    uint32_t cnt = 0;   // selected flags of this lane in the open segment
+    uint32_t none = 0;  // no mask
+    uint4 v[kUnroll];
+    uint32_t m[kUnroll];
+    seg_walk<kSegWaveFlags>(
+        lo0, hi0, base, off, nseg, mode, nunits, min_units,
+        [&](uint64_t u, uint64_t k) __attribute__((always_inline)) {
+            const uint4* p = a0 + u * kSegUnitVecs + lane;
+            const uint8_t* ps = sel + u * kSegUnitVecs + lane;
+            // the first kRollDistance vectors, the selection bytes one vector ahead of them
+            m[0] = load_sel<1, FUNNEL>(ps);
 #pragma unroll
-                for (int r = 0; r < kRollDistance; ++r) {
-                    m[r + 1] = load_sel<1, FUNNEL>(ps + (r + 1) * kSegRowVecs);
-                    v[r] = load_vec<true>(p + r * kSegRowVecs);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                // entering a chain run: whatever came before (a per-flag unit, a skipped stretch, another run) left no entry
-                uint4 entry = lookup(lut, m[0], sh, cnt);
-                for (uint64_t i = 1; i < k; ++i) {
-                    const uint4* pn = p + kSegUnitVecs;
-                    const uint8_t* psn = ps + kSegUnitVecs;
-                    segw_step_and_count<FUNNEL, true>(st, v, m, entry, lut, blk, sh, cnt, p, pn, ps, psn);
-                    p = pn;
-                    ps = psn;
-                }
-                segw_step_and_count<FUNNEL, false>(st, v, m, entry, lut, blk, sh, cnt, p, nullptr, ps, nullptr);
-                u += k;
-                open = true;
-                if (u * kSegWaveFlags >= se) {
-                    emit(s, sb, se);
-                    open = false;
-                    ++s;
-                }
-                continue;
+            for (int r = 0; r < kRollDistance; ++r) {
+                m[r + 1] = load_sel<1, FUNNEL>(ps + (r + 1) * kSegRowVecs);
+                v[r] = load_vec<true>(p + r * kSegRowVecs);
+                __builtin_amdgcn_sched_barrier(0);
             }
-        }
-        // per-flag unit: its 8 rows and their selection bits loaded at once, then every segment piece in it
-        uint4 v[kUnroll];
-        uint32_t m[kUnroll];
-        const uint64_t j0 = u * kSegUnitVecs + lane;
-        if (w0 >= lo0 && w0 + kSegWaveFlags <= hi0) {
+            // entering a chain run: whatever came before (a per-flag unit, a skipped stretch, another run) left no entry
+            uint4 entry = lookup(lut, m[0], sh, cnt);
+            for (uint64_t i = 1; i < k; ++i) {
+                const uint4* pn = p + kSegUnitVecs;
+                const uint8_t* psn = ps + kSegUnitVecs;
+                segw_step_and_count<FUNNEL, true>(st, v, m, entry, lut, blk, sh, cnt, p, pn, ps, psn);
+                p = pn;
+                ps = psn;
+            }
+            segw_step_and_count<FUNNEL, false>(st, v, m, entry, lut, blk, sh, cnt, p, nullptr, ps, nullptr);
+        },
+        [&](uint64_t u, bool whole) __attribute__((always_inline)) {
+            const uint64_t j0 = u * kSegUnitVecs + lane;
+            if (whole) {
 #pragma unroll
-            for (int r = 0; r < kUnroll; ++r) {
-                v[r] = load_vec<true>(a0 + j0 + r * kSegRowVecs);
-                m[r] = __builtin_amdgcn_ubfe(load_sel<1, FUNNEL>(sel + j0 + r * kSegRowVecs), sh, 8);
-            }
-        } else {
+                for (int r = 0; r < kUnroll; ++r) {
+                    v[r] = load_vec<true>(a0 + j0 + r * kSegRowVecs);
+                    m[r] = __builtin_amdgcn_ubfe(load_sel<1, FUNNEL>(sel + j0 + r * kSegRowVecs), sh, 8);
+                }
+            } else {
 #pragma unroll
-            for (int r = 0; r < kUnroll; ++r) {
-                v[r] = load_guarded(a0, j0 + r * kSegRowVecs, lo0, hi0);
-                m[r] = load_sel_guarded<1>(sel, sh, j0 + r * kSegRowVecs, lo0, hi0);
+                for (int r = 0; r < kUnroll; ++r) {
+                    v[r] = load_guarded(a0, j0 + r * kSegRowVecs, lo0, hi0);
+                    m[r] = load_sel_guarded<1>(sel, sh, j0 + r * kSegRowVecs, lo0, hi0);
+                }
             }
-        }
-        const uint64_t w1 = w0 + kSegWaveFlags;
-        uint64_t xx = x;
-        for (;;) {
-            // s < nseg, sb < se, se > xx, sb < w1; the piece [b, e) lies inside [p0, E) and so inside [lo0, hi0)
-            const uint64_t b = sb > xx ? sb : xx, e = se < w1 ? se : w1;
+        },
+        [&](uint64_t w0, uint64_t b, uint64_t e) __attribute__((always_inline)) {
             count_piece_where(st.acc, cnt, lut, v, m, w0, b, e, lane);
-            open = true;
-            if (e < se) break;  // segment s goes on in the next unit
-            emit(s, sb, se);
-            open = false;
-            ++s;
-            xx = e;
-            bool more = false;
-            while (s < nseg) {
-                sw.bounds(s, sb, se);
-                if (sb >= E) break;  // (as in the outer walk: before the empty test)
-                if (se <= sb || se <= xx) {
-                    ++s;
-                    continue;
-                }
-                more = sb < w1;
-                break;
-            }
-            if (!more) break;
-        }
-        ++u;
-    }
-    if (open) emit(s, sb, se);  // this writer's range ends inside segment s
+        },
+        [&](uint64_t s, uint64_t len, bool plain) __attribute__((always_inline)) {
+            seg_emit<true, false>(st, blk, cnt, none, none, red, out, selected, nullptr, s, len, plain, mode, lane);
+        });
 }
 
 }  // namespace fsk
 
 // ------------------------------------------------------------------ launcher
 using fsdrv::where_extent;
-using fsseg::launch_shape;
-using fsseg::wave_totals_fit;
 
 // Host-side geometry.  Grid position q is element q - lo0 of the chunk and so bit or byte sel_offset + q - lo0 of d_sel.
 // Bytes: that is base[q] with base = d_sel + sel_offset - lo0.  Bitmap: bit q + (bit0 - 8) with bit0 = sel_offset + 8 - lo0 >= 1,
@@ -255,8 +186,8 @@ extern "C" hipError_t fsk_segments_where_geometry(uint64_t address, uint64_t m, 
     if (sel_offset > ~0ull - 64 - m) return hipErrorInvalidValue;  // sel_offset + m must be an index
     uint64_t lo0 = 0, nunits = 0;
     uint32_t g = 0;
-    launch_shape(static_cast<uintptr_t>(address), m, grid, &lo0, &nunits, &g);
-    if (!wave_totals_fit(nunits, g)) return hipErrorInvalidValue;
+    fsseg::launch_shape(static_cast<uintptr_t>(address), m, fsk::kSegWaveFlags, grid, &lo0, &nunits, &g);
+    if (!fsseg::wave_totals_fit(nunits, g, fsk::kSegWaveFlags)) return hipErrorInvalidValue;
     uint64_t first, bytes;
     where_extent(m, sel_offset, sel_bits, &first, &bytes);
     geo[0] = lo0;
@@ -312,11 +243,9 @@ extern "C" hipError_t fsk_launch_segments_where(const uint16_t* d_chunk, const v
 }
 
 // ------------------------------------------------------------------ C entry points (include/libflagstats_hip.h)
-using fsint::DeviceGuard;
+// The bodies of the three forms are fsseg's (flagstat_segments_shared.h): 33 words per segment, the rows, then the selected counts.
 using fsint::Engine;
 using fsint::fail_text;
-using fsseg::apply_both;
-using fsseg::seg_grid;
 
 namespace {
 
@@ -334,17 +263,6 @@ int segw_args(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint64
     if (reinterpret_cast<uintptr_t>(array) & 1u) return fail_text("array must be 2-byte aligned");
     if (n > (~0ull - 64) / 2) return fail_text("n * 2 is not a size");
     if (sel_offset > ~0ull - 64 - n) return fail_text("sel_offset + n is not an index");
-    return 0;
-}
-
-int segw_fits(const uint16_t* array, uint64_t n, uint32_t grid)
-{
-    if (n == 0) return 0;
-    uint64_t lo0 = 0, nunits = 0;
-    uint32_t g = 0;
-    launch_shape(reinterpret_cast<uintptr_t>(array), n, grid, &lo0, &nunits, &g);
-    if (!wave_totals_fit(nunits, g))
-        return fail_text("n is too large for this grid: a wave's uint32 totals could overflow (split the array)");
     return 0;
 }
 
@@ -371,18 +289,13 @@ int FLAGSTATS_hip_device_u16_segments_where(const uint16_t* d_array, uint64_t n,
     const fsdrv::Input in[] = {{d_offsets, "d_offsets", (nseg + 1) * sizeof(uint64_t)},
                                {d_array, "d_array", n * 2},
                                {d_sel, "d_sel", n ? sel_bytes(n, sel_offset, sel_bits) : 0}};
-    const int inputs = n ? 3 : 1;
-    fsdrv::DeviceCall call;
-    if ((rc = call.open(d_out, word, in, inputs, stream))) return rc;
-    const uint32_t grid = seg_grid(*call.e);
-    if ((rc = segw_fits(d_array, n, grid))) return rc;
-    if ((rc = fsint::check_extent(d_out, nseg * 32 * sizeof(uint64_t), "d_out"))) return rc;
-    if (d_selected && (rc = fsint::check_extent(d_selected, nseg * sizeof(uint64_t), "d_selected"))) return rc;
-    for (int i = 0; i < inputs; ++i)
-        if ((rc = fsint::check_extent(in[i].p, in[i].bytes, in[i].name))) return rc;
-    FS_HIP_TRY(fsk_launch_segments_where(d_array, d_sel, sel_offset, sel_bits, 0, n, d_offsets, nseg, d_out, d_selected, flags & 3, grid,
-                                         call.s));
-    return 0;
+    return fsseg::device_call(
+        d_out, &word, 1, in, n ? 3 : 1, nseg, stream, [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWaveFlags, grid); },
+        [&](uint32_t grid, hipStream_t s) {
+            FS_HIP_TRY(fsk_launch_segments_where(d_array, d_sel, sel_offset, sel_bits, 0, n, d_offsets, nseg, d_out, d_selected, flags & 3,
+                                                 grid, s));
+            return 0;
+        });
 }
 
 int FLAGSTATS_hip_device_u16_segments_where_sync(const uint16_t* d_array, uint64_t n, const uint64_t* offsets, uint64_t nseg,
@@ -392,38 +305,15 @@ int FLAGSTATS_hip_device_u16_segments_where_sync(const uint16_t* d_array, uint64
     FS_ENTRY();
     int rc = segw_args(d_array, n, offsets, nseg, d_sel, sel_offset, sel_bits, out, flags, "NULL offsets or out with nseg > 0");
     if (rc || nseg == 0) return rc;
-    Engine* ep = nullptr;
-    if (n) {
-        int dev = -1, dev_s = -1;
-        if ((rc = fsint::device_of_pointer(d_array, "d_array", &dev))) return rc;
-        if ((rc = fsint::device_of_pointer(d_sel, "d_sel", &dev_s))) return rc;
-        if (dev_s != dev) return fsdrv::fail_devices("d_sel", "d_array");
-        ep = fsint::engine_for_device(dev);
-    } else {
-        ep = fsint::default_engine();
-    }
-    if (!ep) return -1;
-    Engine& e = *ep;
-    std::lock_guard<std::mutex> lk(e.mu);
-    if (fsint::engine_alive(e)) return -1;
-    DeviceGuard guard(e.device);
-    if (!guard.ok()) return -1;
-    const uint32_t grid = seg_grid(e);
-    if ((rc = segw_fits(d_array, n, grid))) return rc;
-    fsseg::SegBuffers buf;     // rows, then the selected counts
-    fsseg::HostRows got;
-    if ((rc = buf.alloc(nseg, 33)) || (rc = got.alloc(nseg, 33))) return rc;
-    if ((rc = fsseg::check_host_offsets(offsets, nseg, n))) return rc;
-    if (n && (rc = fsint::check_extent(d_array, n * sizeof(uint16_t), "d_array"))) return rc;
-    if (n && (rc = fsint::check_extent(d_sel, sel_bytes(n, sel_offset, sel_bits), "d_sel"))) return rc;
-    hipStream_t s = e.stream[0];
-    FS_HIP_TRY(hipMemcpyAsync(buf.off, offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    FS_HIP_TRY(fsk_launch_segments_where(d_array, d_sel, sel_offset, sel_bits, 0, n, buf.off, nseg, buf.cnt, buf.cnt + nseg * 32,
-                                         1 | (flags & 2), grid, s));
-    FS_HIP_TRY(hipMemcpyAsync(got.p.get(), buf.cnt, got.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    FS_HIP_TRY(hipStreamSynchronize(s));
-    apply_both(out, selected, got, nseg, flags);
-    return 0;
+    const fsdrv::Input in[] = {{d_array, "d_array", n * sizeof(uint16_t)}, {d_sel, "d_sel", n ? sel_bytes(n, sel_offset, sel_bits) : 0}};
+    return fsseg::sync_call(
+        in, n ? 2 : 0, n, offsets, nseg, 33, [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWaveFlags, grid); },
+        [&](fsseg::SegBuffers& buf, uint32_t grid, hipStream_t s) {
+            FS_HIP_TRY(fsk_launch_segments_where(d_array, d_sel, sel_offset, sel_bits, 0, n, buf.off, nseg, buf.cnt, buf.cnt + nseg * 32,
+                                                 1 | (flags & 2), grid, s));
+            return 0;
+        },
+        [&](const fsseg::HostRows& got) { fsseg::apply_both(out, selected, got, nseg, flags); });
 }
 
 int FLAGSTATS_hip_u16_x64_segments_where(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint64_t nseg, const void* sel,
@@ -432,56 +322,24 @@ int FLAGSTATS_hip_u16_x64_segments_where(const uint16_t* array, uint64_t n, cons
     FS_ENTRY();
     int rc = segw_args(array, n, offsets, nseg, sel, sel_offset, sel_bits, out, flags, "NULL offsets or out with nseg > 0");
     if (rc || nseg == 0) return rc;
-    Engine* ep = fsint::default_engine();
-    if (!ep) return -1;
-    Engine& e = *ep;
-    std::lock_guard<std::mutex> lk(e.mu);
-    if (fsint::engine_alive(e)) return -1;
-    DeviceGuard guard(e.device);
-    if (!guard.ok()) return -1;
-    fsint::lz4_gpu_other_use(e);
-    fsseg::SegBuffers buf;     // rows, then the selected counts
-    fsseg::HostRows got;
-    if ((rc = buf.alloc(nseg, 33)) || (rc = got.alloc(nseg, 33))) return rc;
-    if ((rc = fsseg::check_host_offsets(offsets, nseg, n))) return rc;
-    if ((rc = fsint::engine_second(e))) return rc;
-    // only what some segment covers crosses the bus: [offsets[0], offsets[nseg]) of the array and the selection bytes that cover
-    // it, in chunks of "chunk_flags", alternating between the engine's two streams and staging buffers; a chunk's slice of the
-    // selection rides in the same staging buffer, behind the flags -- a bitmap slice from the byte that holds the chunk's first bit
-    // (the launch then starts (sel_offset + pos) & 7 bits into it); every chunk's launch adds its pieces to the same device rows
-    // and counts
-    const uint64_t chunk = fsdrv::chunk_flags();
-    const uint64_t first = offsets[0], last = offsets[nseg];
-    const uint64_t cap = last - first < chunk ? (last - first ? last - first : 1) : chunk;   // flags of the largest chunk
-    const uint64_t sel_cap = sel_bits == 1 ? (cap + 7) / 8 + 1 : cap;                        // bytes of its slice
-    const int slots = last - first > chunk ? 2 : 1;
-    for (int i = 0; i < slots; ++i)
-        if ((rc = fsint::stage_reserve(e, i, cap + (sel_cap + 1) / 2))) return rc;
-    hipStream_t s0 = e.stream[0];
-    FS_HIP_TRY(hipMemsetAsync(buf.cnt, 0, nseg * 33 * sizeof(uint64_t), s0));
-    FS_HIP_TRY(hipMemcpyAsync(buf.off, offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s0));
-    if (slots == 2 && (rc = fsint::stream_wait_stream(e, e.stream[1], s0))) return rc;
-    const uint32_t grid = seg_grid(e);
+    // a chunk's slice of the selection rides in the same staging buffer, behind the flags -- a bitmap slice from the byte that
+    // holds the chunk's first bit (the launch then starts (sel_offset + pos) & 7 bits into it)
     const int mode = flags & 2;
     const uint8_t* sel_src = static_cast<const uint8_t*>(sel);
-    uint64_t k = 0;
-    for (uint64_t pos = first; pos < last; pos += chunk, ++k) {
-        const int sl = static_cast<int>(k % static_cast<uint64_t>(slots));
-        const uint64_t c = last - pos < chunk ? last - pos : chunk;
-        uint64_t sel_first, sel_len;
-        where_extent(c, sel_offset + pos, sel_bits, &sel_first, &sel_len);
-        uint8_t* d_sel = reinterpret_cast<uint8_t*>(e.stage[sl] + cap);
-        FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], array + pos, c * sizeof(uint16_t), hipMemcpyHostToDevice, e.stream[sl]));
-        FS_HIP_TRY(hipMemcpyAsync(d_sel, sel_src + sel_first, sel_len, hipMemcpyHostToDevice, e.stream[sl]));
-        FS_HIP_TRY(fsk_launch_segments_where(e.stage[sl], d_sel, sel_bits == 1 ? (sel_offset + pos) & 7 : 0, sel_bits, pos, c, buf.off, nseg,
-                                             buf.cnt, buf.cnt + nseg * 32, mode, grid, e.stream[sl]));
-    }
-    if (slots == 2 && (rc = fsint::stream_wait_stream(e, s0, e.stream[1]))) return rc;
-    FS_HIP_TRY(hipMemcpyAsync(got.p.get(), buf.cnt, got.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s0));
-    FS_HIP_TRY(hipStreamSynchronize(s0));
-    if (slots == 2) FS_HIP_TRY(hipStreamSynchronize(e.stream[1]));
-    apply_both(out, selected, got, nseg, flags);
-    return 0;
+    return fsseg::host_call(
+        n, offsets, nseg, 33, fsdrv::chunk_flags(), [&] { return offsets[nseg]; },
+        [&](uint64_t cap) { return cap + ((sel_bits == 1 ? (cap + 7) / 8 + 1 : cap) + 1) / 2; },
+        [&](Engine& e, fsseg::SegBuffers& buf, int sl, uint64_t pos, uint64_t c, uint64_t cap, uint32_t grid) {
+            uint64_t sel_first, sel_len;
+            where_extent(c, sel_offset + pos, sel_bits, &sel_first, &sel_len);
+            uint8_t* d_sel = reinterpret_cast<uint8_t*>(e.stage[sl] + cap);
+            FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], array + pos, c * sizeof(uint16_t), hipMemcpyHostToDevice, e.stream[sl]));
+            FS_HIP_TRY(hipMemcpyAsync(d_sel, sel_src + sel_first, sel_len, hipMemcpyHostToDevice, e.stream[sl]));
+            FS_HIP_TRY(fsk_launch_segments_where(e.stage[sl], d_sel, sel_bits == 1 ? (sel_offset + pos) & 7 : 0, sel_bits, pos, c, buf.off,
+                                                 nseg, buf.cnt, buf.cnt + nseg * 32, mode, grid, e.stream[sl]));
+            return 0;
+        },
+        [&](const fsseg::HostRows& got) { fsseg::apply_both(out, selected, got, nseg, flags); });
 }
 
 }  // extern "C"

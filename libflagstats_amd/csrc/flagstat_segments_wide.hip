@@ -1,8 +1,8 @@
 // flagstat_segments_wide.hip -- segmented flagstat of a FLAG array held as 4-byte or 8-byte little-endian integers (int32 / int64
 // columns), read in place: one row of 32 counters per CSR segment, counted from the low 16 bits of its elements exactly as the
 // uint16 segmented kernel counts them, and per segment the OR of every bit above bit 15 that one of ITS elements carries, in one
-// launch.  The segmented kernel's work split, walk and emission (flagstat_segments.hip) over the wide kernel's read-out of an
-// element (flagstat_wide.hip).
+// launch.  The segmented kernels' work split, walk and emission (seg_walk<UE> and seg_emit<false, true> of
+// flagstat_segments_shared.h) over the wide kernel's read-out of an element (flagstat_wide.hip).
 //
 // Geometry.  The array is addressed on the 16-byte grid of its aligned-down base; positions are elements of W bytes.  A wave's
 // unit stays 8 KiB -- 8 rows of 64 lanes x 16 B, 2048 elements at W = 4 and 1024 at W = 8, exactly one wave's share of a wide-kernel
@@ -25,8 +25,6 @@
 // agent-scope atomic OR, only if the word is non-zero.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <mutex>
 
 #include "../../include/libflagstats_hip.h"
 #include "flagstat_count_core.h"
@@ -64,51 +62,6 @@ __device__ __forceinline__ void count_piece_wide(uint32_t (&acc)[kInternal], uin
                              [](int, uint32_t&, uint32_t&, uint32_t&, uint32_t&) __attribute__((always_inline)) {});
 }
 
-// the wave's counters of the piece of segment s it holds -> out[s][32], and the piece's mask -> high[s]
-__device__ __forceinline__ void segw_emit(Lane<kSegWideDepth>& st, uint32_t& blk, uint32_t& or_even, uint32_t& or_odd, uint32_t* red,
-                                          uint64_t* __restrict__ out, uint64_t* __restrict__ high, uint64_t s, uint64_t len, bool plain,
-                                          int mode, uint32_t lane)
-{
-    if (blk) {
-        flush(st, blk);
-        blk = 0;
-    }
-    uint32_t w[kInternal];
-#pragma unroll
-    for (int c = 0; c < kInternal; ++c) {
-        w[c] = wave_sum_lane63(st.acc[c]);
-        st.acc[c] = 0;
-    }
-    const uint32_t we = wave_or_lane63(or_even & 0xFFFF0000u);   // the even-dword stream: bits 16-31 of every element
-    const uint32_t wo = wave_or_lane63(or_odd);                   // W = 8: bits 32-63
-    or_even = 0;
-    or_odd = 0;
-    if (lane == 63) {
-#pragma unroll
-        for (int c = 0; c < kInternal; ++c) red[c] = w[c];
-        red[kInternal] = we;
-        red[kInternal + 1] = wo;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (lane < 32) {
-        const uint64_t add = seg_slot_value(red, lane, mode, len);
-        uint64_t* o = out + s * 32 + lane;
-        if (plain)
-            *o = add;  // store form, the whole segment in this wave: all 32 slots
-        else if (add)
-            (void)__hip_atomic_fetch_add(o, add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else if (lane == 32 && high != nullptr) {
-        const uint64_t m = (static_cast<uint64_t>(red[kInternal + 1]) << 32) | red[kInternal];
-        if (plain)
-            high[s] = m;
-        else if (m)
-            (void)__hip_atomic_fetch_or(high + s, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __builtin_amdgcn_wave_barrier();  // red[] is rewritten by the next segment's totals only after every lane has read it
-}
-
 // a0: 16-B aligned-down base; the chunk's elements occupy grid positions [lo0, hi0) (elements of W bytes) and are global elements
 // [base, base + hi0 - lo0).  nunits = ceil(hi0 / (8192 / W)).  mode: bit 0 store form (out[] and high[] zeroed in front), bit 1
 // superset.  high may be nullptr.
@@ -122,137 +75,50 @@ __global__ __launch_bounds__(kThreads) void flagstat_segments_wide(const uint4* 
     constexpr uint64_t UE = kSegWideUnitBytes / W;   // elements per unit
     __shared__ uint32_t red_all[kThreads / 64][24];
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = threadIdx.x >> 6;
-    const uint64_t waves = static_cast<uint64_t>(gridDim.x) * (kThreads / 64);
-    const uint64_t gw = static_cast<uint64_t>(blockIdx.x) * (kThreads / 64) + wave;
-    const uint64_t u_begin = gw * nunits / waves, u_end = (gw + 1) * nunits / waves;
-    const uint64_t p0 = u_begin * UE > lo0 ? u_begin * UE : lo0;  // this writer: grid positions [p0, E)
-    const uint64_t E = u_end * UE < hi0 ? u_end * UE : hi0;
-    if (p0 >= E) return;
-    uint32_t* red = red_all[wave];
-
-    SegWalk sw{off, nseg, base, hi0 - lo0, lo0, lane, 0, 0, 0};
-    uint64_t s = sw.first_segment(p0);
-    if (s >= nseg) return;
-    sw.load_window(s);
-
+    uint32_t* red = red_all[threadIdx.x >> 6];
     Lane<kSegWideDepth> st;
     lane_init(st);
     uint32_t blk = 0;
-    uint32_t or_even = 0, or_odd = 0;   // dwords of segment s's elements not yet emitted
-    bool open = false;                  // st and the mask accumulators hold segment s's, not yet emitted
-    uint64_t sb = 0, se = 0;
-    auto emit = [&](uint64_t seg, uint64_t b_, uint64_t e_) {
-        const uint64_t pb = b_ > p0 ? b_ : p0, pe = e_ < E ? e_ : E;
-        segw_emit(st, blk, or_even, or_odd, red, out, high, seg, pe - pb, (mode & 1) && b_ >= p0 && e_ <= E, mode, lane);
-    };
-
-    uint64_t u = p0 / UE;
-    while (s < nseg && u < u_end) {
-        sw.bounds(s, sb, se);
-        const uint64_t w0 = u * UE;
-        const uint64_t x = w0 > p0 ? w0 : p0;
-        // (the order of these tests is flagstat_segments.hip's, for its reasons)
-        if (sb >= E) break;
-        if (se <= sb || se <= x) {  // empty (or, with malformed offsets, reversed or behind)
-            ++s;
-            continue;
-        }
-        if (sb >= w0 + UE) {  // elements before the segment belong to none: skip whole units unread
-            u = sb / UE;
-            continue;
-        }
-        const uint64_t seg_e = se < E ? se : E;
-        if (sb <= w0 && w0 >= lo0) {
-            const uint64_t k = (seg_e - w0) / UE;  // whole units of segment s from here on
-            if (k >= min_units && k > 0) {
-                const uint4* p = a0 + u * kSegUnitVecs + lane;
-                uint4 v[kUnroll];
+    uint32_t or_even = 0, or_odd = 0;   // dwords of the open segment's elements
+    uint32_t none = 0;                  // no passing count
+    uint4 v[kUnroll];
+    seg_walk<UE>(
+        lo0, hi0, base, off, nseg, mode, nunits, min_units,
+        [&](uint64_t u, uint64_t k) __attribute__((always_inline)) {
+            const uint4* p = a0 + u * kSegUnitVecs + lane;
 #pragma unroll
-                for (int r = 0; r < kRollDistance; ++r) {
-                    v[r] = load_vec<true>(p + r * kSegRowVecs);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                for (uint64_t i = 1; i < k; ++i) {
-                    const uint4* pn = p + kSegUnitVecs;
-                    segw_step_and_count<W, true>(st, v, blk, or_even, or_odd, p, pn);
-                    p = pn;
-                }
-                segw_step_and_count<W, false>(st, v, blk, or_even, or_odd, p, nullptr);
-                u += k;
-                open = true;
-                if (u * UE >= se) {
-                    emit(s, sb, se);
-                    open = false;
-                    ++s;
-                }
-                continue;
+            for (int r = 0; r < kRollDistance; ++r) {
+                v[r] = load_vec<true>(p + r * kSegRowVecs);
+                __builtin_amdgcn_sched_barrier(0);
             }
-        }
-        // per-piece unit: its 8 rows loaded at once, then every segment piece in it
-        uint4 v[kUnroll];
-        const uint64_t j0 = u * kSegUnitVecs + lane;
-        if (w0 >= lo0 && w0 + UE <= hi0) {
+            for (uint64_t i = 1; i < k; ++i) {
+                const uint4* pn = p + kSegUnitVecs;
+                segw_step_and_count<W, true>(st, v, blk, or_even, or_odd, p, pn);
+                p = pn;
+            }
+            segw_step_and_count<W, false>(st, v, blk, or_even, or_odd, p, nullptr);
+        },
+        [&](uint64_t u, bool whole) __attribute__((always_inline)) {
+            const uint64_t j0 = u * kSegUnitVecs + lane;
+            if (whole) {
 #pragma unroll
-            for (int r = 0; r < kUnroll; ++r) v[r] = load_vec<true>(a0 + j0 + r * kSegRowVecs);
-        } else {
+                for (int r = 0; r < kUnroll; ++r) v[r] = load_vec<true>(a0 + j0 + r * kSegRowVecs);
+            } else {
 #pragma unroll
-            for (int r = 0; r < kUnroll; ++r) v[r] = load_guarded_wide<W>(a0, j0 + r * kSegRowVecs, lo0, hi0);
-        }
-        const uint64_t w1 = w0 + UE;
-        uint64_t xx = x;
-        for (;;) {
-            // s < nseg, sb < se, se > xx, sb < w1; the piece [b, e) lies inside [p0, E) and so inside [lo0, hi0)
-            const uint64_t b = sb > xx ? sb : xx, e = se < w1 ? se : w1;
+                for (int r = 0; r < kUnroll; ++r) v[r] = load_guarded_wide<W>(a0, j0 + r * kSegRowVecs, lo0, hi0);
+            }
+        },
+        [&](uint64_t w0, uint64_t b, uint64_t e) __attribute__((always_inline)) {
             count_piece_wide<W>(st.acc, or_even, or_odd, v, w0, b, e, lane);
-            open = true;
-            if (e < se) break;  // segment s goes on in the next unit
-            emit(s, sb, se);
-            open = false;
-            ++s;
-            xx = e;
-            bool more = false;
-            while (s < nseg) {
-                sw.bounds(s, sb, se);
-                if (sb >= E) break;  // (as in the outer walk: before the empty test)
-                if (se <= sb || se <= xx) {
-                    ++s;
-                    continue;
-                }
-                more = sb < w1;
-                break;
-            }
-            if (!more) break;
-        }
-        ++u;
-    }
-    if (open) emit(s, sb, se);  // this writer's range ends inside segment s
+        },
+        [&](uint64_t s, uint64_t len, bool plain) __attribute__((always_inline)) {
+            seg_emit<false, true>(st, blk, none, or_even, or_odd, red, out, nullptr, high, s, len, plain, mode, lane);
+        });
 }
 
 }  // namespace fsk
 
 // ------------------------------------------------------------------ launcher
-namespace {
-
-// a wave's totals are uint32: every wave must own fewer than 2^32 elements
-bool wave_totals_fit(uint64_t nunits, uint32_t g, uint64_t unit_elems)
-{
-    const uint64_t waves = static_cast<uint64_t>(g) * (fsk::kThreads / 64);
-    return (nunits + waves - 1) / waves < (1ull << 32) / unit_elems;
-}
-
-// units and workgroups of a launch over m > 0 elements of W bytes at `addr` with at most `grid` workgroups
-void launch_shape(uintptr_t addr, uint64_t m, uint64_t W, uint32_t grid, uint64_t* lo0, uint64_t* nunits, uint32_t* g)
-{
-    const uint64_t ue = fsk::kSegWideUnitBytes / W;
-    *lo0 = (addr & 15u) / W;
-    *nunits = (*lo0 + m + ue - 1) / ue;
-    const uint64_t want = (*nunits + 3) / 4;  // one unit per wave at least
-    *g = want < grid ? static_cast<uint32_t>(want) : grid;
-}
-
-}  // namespace
-
 extern "C" hipError_t fsk_launch_segments_wide(const void* d_chunk, int elem_bytes, uint64_t base, uint64_t m, const uint64_t* d_offsets,
                                                uint64_t nseg, uint64_t* d_out, uint64_t* d_high, int mode, uint32_t grid,
                                                hipStream_t stream)
@@ -266,8 +132,8 @@ extern "C" hipError_t fsk_launch_segments_wide(const void* d_chunk, int elem_byt
     uint64_t lo0 = 0, nunits = 0;
     uint32_t g = 0;
     if (m) {
-        launch_shape(addr, m, W, grid, &lo0, &nunits, &g);
-        if (!wave_totals_fit(nunits, g, fsk::kSegWideUnitBytes / W)) return hipErrorInvalidValue;
+        fsseg::launch_shape(addr, m, fsk::kSegWideUnitBytes / W, grid, &lo0, &nunits, &g);
+        if (!fsseg::wave_totals_fit(nunits, g, fsk::kSegWideUnitBytes / W)) return hipErrorInvalidValue;
     }
     if (mode & 1) {
         const bool together = d_high == d_out + nseg * 32;
@@ -291,10 +157,9 @@ extern "C" hipError_t fsk_launch_segments_wide(const void* d_chunk, int elem_byt
 }
 
 // ------------------------------------------------------------------ C entry points (include/libflagstats_hip.h)
-using fsint::DeviceGuard;
+// The bodies of the three forms are fsseg's (flagstat_segments_shared.h): 33 words per segment, the rows, then the masks.
 using fsint::Engine;
 using fsint::fail_text;
-using fsseg::seg_grid;
 
 namespace {
 
@@ -316,25 +181,11 @@ int segw_args(const void* array, uint64_t n, int elem_bytes, const uint64_t* off
     return 0;
 }
 
-int segw_fits(const void* array, uint64_t n, int elem_bytes, uint32_t grid)
-{
-    if (n == 0) return 0;
-    uint64_t lo0 = 0, nunits = 0;
-    uint32_t g = 0;
-    const uint64_t W = static_cast<uint64_t>(elem_bytes);
-    launch_shape(reinterpret_cast<uintptr_t>(array), n, W, grid, &lo0, &nunits, &g);
-    if (!wave_totals_fit(nunits, g, fsk::kSegWideUnitBytes / W))
-        return fail_text("n is too large for this grid: a wave's uint32 totals could overflow (split the array)");
-    return 0;
-}
-
 // rows, then masks, of a synchronous call into the caller's host words: rows stored or added, masks stored or ORed
 void apply_rows_and_masks(uint64_t* out, uint64_t* high, const fsseg::HostRows& got, uint64_t nseg, int flags)
 {
     fsseg::apply(out, got.p.get(), nseg * 32, flags);
-    if (!high) return;
-    const uint64_t* m = got.p.get() + nseg * 32;
-    for (uint64_t i = 0; i < nseg; ++i) high[i] = (flags & 1) ? m[i] : (high[i] | m[i]);
+    fsseg::apply_masks(high, got.p.get() + nseg * 32, nseg, flags);
 }
 
 }  // namespace
@@ -347,19 +198,16 @@ int FLAGSTATS_hip_device_wide_segments(const void* d_array, uint64_t n, int elem
     FS_ENTRY();
     int rc = segw_args(d_array, n, elem_bytes, d_offsets, nseg, d_out, flags, "NULL d_offsets or d_out with nseg > 0");
     if (rc || nseg == 0) return rc;
+    const uint64_t W = static_cast<uint64_t>(elem_bytes);
     const fsdrv::DeviceWord word{d_high, "d_high", "the masks are ORed with device atomics"};
-    const fsdrv::Input in[] = {{d_offsets, "d_offsets", (nseg + 1) * sizeof(uint64_t)}, {d_array, "d_array", n * static_cast<uint64_t>(elem_bytes)}};
-    const int inputs = n ? 2 : 1;
-    fsdrv::DeviceCall call;
-    if ((rc = call.open(d_out, word, in, inputs, stream))) return rc;
-    const uint32_t grid = seg_grid(*call.e);
-    if ((rc = segw_fits(d_array, n, elem_bytes, grid))) return rc;
-    if ((rc = fsint::check_extent(d_out, nseg * 32 * sizeof(uint64_t), "d_out"))) return rc;
-    if (d_high && (rc = fsint::check_extent(d_high, nseg * sizeof(uint64_t), "d_high"))) return rc;
-    for (int i = 0; i < inputs; ++i)
-        if ((rc = fsint::check_extent(in[i].p, in[i].bytes, in[i].name))) return rc;
-    FS_HIP_TRY(fsk_launch_segments_wide(d_array, elem_bytes, 0, n, d_offsets, nseg, d_out, d_high, flags & 3, grid, call.s));
-    return 0;
+    const fsdrv::Input in[] = {{d_offsets, "d_offsets", (nseg + 1) * sizeof(uint64_t)}, {d_array, "d_array", n * W}};
+    return fsseg::device_call(
+        d_out, &word, 1, in, n ? 2 : 1, nseg, stream,
+        [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWideUnitBytes / W, grid); },
+        [&](uint32_t grid, hipStream_t s) {
+            FS_HIP_TRY(fsk_launch_segments_wide(d_array, elem_bytes, 0, n, d_offsets, nseg, d_out, d_high, flags & 3, grid, s));
+            return 0;
+        });
 }
 
 int FLAGSTATS_hip_device_wide_segments_sync(const void* d_array, uint64_t n, int elem_bytes, const uint64_t* offsets, uint64_t nseg,
@@ -368,34 +216,15 @@ int FLAGSTATS_hip_device_wide_segments_sync(const void* d_array, uint64_t n, int
     FS_ENTRY();
     int rc = segw_args(d_array, n, elem_bytes, offsets, nseg, out, flags, "NULL offsets or out with nseg > 0");
     if (rc || nseg == 0) return rc;
-    Engine* ep = nullptr;
-    if (n) {
-        int dev = -1;
-        if ((rc = fsint::device_of_pointer(d_array, "d_array", &dev))) return rc;
-        ep = fsint::engine_for_device(dev);
-    } else {
-        ep = fsint::default_engine();
-    }
-    if (!ep) return -1;
-    Engine& e = *ep;
-    std::lock_guard<std::mutex> lk(e.mu);
-    if (fsint::engine_alive(e)) return -1;
-    DeviceGuard guard(e.device);
-    if (!guard.ok()) return -1;
-    const uint32_t grid = seg_grid(e);
-    if ((rc = segw_fits(d_array, n, elem_bytes, grid))) return rc;
-    fsseg::SegBuffers buf;     // rows, then the masks
-    fsseg::HostRows got;
-    if ((rc = buf.alloc(nseg, 33)) || (rc = got.alloc(nseg, 33))) return rc;
-    if ((rc = fsseg::check_host_offsets(offsets, nseg, n))) return rc;
-    if (n && (rc = fsint::check_extent(d_array, n * static_cast<uint64_t>(elem_bytes), "d_array"))) return rc;
-    hipStream_t s = e.stream[0];
-    FS_HIP_TRY(hipMemcpyAsync(buf.off, offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    FS_HIP_TRY(fsk_launch_segments_wide(d_array, elem_bytes, 0, n, buf.off, nseg, buf.cnt, buf.cnt + nseg * 32, 1 | (flags & 2), grid, s));
-    FS_HIP_TRY(hipMemcpyAsync(got.p.get(), buf.cnt, got.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    FS_HIP_TRY(hipStreamSynchronize(s));
-    apply_rows_and_masks(out, high, got, nseg, flags);
-    return 0;
+    const uint64_t W = static_cast<uint64_t>(elem_bytes);
+    const fsdrv::Input in[] = {{d_array, "d_array", n * W}};
+    return fsseg::sync_call(
+        in, n ? 1 : 0, n, offsets, nseg, 33, [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWideUnitBytes / W, grid); },
+        [&](fsseg::SegBuffers& buf, uint32_t grid, hipStream_t s) {
+            FS_HIP_TRY(fsk_launch_segments_wide(d_array, elem_bytes, 0, n, buf.off, nseg, buf.cnt, buf.cnt + nseg * 32, 1 | (flags & 2), grid, s));
+            return 0;
+        },
+        [&](const fsseg::HostRows& got) { apply_rows_and_masks(out, high, got, nseg, flags); });
 }
 
 int FLAGSTATS_hip_wide_x64_segments(const void* array, uint64_t n, int elem_bytes, const uint64_t* offsets, uint64_t nseg, uint64_t* out,
@@ -404,50 +233,20 @@ int FLAGSTATS_hip_wide_x64_segments(const void* array, uint64_t n, int elem_byte
     FS_ENTRY();
     int rc = segw_args(array, n, elem_bytes, offsets, nseg, out, flags, "NULL offsets or out with nseg > 0");
     if (rc || nseg == 0) return rc;
-    Engine* ep = fsint::default_engine();
-    if (!ep) return -1;
-    Engine& e = *ep;
-    std::lock_guard<std::mutex> lk(e.mu);
-    if (fsint::engine_alive(e)) return -1;
-    DeviceGuard guard(e.device);
-    if (!guard.ok()) return -1;
-    fsint::lz4_gpu_other_use(e);
-    fsseg::SegBuffers buf;     // rows, then the masks
-    fsseg::HostRows got;
-    if ((rc = buf.alloc(nseg, 33)) || (rc = got.alloc(nseg, 33))) return rc;
-    if ((rc = fsseg::check_host_offsets(offsets, nseg, n))) return rc;
-    if ((rc = fsint::engine_second(e))) return rc;
-    // only the elements some segment covers cross the bus, as they are: [offsets[0], offsets[nseg]) in chunks of "chunk_flags" * 2
-    // bytes (the wide host entry's), alternating between the engine's two streams and staging buffers; every chunk's launch adds
-    // the pieces of the segments it holds to the same device rows and ORs into the same device masks
+    // the elements cross the bus as they are, in chunks of "chunk_flags" * 2 bytes (the wide host entry's); every chunk's launch
+    // adds to the same device rows and ORs into the same device masks
     const uint64_t W = static_cast<uint64_t>(elem_bytes);
-    const uint64_t chunk = fsdrv::chunk_flags() * 2 / W;   // elements per chunk (at least 2)
-    const uint64_t first = offsets[0], last = offsets[nseg];
-    const uint64_t cap = last - first < chunk ? (last - first ? last - first : 1) : chunk;   // elements of the largest chunk
-    const int slots = last - first > chunk ? 2 : 1;
-    for (int i = 0; i < slots; ++i)
-        if ((rc = fsint::stage_reserve(e, i, cap * W / 2))) return rc;
-    hipStream_t s0 = e.stream[0];
-    FS_HIP_TRY(hipMemsetAsync(buf.cnt, 0, nseg * 33 * sizeof(uint64_t), s0));
-    FS_HIP_TRY(hipMemcpyAsync(buf.off, offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s0));
-    if (slots == 2 && (rc = fsint::stream_wait_stream(e, e.stream[1], s0))) return rc;
-    const uint32_t grid = seg_grid(e);
     const int mode = flags & 2;
     const uint8_t* src = static_cast<const uint8_t*>(array);
-    uint64_t k = 0;
-    for (uint64_t pos = first; pos < last; pos += chunk, ++k) {
-        const int sl = static_cast<int>(k % static_cast<uint64_t>(slots));
-        const uint64_t c = last - pos < chunk ? last - pos : chunk;
-        FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], src + pos * W, c * W, hipMemcpyHostToDevice, e.stream[sl]));
-        FS_HIP_TRY(fsk_launch_segments_wide(e.stage[sl], elem_bytes, pos, c, buf.off, nseg, buf.cnt, buf.cnt + nseg * 32, mode, grid,
-                                            e.stream[sl]));
-    }
-    if (slots == 2 && (rc = fsint::stream_wait_stream(e, s0, e.stream[1]))) return rc;
-    FS_HIP_TRY(hipMemcpyAsync(got.p.get(), buf.cnt, got.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s0));
-    FS_HIP_TRY(hipStreamSynchronize(s0));
-    if (slots == 2) FS_HIP_TRY(hipStreamSynchronize(e.stream[1]));
-    apply_rows_and_masks(out, high, got, nseg, flags);
-    return 0;
+    return fsseg::host_call(
+        n, offsets, nseg, 33, fsdrv::chunk_flags() * 2 / W, [&] { return offsets[nseg]; }, [&](uint64_t cap) { return cap * W / 2; },
+        [&](Engine& e, fsseg::SegBuffers& buf, int sl, uint64_t pos, uint64_t c, uint64_t, uint32_t grid) {
+            FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], src + pos * W, c * W, hipMemcpyHostToDevice, e.stream[sl]));
+            FS_HIP_TRY(fsk_launch_segments_wide(e.stage[sl], elem_bytes, pos, c, buf.off, nseg, buf.cnt, buf.cnt + nseg * 32, mode, grid,
+                                                e.stream[sl]));
+            return 0;
+        },
+        [&](const fsseg::HostRows& got) { apply_rows_and_masks(out, high, got, nseg, flags); });
 }
 
 }  // extern "C"

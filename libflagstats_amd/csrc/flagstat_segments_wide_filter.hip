@@ -6,7 +6,10 @@
 // It is flagstat_segments_wide.hip with the filter in front of the count; the last corner of the grid {uint16, wide} x {whole
 // array, per segment} x {no predicate, -f / -F / -q}.
 //
-// Geometry, work split and walk.  flagstat_segments_wide.hip's, unchanged: the 16-byte grid of the aligned-down base, positions
+// Geometry, work split and walk.  flagstat_segments_wide.hip's -- but this kernel keeps its own copy of the walk that the other
+// four take from flagstat_segments_shared.h (seg_walk<UE>): under the shared form the two MAPQ instantiations need 262 and 260
+// VGPRs against 255 and 253 and fall from 2 waves per SIMD to 1 (profiles/r18/).  A change to the walk is made there and here;
+// tests/test_segments_wide_filter_host.py holds the two together rule by rule.  The 16-byte grid of the aligned-down base, positions
 // are elements of W bytes, units of 8 KiB (2048 elements at W = 4, 1024 at W = 8), every wave of the grid a writer over a
 // contiguous run of units, SegWalk / seg_slot_value (flagstat_segments_shared.h), the policy of fsk_segments_policy.
 // tests/segments_wide_oracle.WideWriterSplit mirrors the split of both kernels.
@@ -27,14 +30,12 @@
 //     At W = 8 a count_planes call takes four rows of the unit: the MAPQ dword of its first plane pair is the 16-bit halves of
 //     rows 4 g and 4 g + 1 (low, high), that of the second those of rows 4 g + 2 and 4 g + 3; the valid bits pair up the same way.
 //
-// Emission.  segw_emit plus segf_emit: the lane's 21 counters, its passing count and its two mask accumulators are reduced and
+// Emission (seg_emit<true, true> of flagstat_segments_shared.h): the lane's 21 counters, its passing count and its two mask accumulators are reduced and
 // reset at a segment's end; lanes 0-31 of one instruction write the row (superset slot 9 from the passing count), lane 32
 // selected[s], lane 33 high[s]: plain stores where the row is stored plainly, else relaxed agent-scope atomics (add, add, OR),
 // issued only for non-zero values.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <mutex>
 
 #include "../../include/libflagstats_hip.h"
 #include "flagstat_count_core.h"
@@ -110,54 +111,6 @@ __device__ __forceinline__ void count_piece_wide_filter(uint32_t (&acc)[kInterna
     });
 }
 
-// the wave's counters of the piece of segment s it holds -> out[s][32], its passing count -> selected[s], its mask -> high[s]
-__device__ __forceinline__ void segwf_emit(Lane<kSegWideFilterDepth>& st, uint32_t& blk, uint32_t& cnt, uint32_t& or_even, uint32_t& or_odd,
-                                           uint32_t* red, uint64_t* __restrict__ out, uint64_t* __restrict__ selected,
-                                           uint64_t* __restrict__ high, uint64_t s, bool plain, int mode, uint32_t lane)
-{
-    if (blk) {
-        flush(st, blk);
-        blk = 0;
-    }
-    uint32_t w[kInternal + 1];
-#pragma unroll
-    for (int c = 0; c < kInternal; ++c) {
-        w[c] = wave_sum_lane63(st.acc[c]);
-        st.acc[c] = 0;
-    }
-    w[kInternal] = wave_sum_lane63(cnt);
-    cnt = 0;
-    const uint32_t we = wave_or_lane63(or_even & 0xFFFF0000u);   // the even-dword stream: bits 16-31 of every element
-    const uint32_t wo = wave_or_lane63(or_odd);                   // W = 8: bits 32-63
-    or_even = 0;
-    or_odd = 0;
-    if (lane == 63) {
-#pragma unroll
-        for (int c = 0; c <= kInternal; ++c) red[c] = w[c];
-        red[kInternal + 1] = we;
-        red[kInternal + 2] = wo;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (lane < 32 || (lane == 32 && selected != nullptr)) {
-        const uint64_t passing = red[kInternal];
-        const uint64_t add = lane < 32 ? seg_slot_value(red, lane, mode, passing) : passing;
-        uint64_t* o = lane < 32 ? out + s * 32 + lane : selected + s;
-        if (plain)
-            *o = add;  // store form, the whole segment in this wave: all 32 slots and the count
-        else if (add)
-            (void)__hip_atomic_fetch_add(o, add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else if (lane == 33 && high != nullptr) {
-        const uint64_t mk = (static_cast<uint64_t>(red[kInternal + 2]) << 32) | red[kInternal + 1];
-        if (plain)
-            high[s] = mk;
-        else if (mk)
-            (void)__hip_atomic_fetch_or(high + s, mk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __builtin_amdgcn_wave_barrier();  // red[] is rewritten by the next segment's totals only after every lane has read it
-}
-
 // a0: 16-B aligned-down base; the chunk's elements occupy grid positions [lo0, hi0) (elements of W bytes) and are global elements
 // [base, base + hi0 - lo0).  mq: the chunk's MAPQ column on the same grid (the byte of position q is mq[q]; not read when !MAPQ).
 // require & exclude == 0 (the launcher's business), both below 2^16, min_mapq in 1..255 when MAPQ.  nunits = ceil(hi0 / (8192 /
@@ -201,7 +154,7 @@ __global__ __launch_bounds__(kThreads) void flagstat_segments_wide_filter(const 
     bool open = false;                  // st, cnt and the mask accumulators hold segment s's, not yet emitted
     uint64_t sb = 0, se = 0;
     auto emit = [&](uint64_t seg, uint64_t b_, uint64_t e_) {
-        segwf_emit(st, blk, cnt, or_even, or_odd, red, out, selected, high, seg, (mode & 1) && b_ >= p0 && e_ <= E, mode, lane);
+        seg_emit<true, true>(st, blk, cnt, or_even, or_odd, red, out, selected, high, seg, 0, (mode & 1) && b_ >= p0 && e_ <= E, mode, lane);
     };
 
     uint64_t u = p0 / UE;
@@ -209,7 +162,7 @@ __global__ __launch_bounds__(kThreads) void flagstat_segments_wide_filter(const 
         sw.bounds(s, sb, se);
         const uint64_t w0 = u * UE;
         const uint64_t x = w0 > p0 ? w0 : p0;
-        // (the order of these tests is flagstat_segments.hip's, for its reasons)
+        // (the order of these tests is seg_walk's in flagstat_segments_shared.h, for its reasons)
         if (sb >= E) break;
         if (se <= sb || se <= x) {  // empty (or, with malformed offsets, reversed or behind)
             ++s;
@@ -307,27 +260,6 @@ __global__ __launch_bounds__(kThreads) void flagstat_segments_wide_filter(const 
 }  // namespace fsk
 
 // ------------------------------------------------------------------ launcher
-namespace {
-
-// a wave's totals are uint32: every wave must own fewer than 2^32 elements
-bool wave_totals_fit(uint64_t nunits, uint32_t g, uint64_t unit_elems)
-{
-    const uint64_t waves = static_cast<uint64_t>(g) * (fsk::kThreads / 64);
-    return (nunits + waves - 1) / waves < (1ull << 32) / unit_elems;
-}
-
-// units and workgroups of a launch over m > 0 elements of W bytes at `addr` with at most `grid` workgroups
-void launch_shape(uintptr_t addr, uint64_t m, uint64_t W, uint32_t grid, uint64_t* lo0, uint64_t* nunits, uint32_t* g)
-{
-    const uint64_t ue = fsk::kSegWideUnitBytes / W;
-    *lo0 = (addr & 15u) / W;
-    *nunits = (*lo0 + m + ue - 1) / ue;
-    const uint64_t want = (*nunits + 3) / 4;  // one unit per wave at least
-    *g = want < grid ? static_cast<uint32_t>(want) : grid;
-}
-
-}  // namespace
-
 extern "C" hipError_t fsk_launch_segments_wide_filter(const void* d_chunk, int elem_bytes, const uint8_t* d_mapq_chunk, uint64_t base,
                                                       uint64_t m, const uint64_t* d_offsets, uint64_t nseg, uint32_t require,
                                                       uint32_t exclude, uint32_t min_mapq, uint64_t* d_out, uint64_t* d_selected,
@@ -344,8 +276,8 @@ extern "C" hipError_t fsk_launch_segments_wide_filter(const void* d_chunk, int e
     uint64_t lo0 = 0, nunits = 0;
     uint32_t g = 0;
     if (m) {
-        launch_shape(addr, m, W, grid, &lo0, &nunits, &g);
-        if (!wave_totals_fit(nunits, g, fsk::kSegWideUnitBytes / W)) return hipErrorInvalidValue;
+        fsseg::launch_shape(addr, m, fsk::kSegWideUnitBytes / W, grid, &lo0, &nunits, &g);
+        if (!fsseg::wave_totals_fit(nunits, g, fsk::kSegWideUnitBytes / W)) return hipErrorInvalidValue;
     }
     if (mode & 1) {
         hipError_t e;
@@ -387,10 +319,10 @@ extern "C" hipError_t fsk_launch_segments_wide_filter(const void* d_chunk, int e
 }
 
 // ------------------------------------------------------------------ C entry points (include/libflagstats_hip.h)
-using fsint::DeviceGuard;
+// The bodies of the three forms are fsseg's (flagstat_segments_shared.h): 34 words per segment, the rows, then the selected
+// counts, then the masks.
 using fsint::Engine;
 using fsint::fail_text;
-using fsseg::seg_grid;
 
 namespace {
 
@@ -418,27 +350,12 @@ int segwf_args(const void* array, uint64_t n, int elem_bytes, const uint64_t* of
     return 0;
 }
 
-int segwf_fits(const void* array, uint64_t n, int elem_bytes, uint32_t grid)
-{
-    if (n == 0) return 0;
-    uint64_t lo0 = 0, nunits = 0;
-    uint32_t g = 0;
-    const uint64_t W = static_cast<uint64_t>(elem_bytes);
-    launch_shape(reinterpret_cast<uintptr_t>(array), n, W, grid, &lo0, &nunits, &g);
-    if (!wave_totals_fit(nunits, g, fsk::kSegWideUnitBytes / W))
-        return fail_text("n is too large for this grid: a wave's uint32 totals could overflow (split the array)");
-    return 0;
-}
-
 // rows, selected counts, then masks, of a synchronous call into the caller's host words: rows and counts stored or added, masks
 // stored or ORed
 void apply_all(uint64_t* out, uint64_t* selected, uint64_t* high, const fsseg::HostRows& got, uint64_t nseg, int flags)
 {
-    fsseg::apply(out, got.p.get(), nseg * 32, flags);
-    if (selected) fsseg::apply(selected, got.p.get() + nseg * 32, nseg, flags);
-    if (!high) return;
-    const uint64_t* mk = got.p.get() + nseg * 33;
-    for (uint64_t i = 0; i < nseg; ++i) high[i] = (flags & 1) ? mk[i] : (high[i] | mk[i]);
+    fsseg::apply_both(out, selected, got, nseg, flags);
+    fsseg::apply_masks(high, got.p.get() + nseg * 33, nseg, flags);
 }
 
 }  // namespace
@@ -453,24 +370,18 @@ int FLAGSTATS_hip_device_wide_segments_filter(const void* d_array, uint64_t n, i
     int rc = segwf_args(d_array, n, elem_bytes, d_offsets, nseg, require, exclude, d_mapq, min_mapq, d_out, flags,
                         "NULL d_offsets or d_out with nseg > 0");
     if (rc || nseg == 0) return rc;
+    const uint64_t W = static_cast<uint64_t>(elem_bytes);
     const fsdrv::DeviceWord words[] = {{d_selected, "d_selected", "the counts are added with device atomics"},
                                        {d_high, "d_high", "the masks are ORed with device atomics"}};
-    const fsdrv::Input in[] = {{d_offsets, "d_offsets", (nseg + 1) * sizeof(uint64_t)},
-                               {d_array, "d_array", n * static_cast<uint64_t>(elem_bytes)},
-                               {d_mapq, "d_mapq", n}};
-    const int inputs = n ? (min_mapq ? 3 : 2) : 1;
-    fsdrv::DeviceCall call;
-    if ((rc = call.open(d_out, words, 2, in, inputs, stream))) return rc;
-    const uint32_t grid = seg_grid(*call.e);
-    if ((rc = segwf_fits(d_array, n, elem_bytes, grid))) return rc;
-    if ((rc = fsint::check_extent(d_out, nseg * 32 * sizeof(uint64_t), "d_out"))) return rc;
-    if (d_selected && (rc = fsint::check_extent(d_selected, nseg * sizeof(uint64_t), "d_selected"))) return rc;
-    if (d_high && (rc = fsint::check_extent(d_high, nseg * sizeof(uint64_t), "d_high"))) return rc;
-    for (int i = 0; i < inputs; ++i)
-        if ((rc = fsint::check_extent(in[i].p, in[i].bytes, in[i].name))) return rc;
-    FS_HIP_TRY(fsk_launch_segments_wide_filter(d_array, elem_bytes, d_mapq, 0, n, d_offsets, nseg, require, exclude, min_mapq, d_out,
-                                               d_selected, d_high, flags & 3, grid, call.s));
-    return 0;
+    const fsdrv::Input in[] = {{d_offsets, "d_offsets", (nseg + 1) * sizeof(uint64_t)}, {d_array, "d_array", n * W}, {d_mapq, "d_mapq", n}};
+    return fsseg::device_call(
+        d_out, words, 2, in, n ? (min_mapq ? 3 : 2) : 1, nseg, stream,
+        [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWideUnitBytes / W, grid); },
+        [&](uint32_t grid, hipStream_t s) {
+            FS_HIP_TRY(fsk_launch_segments_wide_filter(d_array, elem_bytes, d_mapq, 0, n, d_offsets, nseg, require, exclude, min_mapq, d_out,
+                                                       d_selected, d_high, flags & 3, grid, s));
+            return 0;
+        });
 }
 
 int FLAGSTATS_hip_device_wide_segments_filter_sync(const void* d_array, uint64_t n, int elem_bytes, const uint64_t* offsets, uint64_t nseg,
@@ -481,40 +392,17 @@ int FLAGSTATS_hip_device_wide_segments_filter_sync(const void* d_array, uint64_t
     int rc = segwf_args(d_array, n, elem_bytes, offsets, nseg, require, exclude, d_mapq, min_mapq, out, flags,
                         "NULL offsets or out with nseg > 0");
     if (rc || nseg == 0) return rc;
-    Engine* ep = nullptr;
-    if (n) {
-        int dev = -1, dev_q = -1;
-        if ((rc = fsint::device_of_pointer(d_array, "d_array", &dev))) return rc;
-        if (min_mapq) {
-            if ((rc = fsint::device_of_pointer(d_mapq, "d_mapq", &dev_q))) return rc;
-            if (dev_q != dev) return fsdrv::fail_devices("d_mapq", "d_array");
-        }
-        ep = fsint::engine_for_device(dev);
-    } else {
-        ep = fsint::default_engine();
-    }
-    if (!ep) return -1;
-    Engine& e = *ep;
-    std::lock_guard<std::mutex> lk(e.mu);
-    if (fsint::engine_alive(e)) return -1;
-    DeviceGuard guard(e.device);
-    if (!guard.ok()) return -1;
-    const uint32_t grid = seg_grid(e);
-    if ((rc = segwf_fits(d_array, n, elem_bytes, grid))) return rc;
-    fsseg::SegBuffers buf;     // rows, then the selected counts, then the masks
-    fsseg::HostRows got;
-    if ((rc = buf.alloc(nseg, 34)) || (rc = got.alloc(nseg, 34))) return rc;
-    if ((rc = fsseg::check_host_offsets(offsets, nseg, n))) return rc;
-    if (n && (rc = fsint::check_extent(d_array, n * static_cast<uint64_t>(elem_bytes), "d_array"))) return rc;
-    if (n && min_mapq && (rc = fsint::check_extent(d_mapq, n, "d_mapq"))) return rc;
-    hipStream_t s = e.stream[0];
-    FS_HIP_TRY(hipMemcpyAsync(buf.off, offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    FS_HIP_TRY(fsk_launch_segments_wide_filter(d_array, elem_bytes, d_mapq, 0, n, buf.off, nseg, require, exclude, min_mapq, buf.cnt,
-                                               buf.cnt + nseg * 32, buf.cnt + nseg * 33, 1 | (flags & 2), grid, s));
-    FS_HIP_TRY(hipMemcpyAsync(got.p.get(), buf.cnt, got.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    FS_HIP_TRY(hipStreamSynchronize(s));
-    apply_all(out, selected, high, got, nseg, flags);
-    return 0;
+    const uint64_t W = static_cast<uint64_t>(elem_bytes);
+    const fsdrv::Input in[] = {{d_array, "d_array", n * W}, {d_mapq, "d_mapq", n}};
+    return fsseg::sync_call(
+        in, n ? (min_mapq ? 2 : 1) : 0, n, offsets, nseg, 34,
+        [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWideUnitBytes / W, grid); },
+        [&](fsseg::SegBuffers& buf, uint32_t grid, hipStream_t s) {
+            FS_HIP_TRY(fsk_launch_segments_wide_filter(d_array, elem_bytes, d_mapq, 0, n, buf.off, nseg, require, exclude, min_mapq, buf.cnt,
+                                                       buf.cnt + nseg * 32, buf.cnt + nseg * 33, 1 | (flags & 2), grid, s));
+            return 0;
+        },
+        [&](const fsseg::HostRows& got) { apply_all(out, selected, high, got, nseg, flags); });
 }
 
 int FLAGSTATS_hip_wide_x64_segments_filter(const void* array, uint64_t n, int elem_bytes, const uint64_t* offsets, uint64_t nseg,
@@ -525,55 +413,25 @@ int FLAGSTATS_hip_wide_x64_segments_filter(const void* array, uint64_t n, int el
     int rc = segwf_args(array, n, elem_bytes, offsets, nseg, require, exclude, mapq, min_mapq, out, flags,
                         "NULL offsets or out with nseg > 0");
     if (rc || nseg == 0) return rc;
-    Engine* ep = fsint::default_engine();
-    if (!ep) return -1;
-    Engine& e = *ep;
-    std::lock_guard<std::mutex> lk(e.mu);
-    if (fsint::engine_alive(e)) return -1;
-    DeviceGuard guard(e.device);
-    if (!guard.ok()) return -1;
-    fsint::lz4_gpu_other_use(e);
-    fsseg::SegBuffers buf;     // rows, then the selected counts, then the masks
-    fsseg::HostRows got;
-    if ((rc = buf.alloc(nseg, 34)) || (rc = got.alloc(nseg, 34))) return rc;
-    if ((rc = fsseg::check_host_offsets(offsets, nseg, n))) return rc;
-    if ((rc = fsint::engine_second(e))) return rc;
-    // only what some segment covers crosses the bus, as it is: [offsets[0], offsets[nseg]) of the array and of the MAPQ column, in
-    // chunks of "chunk_flags" * 2 bytes of elements (the wide host entries'), alternating between the engine's two streams and
-    // staging buffers; a chunk's slice of the column rides in the same staging buffer, behind its elements (as
-    // FLAGSTATS_hip_wide_x64_filter stages it); every chunk's launch adds its pieces to the same device rows and counts and ORs
-    // into the same device masks.  An overlapping pair selects nothing and reads no element: nothing is moved.
+    // the elements cross the bus as they are, in chunks of "chunk_flags" * 2 bytes (the wide host entries'); a chunk's slice of the
+    // MAPQ column rides in the same staging buffer, behind its elements (as FLAGSTATS_hip_wide_x64_filter stages it); every
+    // chunk's launch adds to the same device rows and counts and ORs into the same device masks.  An overlapping pair selects
+    // nothing and reads no element: nothing is moved.
     const uint64_t W = static_cast<uint64_t>(elem_bytes);
-    const uint64_t chunk = fsdrv::chunk_flags() * 2 / W;   // elements per chunk (at least 2)
-    const uint64_t first = offsets[0], last = (require & exclude) ? first : offsets[nseg];
-    const uint64_t cap = last - first < chunk ? (last - first ? last - first : 1) : chunk;   // elements of the largest chunk
-    const uint64_t mapq_cap = min_mapq ? cap : 0;                                            // bytes of its MAPQ slice
-    const int slots = last - first > chunk ? 2 : 1;
-    for (int i = 0; i < slots; ++i)
-        if ((rc = fsint::stage_reserve(e, i, cap * W / 2 + (mapq_cap + 1) / 2))) return rc;
-    hipStream_t s0 = e.stream[0];
-    FS_HIP_TRY(hipMemsetAsync(buf.cnt, 0, nseg * 34 * sizeof(uint64_t), s0));
-    FS_HIP_TRY(hipMemcpyAsync(buf.off, offsets, (nseg + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s0));
-    if (slots == 2 && (rc = fsint::stream_wait_stream(e, e.stream[1], s0))) return rc;
-    const uint32_t grid = seg_grid(e);
     const int mode = flags & 2;
     const uint8_t* src = static_cast<const uint8_t*>(array);
-    uint64_t k = 0;
-    for (uint64_t pos = first; pos < last; pos += chunk, ++k) {
-        const int sl = static_cast<int>(k % static_cast<uint64_t>(slots));
-        const uint64_t c = last - pos < chunk ? last - pos : chunk;
-        uint8_t* d_mapq = reinterpret_cast<uint8_t*>(e.stage[sl]) + cap * W;
-        FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], src + pos * W, c * W, hipMemcpyHostToDevice, e.stream[sl]));
-        if (min_mapq) FS_HIP_TRY(hipMemcpyAsync(d_mapq, mapq + pos, c, hipMemcpyHostToDevice, e.stream[sl]));
-        FS_HIP_TRY(fsk_launch_segments_wide_filter(e.stage[sl], elem_bytes, d_mapq, pos, c, buf.off, nseg, require, exclude, min_mapq,
-                                                   buf.cnt, buf.cnt + nseg * 32, buf.cnt + nseg * 33, mode, grid, e.stream[sl]));
-    }
-    if (slots == 2 && (rc = fsint::stream_wait_stream(e, s0, e.stream[1]))) return rc;
-    FS_HIP_TRY(hipMemcpyAsync(got.p.get(), buf.cnt, got.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s0));
-    FS_HIP_TRY(hipStreamSynchronize(s0));
-    if (slots == 2) FS_HIP_TRY(hipStreamSynchronize(e.stream[1]));
-    apply_all(out, selected, high, got, nseg, flags);
-    return 0;
+    return fsseg::host_call(
+        n, offsets, nseg, 34, fsdrv::chunk_flags() * 2 / W, [&] { return (require & exclude) ? offsets[0] : offsets[nseg]; },
+        [&](uint64_t cap) { return cap * W / 2 + ((min_mapq ? cap : 0) + 1) / 2; },
+        [&](Engine& e, fsseg::SegBuffers& buf, int sl, uint64_t pos, uint64_t c, uint64_t cap, uint32_t grid) {
+            uint8_t* d_mapq = reinterpret_cast<uint8_t*>(e.stage[sl]) + cap * W;
+            FS_HIP_TRY(hipMemcpyAsync(e.stage[sl], src + pos * W, c * W, hipMemcpyHostToDevice, e.stream[sl]));
+            if (min_mapq) FS_HIP_TRY(hipMemcpyAsync(d_mapq, mapq + pos, c, hipMemcpyHostToDevice, e.stream[sl]));
+            FS_HIP_TRY(fsk_launch_segments_wide_filter(e.stage[sl], elem_bytes, d_mapq, pos, c, buf.off, nseg, require, exclude, min_mapq,
+                                                       buf.cnt, buf.cnt + nseg * 32, buf.cnt + nseg * 33, mode, grid, e.stream[sl]));
+            return 0;
+        },
+        [&](const fsseg::HostRows& got) { apply_all(out, selected, high, got, nseg, flags); });
 }
 
 }  // extern "C"

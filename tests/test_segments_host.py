@@ -171,17 +171,24 @@ def test_writer_mirror_matches_the_sources():
     assert int(re.search(r"constexpr int kThreads = (\d+);", k1).group(1)) == 64 * so.SEG_WAVES_PER_BLOCK
     assert (1 << int(re.search(r"constexpr int kSegDepth = (\d+);", src).group(1))) - 1 == so.SEG_EPOCH
     assert "static std::atomic<uint32_t> g_seg_min_units{%d};" % so.SEG_MIN_UNITS in src
-    for rule in ("const uint64_t lo0 = (addr - a0) / 2, hi0 = lo0 + m;",
-                 "const uint64_t nunits = (hi0 + fsk::kSegWaveFlags - 1) / fsk::kSegWaveFlags;",
-                 "const uint64_t want = (nunits + 3) / 4;",
-                 "const uint32_t g = want < grid ? static_cast<uint32_t>(want) : grid;",
+    # the launcher's shape and the kernel's walk are the segmented kernels' shared ones (flagstat_segments_shared.h), which this
+    # unit instantiates for its unit of kSegWaveFlags elements of 8192 / kSegWaveFlags = 2 bytes
+    shared = re.sub(r"\s+", " ", _source("libflagstats_amd", "csrc", "flagstat_segments_shared.h"))
+    assert "fsseg::launch_shape(addr, m, fsk::kSegWaveFlags, grid, &lo0, &nunits, &g);" in src
+    assert "reinterpret_cast<const uint4*>(a0), lo0, lo0 + m, base," in src and "seg_walk<kSegWaveFlags>( lo0, hi0, base," in src
+    assert "constexpr int kSegUnitVecs = kSegWaveFlags / 8;" in shared
+    for rule in ("const uint64_t W = fsk::kSegUnitVecs * 16 / ue;",
+                 "*lo0 = (addr & 15u) / W;",
+                 "*nunits = (*lo0 + m + ue - 1) / ue;",
+                 "const uint64_t want = (*nunits + 3) / 4;",
+                 "*g = want < grid ? static_cast<uint32_t>(want) : grid;",
                  "const uint64_t waves = static_cast<uint64_t>(gridDim.x) * (kThreads / 64);",
                  "const uint64_t u_begin = gw * nunits / waves, u_end = (gw + 1) * nunits / waves;",
-                 "const uint64_t p0 = u_begin * kSegWaveFlags > lo0 ? u_begin * kSegWaveFlags : lo0;",
-                 "const uint64_t E = u_end * kSegWaveFlags < hi0 ? u_end * kSegWaveFlags : hi0;",
+                 "const uint64_t p0 = u_begin * UE > lo0 ? u_begin * UE : lo0;",
+                 "const uint64_t E = u_end * UE < hi0 ? u_end * UE : hi0;",
                  "if (k >= min_units && k > 0) {",
                  "(mode & 1) && b_ >= p0 && e_ <= E"):
-        assert rule in src, rule
+        assert shared.count(rule) == 1, rule
     # the epoch test lives once in the shared end_step, which the chain step calls at the segmented kernel's depth
     assert core.count("if (blk == (1u << DEPTH) - 1u) {") == 1 and "end_step<kSegDepth>(s, blk);" in src
 

@@ -390,18 +390,26 @@ def test_writer_mirror_matches_the_new_source():
     hdr = open(os.path.join(CSRC, "flagstat_segments_wide.h")).read()
     assert int(re.search(r"constexpr int kSegWideUnitBytes = (\d+);", hdr).group(1)) == swfo.UNIT_BYTES
     assert (1 << int(re.search(r"constexpr int kSegWideFilterDepth = (\d+);", src).group(1))) - 1 == swfo.SEG_EPOCH
-    for rule in ("constexpr uint64_t UE = kSegWideUnitBytes / W;",
+    # the parent's walk is the segmented kernels' shared one (seg_walk<UE> of flagstat_segments_shared.h); this kernel keeps a
+    # walk of its own (HISTORY.md), which must state the same rules; the launcher's shape is the shared one for both
+    shared = re.sub(r"\s+", " ", open(os.path.join(CSRC, "flagstat_segments_shared.h")).read())
+    assert "seg_walk<UE>( lo0, hi0, base," in parent and "seg_walk<UE>(" not in src
+    for rule in ("const uint64_t W = fsk::kSegUnitVecs * 16 / ue;",
                  "*lo0 = (addr & 15u) / W;",
                  "*nunits = (*lo0 + m + ue - 1) / ue;",
                  "const uint64_t want = (*nunits + 3) / 4;",
-                 "*g = want < grid ? static_cast<uint32_t>(want) : grid;",
-                 "const uint64_t u_begin = gw * nunits / waves, u_end = (gw + 1) * nunits / waves;",
+                 "*g = want < grid ? static_cast<uint32_t>(want) : grid;"):
+        assert shared.count(rule) == 1, rule
+    for rule in ("const uint64_t u_begin = gw * nunits / waves, u_end = (gw + 1) * nunits / waves;",
                  "const uint64_t p0 = u_begin * UE > lo0 ? u_begin * UE : lo0;",
                  "const uint64_t E = u_end * UE < hi0 ? u_end * UE : hi0;",
                  "if (sb >= E) break; if (se <= sb || se <= x) {",
                  "if (sb <= w0 && w0 >= lo0) { const uint64_t k = (seg_e - w0) / UE;",
                  "if (k >= min_units && k > 0) {",
-                 "(mode & 1) && b_ >= p0 && e_ <= E",
+                 "(mode & 1) && b_ >= p0 && e_ <= E"):
+        assert rule in src and shared.count(rule) == 1, rule
+    for rule in ("constexpr uint64_t UE = kSegWideUnitBytes / W;",
+                 "fsseg::launch_shape(addr, m, fsk::kSegWideUnitBytes / W, grid, &lo0, &nunits, &g);",
                  "fsk_segments_policy(&min_units, &blocks_per_cu);"):
         assert rule in src and rule in parent, rule
     assert "end_step<kSegWideFilterDepth>(s, blk);" in src

@@ -241,7 +241,16 @@ def test_writer_mirror_matches_the_sources_and_partitions_the_array():
     hdr = open(os.path.join(ROOT, "libflagstats_amd", "csrc", "flagstat_segments_wide.h")).read()
     assert int(re.search(r"constexpr int kSegWideUnitBytes = (\d+);", hdr).group(1)) == swo.UNIT_BYTES
     assert (1 << int(re.search(r"constexpr int kSegWideDepth = (\d+);", src).group(1))) - 1 == swo.SEG_EPOCH
+    # the launcher's shape and the kernel's walk are the segmented kernels' shared ones (flagstat_segments_shared.h), which this
+    # unit instantiates for its unit of UE elements of 8192 / UE = W bytes
+    shared = re.sub(r"\s+", " ", open(os.path.join(ROOT, "libflagstats_amd", "csrc", "flagstat_segments_shared.h")).read())
     for rule in ("constexpr uint64_t UE = kSegWideUnitBytes / W;",
+                 "fsseg::launch_shape(addr, m, fsk::kSegWideUnitBytes / W, grid, &lo0, &nunits, &g);",
+                 "seg_walk<UE>( lo0, hi0, base,",
+                 "end_step<kSegWideDepth>(s, blk);"):
+        assert rule in src, rule
+    assert "constexpr int kSegUnitVecs = kSegWaveFlags / 8;" in shared and swo.UNIT_BYTES == 4096 // 8 * 16
+    for rule in ("const uint64_t W = fsk::kSegUnitVecs * 16 / ue;",
                  "*lo0 = (addr & 15u) / W;",
                  "*nunits = (*lo0 + m + ue - 1) / ue;",
                  "const uint64_t want = (*nunits + 3) / 4;",
@@ -250,9 +259,8 @@ def test_writer_mirror_matches_the_sources_and_partitions_the_array():
                  "const uint64_t p0 = u_begin * UE > lo0 ? u_begin * UE : lo0;",
                  "const uint64_t E = u_end * UE < hi0 ? u_end * UE : hi0;",
                  "if (k >= min_units && k > 0) {",
-                 "(mode & 1) && b_ >= p0 && e_ <= E",
-                 "end_step<kSegWideDepth>(s, blk);"):
-        assert rule in src, rule
+                 "(mode & 1) && b_ >= p0 && e_ <= E"):
+        assert shared.count(rule) == 1, rule
     rng = np.random.RandomState(31)
     for W in (4, 8):
         U = swo.UNIT_BYTES // W
