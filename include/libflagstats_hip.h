@@ -325,6 +325,47 @@ int FLAGSTATS_hip_wide_x64_filter(const void* array, uint64_t n, int elem_bytes,
                                   const uint8_t* mapq, uint32_t min_mapq, uint64_t* out, uint64_t* selected, uint64_t* high,
                                   int flags);
 
+/* ================= selected elements of wide input: a bitmap or byte mask on a FLAG column of 4-byte or 8-byte integers =========
+ * An Arrow FLAG column is both at once: int32 values and an LSB-first validity bitmap at some bit offset.  One pass over the
+ * array as it is and its selection: no uint16 copy in front (which would turn a negative element or one >= 65,536 into a
+ * plausible FLAG), no compaction, no unpacked bitmap.  With f(i) = the low 16 bits of element i (little-endian elements of
+ * `elem_bytes` = 4 or 8 bytes, aligned to elem_bytes) and sel(i) exactly as in FLAGSTATS_hip_device_u16_where (sel_bits == 1:
+ * bit sel_offset + i of an LSB-first bitmap, any bit offset; sel_bits == 8: byte sel_offset + i, any non-zero byte selects):
+ *   out      : FLAGSTAT_scalar's 32 counters over {f(i) : sel(i), 0 <= i < n}
+ *   selected : the number of i with sel(i)
+ *   high     : OR of (element & ~0xFFFF), taken as unsigned, over the SELECTED elements ONLY.  This differs on purpose from the
+ *              filtered wide entries above, whose `high` covers every element read, passing or not: a selection is typically a
+ *              validity bitmap and the value of a null slot is unspecified, so what lies in a slot that is not selected must not
+ *              make high != 0.  high == 0 says that every selected element is a valid 16-bit FLAG, and nothing about the others.
+ * Only bytes of `sel` that hold the bit or byte of an element of [0, n) and only dwords of elements of [0, n) are ever read.
+ * `flags`: bit 0 = store (out = counters, all 32 slots written; selected = count; high = mask) instead of out += counters,
+ * selected += count, high |= mask; bit 1 = superset (slots 0 / 16 = primary paired reads among the selected, slot 9 = selected
+ * minus slot 25).  `selected` / `d_selected` and `high` / `d_high` may each be NULL: that value is not reported.
+ * n == 0 succeeds and touches nothing (the store form writes zeros to all three).
+ * Refused (non-zero, message in FLAGSTATS_hip_last_error, outputs untouched, nothing launched): elem_bytes other than 4 or 8
+ * (2: use the u16 where entries), sel_bits other than 1 or 8, an array pointer not aligned to elem_bytes, an n with n * elem_bytes
+ * not a size or too large for a wave's uint32 totals, a sel_offset + n that is no index, a NULL array or selection with n > 0,
+ * flag bits other than 0 and 1, NULL counters; for the device form also a d_out, d_selected or d_high that is not plain device
+ * memory, host memory for d_array or d_sel, pointers on different devices, a stream of another device and an allocation shorter
+ * than the call needs (d_array: n * elem_bytes bytes, d_sel: from d_sel up to the last byte that holds an element's bit or
+ * byte, d_out: 256, d_selected: 8, d_high: 8). */
+/* DEVICE array and selection, DEVICE d_out[32], d_selected[1] and d_high[1] (uint64); asynchronous on `stream`: ONE kernel (the
+ * store form puts one zeroing per pointer in front of it; one in all when d_selected == d_out + 32 and d_high == d_out + 33), no
+ * workspace, so a captured launch holds no pointer of the library's (capture and replay: tests/test_gpu_wide_where_graphs.py;
+ * make one plain call before capturing).  Adds and ORs are atomic: launches on several streams may share the three in the +=
+ * form. */
+int FLAGSTATS_hip_device_wide_where(const void* d_array, uint64_t n, int elem_bytes, const void* d_sel, uint64_t sel_offset,
+                                    int sel_bits, uint64_t* d_out, uint64_t* d_selected, uint64_t* d_high, int flags, void* stream);
+/* DEVICE array and selection, HOST out[32], selected[1] and high[1]; synchronous */
+int FLAGSTATS_hip_device_wide_where_sync(const void* d_array, uint64_t n, int elem_bytes, const void* d_sel, uint64_t sel_offset,
+                                         int sel_bits, uint64_t* out, uint64_t* selected, uint64_t* high, int flags);
+/* HOST array and selection, HOST out[32], selected[1] and high[1]; synchronous.  The array crosses the bus as it is in the
+ * engine's chunks (knob "chunk_flags": chunk_flags * 2 bytes of elements each), each chunk's slice of the selection behind its
+ * elements (a bitmap slice from the byte that holds the chunk's first bit); counters, count and mask are summed / ORed on the
+ * device. */
+int FLAGSTATS_hip_wide_x64_where(const void* array, uint64_t n, int elem_bytes, const void* sel, uint64_t sel_offset, int sel_bits,
+                                 uint64_t* out, uint64_t* selected, uint64_t* high, int flags);
+
 /* ================= wide input per segment: a row and a high mask for every segment of an int32 / int64 column =================
  * The union of the segmented and the wide entries: segment i (i < nseg) is [offsets[i], offsets[i+1]) of an array of 4-byte or
  * 8-byte little-endian elements (aligned to elem_bytes), read as it is.  With f(j) = the low 16 bits of element j,

@@ -21,6 +21,8 @@ Only what the path needs:
                      segment in one launch (the selection is indexed by array element)
 * ``wide_filter``    the filter on int32 / int64 (and 16-bit) arrays and tensors in place: counters, the number of
                      reads that pass and the mask of bits seen above bit 15, in one pass
+* ``wide_where``     the mask or bitmap on int32 / int64 (and 16-bit) arrays and tensors in place: counters, the number
+                     selected and the mask of bits seen above bit 15 of the selected elements, in one pass
 * ``segments_wide``  rows of counters and one high-bit mask per CSR segment of an int32 / int64 (or 16-bit) array or
                      tensor, in one launch
 * ``segments_wide_filter`` the filter per segment of an int32 / int64 (or 16-bit) array or tensor in place: rows of counters,
@@ -71,6 +73,12 @@ from .wide_filter import (  # noqa: F401
     counters_ints_filter,
     flagstats_ints_filter,
 )
+from .wide_where import (  # noqa: F401
+    count_device_ptr_ints_where,
+    count_torch_ints_where,
+    counters_ints_where,
+    flagstats_ints_where,
+)
 
 __all__ = ["flagstats", "flagstats_x64", "SAM_FLAG_NAMES", "flagstats_segments", "offsets_from_lengths",
            "count_segments_device_ptr", "count_segments_torch", "segment_dicts", "counters_ints", "flagstats_ints",
@@ -81,4 +89,5 @@ __all__ = ["flagstats", "flagstats_x64", "SAM_FLAG_NAMES", "flagstats_segments",
            "counters_segments_ints", "flagstats_segments_ints", "count_segments_device_ptr_ints", "count_segments_torch_ints",
            "counters_segments_ints_filter", "flagstats_segments_ints_filter", "count_segments_device_ptr_ints_filter",
            "count_segments_torch_ints_filter", "counters_segments_where", "flagstats_segments_where",
-           "count_segments_device_ptr_where", "count_segments_torch_where"]
+           "count_segments_device_ptr_where", "count_segments_torch_where", "counters_ints_where", "flagstats_ints_where",
+           "count_device_ptr_ints_where", "count_torch_ints_where"]

@@ -44,14 +44,6 @@ namespace fsk {
 
 constexpr int kWhereDepth = 8;        // chain depth as K1: epochs of 255 steps
 
-// 4 selection bytes to 4 byte masks (any non-zero byte selects); s = 0x01 per selected flag
-__device__ __forceinline__ uint32_t bytes_mask(uint32_t x, uint32_t& s)
-{
-    const uint32_t t = (x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;   // bit 7 of a byte: one of its bits 0-6 is set (no carry leaves a byte)
-    s = ((t | x) & 0x80808080u) >> 7;
-    return perm(0u, 0x0000FF00u, s);
-}
-
 // the byte masks of a vector's flags 0-3 and 4-7 in the byte form; the number selected is added to cnt
 __device__ __forceinline__ void bytes_masks(const uint2& w, uint32_t& M0, uint32_t& M1, uint32_t& cnt)
 {

@@ -67,6 +67,14 @@ __device__ __forceinline__ typename SelWord<SEL_BITS>::type load_sel_guarded(con
     }
 }
 
+// 4 selection bytes to 4 byte masks (any non-zero byte selects); s = 0x01 per selected flag (also flagstat_wide_where.hip's test)
+__device__ __forceinline__ uint32_t bytes_mask(uint32_t x, uint32_t& s)
+{
+    const uint32_t t = (x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;   // bit 7 of a byte: one of its bits 0-6 is set (no carry leaves a byte)
+    s = ((t | x) & 0x80808080u) >> 7;
+    return perm(0u, 0x0000FF00u, s);
+}
+
 // 4 selection bits (bit k = flag k) to 4 byte masks
 __device__ __forceinline__ uint32_t nibble_mask(uint32_t nib)
 {

@@ -59,9 +59,11 @@ __device__ __forceinline__ uint32_t wide_tree(uint32_t (&x)[N], uint32_t& p1, ui
 // `reissue_vec(u)` is the caller's re-issue of vector u's registers right after they have been read out, between the two
 // sched_barriers of a rolling schedule (K1's schedule 71 through reissue(), at the caller's stride between a lane's consecutive
 // loads: kWaveStride in flagstat_wide.hip, kSegRowVecs in flagstat_segments_wide.hip), or nothing when the vectors are all in v[].
-template <int W, int DEPTH, typename Reissue>
+// `select_vec(u)` runs right in front of the read-out and may change v[u] in its registers: flagstat_wide_where.hip zeroes the
+// elements that its selection leaves out there, so that neither the counters nor the mask accumulators see them.
+template <int W, int DEPTH, typename Reissue, typename Select>
 __device__ __forceinline__ void wide_step_with(Lane<DEPTH>& s, uint4 (&v)[kUnroll], uint32_t blk, uint32_t& or_even, uint32_t& or_odd,
-                                               Reissue&& reissue_vec)
+                                               Reissue&& reissue_vec, Select&& select_vec)
 {
     constexpr int NIN = 32 / W;
     uint32_t T[NIN], F[NIN], S[NIN];
@@ -70,6 +72,7 @@ __device__ __forceinline__ void wide_step_with(Lane<DEPTH>& s, uint4 (&v)[kUnrol
     for (int u = 0; u < kUnroll; ++u) {
         uint32_t p0, p1 = 0;
         __builtin_amdgcn_sched_barrier(0);
+        select_vec(u);
         narrow_out<W>(v[u], p0, p1, or_even, or_odd);
         reissue_vec(u);
         __builtin_amdgcn_sched_barrier(0);
@@ -89,6 +92,14 @@ __device__ __forceinline__ void wide_step_with(Lane<DEPTH>& s, uint4 (&v)[kUnrol
     const uint32_t cf = wide_tree(F, s.f1, s.f2, s.f4, s.f8);
     const uint32_t cs = wide_tree(S, s.s1, s.s2, s.s4, s.s8);
     chain_push<0, DEPTH>(s, blk, ct, cf, cs);
+}
+
+// the step over every element of its vectors
+template <int W, int DEPTH, typename Reissue>
+__device__ __forceinline__ void wide_step_with(Lane<DEPTH>& s, uint4 (&v)[kUnroll], uint32_t blk, uint32_t& or_even, uint32_t& or_odd,
+                                               Reissue&& reissue_vec)
+{
+    wide_step_with<W>(s, v, blk, or_even, or_odd, reissue_vec, [](int) __attribute__((always_inline)) {});
 }
 
 // Vector j of the 16-byte grid holds element positions [j * 16 / W, (j + 1) * 16 / W); positions in [lo, hi) are the caller's

@@ -31,13 +31,8 @@ def _packed_bytes(n: int, bit_offset: int) -> int:
     return (bit_offset + n + 7) // 8
 
 
-def _check_numpy(values, where, packed, bit_offset):
-    if not isinstance(values, np.ndarray):
-        raise ValueError("values must be a numpy.ndarray, not %s" % type(values).__name__)
-    if values.dtype != np.uint16:
-        raise ValueError("values must have dtype uint16, not %s" % values.dtype)
-    if values.ndim != 1:
-        raise ValueError("values must be 1-D, not %d-D" % values.ndim)
+def _check_selection_numpy(where, n: int, packed, bit_offset):
+    """the selection of ``n`` host values (also wide_where.py's): the contiguous array and the bit offset"""
     if not isinstance(where, np.ndarray):
         raise ValueError("where must be a numpy.ndarray, not %s" % type(where).__name__)
     if where.ndim != 1:
@@ -46,15 +41,49 @@ def _check_numpy(values, where, packed, bit_offset):
     if packed:
         if where.dtype != np.uint8:
             raise ValueError("where must have dtype uint8 with packed=True (an LSB-first bitmap), not %s" % where.dtype)
-        need = _packed_bytes(values.size, bit_offset)
+        need = _packed_bytes(n, bit_offset)
         if where.size < need:
-            raise ValueError("where holds %d bytes, %d values from bit %d on need %d" % (where.size, values.size, bit_offset, need))
+            raise ValueError("where holds %d bytes, %d values from bit %d on need %d" % (where.size, n, bit_offset, need))
     else:
         if where.dtype != np.bool_:
             raise ValueError("where must have dtype bool (packed=True: a uint8 bitmap), not %s" % where.dtype)
-        if where.size != values.size:
-            raise ValueError("where must have one element per value (%d), not %d" % (values.size, where.size))
-    return np.ascontiguousarray(values), np.ascontiguousarray(where), bit_offset
+        if where.size != n:
+            raise ValueError("where must have one element per value (%d), not %d" % (n, where.size))
+    return np.ascontiguousarray(where), bit_offset
+
+
+def _check_numpy(values, where, packed, bit_offset):
+    if not isinstance(values, np.ndarray):
+        raise ValueError("values must be a numpy.ndarray, not %s" % type(values).__name__)
+    if values.dtype != np.uint16:
+        raise ValueError("values must have dtype uint16, not %s" % values.dtype)
+    if values.ndim != 1:
+        raise ValueError("values must be 1-D, not %d-D" % values.ndim)
+    where, bit_offset = _check_selection_numpy(where, values.size, packed, bit_offset)
+    return np.ascontiguousarray(values), where, bit_offset
+
+
+def _check_selection_torch(where, n: int, packed, bit_offset) -> int:
+    """the selection of a tensor of ``n`` elements (also wide_where.py's; devices are checked by the caller); the bit offset"""
+    import torch
+
+    if not isinstance(where, torch.Tensor):
+        raise ValueError("where must be a torch.Tensor, not %s" % type(where).__name__)
+    if where.dim() != 1 or not where.is_contiguous():
+        raise ValueError("where must be 1-D and contiguous")
+    bit_offset = _check_bit_offset(packed, bit_offset)
+    if packed:
+        if where.dtype != torch.uint8:
+            raise ValueError("where must have dtype torch.uint8 with packed=True (an LSB-first bitmap), not %s" % where.dtype)
+        need = _packed_bytes(n, bit_offset)
+        if where.numel() < need:
+            raise ValueError("where holds %d bytes, %d values from bit %d on need %d" % (where.numel(), n, bit_offset, need))
+    else:
+        if where.dtype != torch.bool:
+            raise ValueError("where must have dtype torch.bool (packed=True: a torch.uint8 bitmap), not %s" % where.dtype)
+        if where.numel() != n:
+            raise ValueError("where must have one element per value (%d), not %d" % (n, where.numel()))
+    return bit_offset
 
 
 def _check_torch(t, where, packed, bit_offset) -> int:
@@ -67,23 +96,12 @@ def _check_torch(t, where, packed, bit_offset) -> int:
         raise ValueError("t must have dtype int16 or uint16, not %s" % t.dtype)
     if t.dim() != 1 or not t.is_contiguous():
         raise ValueError("t must be 1-D and contiguous")
-    if not isinstance(where, torch.Tensor):
-        raise ValueError("where must be a torch.Tensor, not %s" % type(where).__name__)
-    if where.dim() != 1 or not where.is_contiguous():
-        raise ValueError("where must be 1-D and contiguous")
-    bit_offset = _check_bit_offset(packed, bit_offset)
-    if packed:
-        if where.dtype != torch.uint8:
-            raise ValueError("where must have dtype torch.uint8 with packed=True (an LSB-first bitmap), not %s" % where.dtype)
-        need = _packed_bytes(t.numel(), bit_offset)
-        if where.numel() < need:
-            raise ValueError("where holds %d bytes, %d values from bit %d on need %d" % (where.numel(), t.numel(), bit_offset, need))
-    else:
-        if where.dtype != torch.bool:
-            raise ValueError("where must have dtype torch.bool (packed=True: a torch.uint8 bitmap), not %s" % where.dtype)
-        if where.numel() != t.numel():
-            raise ValueError("where must have one element per value (%d), not %d" % (t.numel(), where.numel()))
-    return bit_offset
+    return _check_selection_torch(where, t.numel(), packed, bit_offset)
+
+
+def _check_sel_bits(sel_bits) -> None:
+    if sel_bits not in (1, 8) or isinstance(sel_bits, bool):
+        raise ValueError("sel_bits must be 1 (an LSB-first bitmap) or 8 (one byte per element), not %r" % (sel_bits,))
 
 
 def counters_where(values, where, packed: bool = False, bit_offset: int = 0, superset: bool = False):
@@ -111,8 +129,7 @@ def count_device_ptr_where(ptr: int, n: int, sel_ptr: int, sel_bits: int, sel_of
     """``(uint64[32], int selected)`` of a device array of ``n`` ``uint16`` flags under a device selection, both given as raw
     pointers: ``sel_bits`` 1 = LSB-first bitmap, 8 = one byte per element; element ``i`` is bit / byte ``sel_offset + i``.
     Synchronous (``FLAGSTATS_hip_device_u16_where_sync``)."""
-    if sel_bits not in (1, 8) or isinstance(sel_bits, bool):
-        raise ValueError("sel_bits must be 1 (an LSB-first bitmap) or 8 (one byte per element), not %r" % (sel_bits,))
+    _check_sel_bits(sel_bits)
     _checks.check_raw_ints((("ptr", ptr), ("n", n), ("sel_ptr", sel_ptr), ("sel_offset", sel_offset)), non_negative=("n", "sel_offset"))
     ptr, n, sel_ptr, sel_offset = int(ptr), int(n), int(sel_ptr), int(sel_offset)
     out = np.zeros(32, dtype=np.uint64)
