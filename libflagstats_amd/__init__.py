@@ -27,6 +27,8 @@ Only what the path needs:
                      tensor, in one launch
 * ``segments_wide_filter`` the filter per segment of an int32 / int64 (or 16-bit) array or tensor in place: rows of counters,
                      the number of reads that pass and one high-bit mask per CSR segment, in one launch
+* ``segments_wide_where`` the mask or bitmap per segment of an int32 / int64 (or 16-bit) array or tensor in place: rows of
+                     counters, the number selected and one high-bit mask of the selected elements per CSR segment, in one launch
 * ``dist``          shard + single all-reduce for multi-GPU runs
 
 The hot path has no CPU fallback: importing the compute entry points without the
@@ -65,6 +67,12 @@ from .segments_where import (  # noqa: F401
     counters_segments_where,
     flagstats_segments_where,
 )
+from .segments_wide_where import (  # noqa: F401
+    count_segments_device_ptr_ints_where,
+    count_segments_torch_ints_where,
+    counters_segments_ints_where,
+    flagstats_segments_ints_where,
+)
 from .where import count_device_ptr_where, count_torch_where, counters_where, flagstats_where  # noqa: F401
 from .wide import count_device_ptr_ints, count_torch_ints, counters_ints, flagstats_ints  # noqa: F401
 from .wide_filter import (  # noqa: F401
@@ -90,4 +98,5 @@ __all__ = ["flagstats", "flagstats_x64", "SAM_FLAG_NAMES", "flagstats_segments",
            "counters_segments_ints_filter", "flagstats_segments_ints_filter", "count_segments_device_ptr_ints_filter",
            "count_segments_torch_ints_filter", "counters_segments_where", "flagstats_segments_where",
            "count_segments_device_ptr_where", "count_segments_torch_where", "counters_ints_where", "flagstats_ints_where",
-           "count_device_ptr_ints_where", "count_torch_ints_where"]
+           "count_device_ptr_ints_where", "count_torch_ints_where", "counters_segments_ints_where", "flagstats_segments_ints_where",
+           "count_segments_device_ptr_ints_where", "count_segments_torch_ints_where"]
