@@ -209,6 +209,46 @@ int FLAGSTATS_hip_device_u16_filter_sync(const uint16_t* d_array, uint64_t n, ui
 int FLAGSTATS_hip_u16_x64_filter(const uint16_t* array, uint64_t n, uint32_t require, uint32_t exclude, const uint8_t* mapq,
                                  uint32_t min_mapq, uint64_t* out, uint64_t* selected, int flags);
 
+/* ================= filtered and selected: samtools' view filter -f / -F / -q under a bitmap or a byte mask =================
+ * The table for `-F 0x904 -q 30` of a FLAG column that has a validity bitmap (Arrow leaves the value of a null slot unspecified,
+ * so a null FLAG must not be tested or counted), or of the reads that pass the filter AND lie in a region / read-group / dedup
+ * mask: filter and selection together, in one kernel and one pass, with no combined mask in memory.
+ *   counted(i) = pass(i) && sel(i)
+ * pass(i) is exactly that of the filtered entries (require, exclude, mapq, min_mapq) and sel(i) exactly that of the `where`
+ * entries (sel_bits == 1: an LSB-first bitmap at any sel_offset; sel_bits == 8: one byte per element, any non-zero byte
+ * selects).  The 32 counters are FLAGSTAT_scalar's over {array[i] : counted(i), 0 <= i < n}; `selected` is the number of i with
+ * counted(i).  require & exclude != 0 is legal and counts nothing (nothing is launched, nothing is read).  min_mapq == 0 reads
+ * no byte of `mapq`, which may then be NULL; otherwise exactly mapq[0 .. n) is read.  Only bytes of `sel` that hold the bit or
+ * byte of an element are read.  The FLAG or MAPQ of an element that is not selected may be read; it enters no counter and no
+ * count.  A NULL selection with n > 0 is refused: the filtered entries are the call without one.
+ * `flags`: as for both parents -- bit 0 = store (out = counters, all 32 slots written; selected = count) instead of +=; bit 1 =
+ * superset (slots 0 / 16 = primary paired reads among those counted, slot 9 = selected minus slot 25).  `selected` /
+ * `d_selected` may be NULL: nothing is reported.  n == 0 succeeds and touches nothing (the store form writes zeros).
+ * Refused (non-zero, message in FLAGSTATS_hip_last_error, out and selected untouched, nothing launched): what the filtered or
+ * the `where` entries refuse -- require or exclude above 0xFFFF, min_mapq above 255, sel_bits other than 1 or 8, flag bits other
+ * than 0 and 1, a NULL array, a NULL mapq with min_mapq > 0 or a NULL selection with n > 0, an odd array pointer, an n with n * 2
+ * not a size or too large for a wave's uint32 totals, a sel_offset + n that is no index, NULL counters; for the device forms also
+ * a d_out or d_selected that is not plain device memory, pointers on different devices, a stream of another device and an
+ * allocation shorter than the call needs (d_array: n * 2 bytes, d_mapq: n bytes when min_mapq > 0, d_sel: the bytes that hold the
+ * n bits or bytes, d_out: 256, d_selected: 8). */
+/* DEVICE array, MAPQ column and selection, DEVICE d_out[32] and d_selected[1] (uint64); asynchronous on `stream`: ONE kernel (the
+ * store form puts one memset per pointer in front of it; one in all when d_selected == d_out + 32), no workspace, nothing
+ * synchronised; may be captured into a graph.  Adds are atomic: launches on several streams may share d_out and d_selected in
+ * the += form. */
+int FLAGSTATS_hip_device_u16_filter_where(const uint16_t* d_array, uint64_t n, uint32_t require, uint32_t exclude,
+                                          const uint8_t* d_mapq, uint32_t min_mapq, const void* d_sel, uint64_t sel_offset,
+                                          int sel_bits, uint64_t* d_out, uint64_t* d_selected, int flags, void* stream);
+/* DEVICE array, MAPQ column and selection, HOST out[32] and selected[1]; synchronous */
+int FLAGSTATS_hip_device_u16_filter_where_sync(const uint16_t* d_array, uint64_t n, uint32_t require, uint32_t exclude,
+                                               const uint8_t* d_mapq, uint32_t min_mapq, const void* d_sel, uint64_t sel_offset,
+                                               int sel_bits, uint64_t* out, uint64_t* selected, int flags);
+/* HOST array, MAPQ column and selection, HOST out[32] and selected[1]; synchronous.  All three cross the bus in the engine's
+ * chunks (knob "chunk_flags"), each chunk's slices of the column and of the selection behind its flags; the counters are summed
+ * on the device. */
+int FLAGSTATS_hip_u16_x64_filter_where(const uint16_t* array, uint64_t n, uint32_t require, uint32_t exclude, const uint8_t* mapq,
+                                       uint32_t min_mapq, const void* sel, uint64_t sel_offset, int sel_bits, uint64_t* out,
+                                       uint64_t* selected, int flags);
+
 /* ================= filtered segments: samtools' view filter -f / -F / -q per segment =================
  * Per-contig, per-sample or per-block tables of the reads that pass `-F 0x904 -q 30`: the segmented entries under the filtered
  * entries' predicate, in one launch.  Segment i is [offsets[i], offsets[i+1]) under the contract of the segmented entries;

@@ -15,6 +15,8 @@ Only what the path needs:
                      bitmap selects, with the number selected, in one pass
 * ``filter``         the same counters for the reads that pass samtools' ``-f`` / ``-F`` / ``-q``
                      (FLAG bits required and excluded, a MAPQ threshold), with no mask array
+* ``filter_where``   the filter and a boolean mask or bitmap together: the counters of the reads that pass ``-f`` / ``-F`` /
+                     ``-q`` AND are selected (the non-null rows of an Arrow FLAG column), with their number, in one pass
 * ``segments_filter`` the filter per segment: rows of counters and the number of reads that pass, for
                      every CSR segment in one launch
 * ``segments_where`` the mask or bitmap per segment: rows of counters and the number of selected reads, for every CSR
@@ -43,6 +45,12 @@ from .segments import (  # noqa: F401
     segment_dicts,
 )
 from .filter import count_device_ptr_filter, count_torch_filter, counters_filter, flagstats_filter  # noqa: F401
+from .filter_where import (  # noqa: F401
+    count_device_ptr_filter_where,
+    count_torch_filter_where,
+    counters_filter_where,
+    flagstats_filter_where,
+)
 from .segments_filter import (  # noqa: F401
     count_segments_device_ptr_filter,
     count_segments_torch_filter,
@@ -99,4 +107,5 @@ __all__ = ["flagstats", "flagstats_x64", "SAM_FLAG_NAMES", "flagstats_segments",
            "count_segments_torch_ints_filter", "counters_segments_where", "flagstats_segments_where",
            "count_segments_device_ptr_where", "count_segments_torch_where", "counters_ints_where", "flagstats_ints_where",
            "count_device_ptr_ints_where", "count_torch_ints_where", "counters_segments_ints_where", "flagstats_segments_ints_where",
-           "count_segments_device_ptr_ints_where", "count_segments_torch_ints_where"]
+           "count_segments_device_ptr_ints_where", "count_segments_torch_ints_where", "counters_filter_where",
+           "flagstats_filter_where", "count_device_ptr_filter_where", "count_torch_filter_where"]
