@@ -323,6 +323,58 @@ int FLAGSTATS_hip_device_u16_segments_where_sync(const uint16_t* d_array, uint64
 int FLAGSTATS_hip_u16_x64_segments_where(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint64_t nseg, const void* sel,
                                          uint64_t sel_offset, int sel_bits, uint64_t* out, uint64_t* selected, int flags);
 
+/* ================= filtered and selected per segment: -f / -F / -q under a bitmap or byte mask, per CSR segment =================
+ * The table of `-F 0x904 -q 30` per row group, contig, sample or block of a FLAG column that has a validity bitmap (Arrow leaves
+ * the value of a null slot unspecified, so a null FLAG must not be tested, counted or reported in selected[i]), or of the reads
+ * that pass the filter AND lie in a region / read-group / dedup mask: the filtered segmented entries and the selected segmented
+ * entries together, in one launch and one pass, with no combined mask in memory, instead of one filter_where launch per segment.
+ *   counted(j) = pass(j) && sel(j)
+ * Segment i is [offsets[i], offsets[i+1]) under the contract of the segmented entries.  pass(j) is exactly that of the filtered
+ * entries (require, exclude, mapq, min_mapq: an overlapping pair is legal, counts nothing, launches nothing and reads nothing;
+ * min_mapq == 0 reads no byte of `mapq`, which may then be NULL) and sel(j) exactly that of the `where` entries, indexed by ARRAY
+ * ELEMENT, not by segment (sel_bits == 1: bit sel_offset + j of an LSB-first bitmap, any sel_offset; sel_bits == 8: byte
+ * sel_offset + j, any non-zero byte selects).  Row i of out[nseg][32] holds FLAGSTAT_scalar's counters over
+ * {array[j] : j in segment i, counted(j)}, and selected[i] (nseg uint64; the pointer may be NULL: nothing is reported) the number
+ * of such j.  Flags outside every segment count nowhere.  Only bytes of `sel` that hold the bit or byte of an element of [0, n)
+ * are ever read, and of `mapq` only bytes of elements of [0, n).  The FLAG or MAPQ of an element that is not selected may be
+ * read; it enters no counter and no count.  A NULL selection with n > 0 is refused: the filtered segmented entries are the call
+ * without one.
+ * `flags`: bit 0 = store (rows and selected[0 .. nseg) are zeroed in front, every slot of every row and every selected[i] is
+ * written, empty segments and segments with nothing counted read 0) instead of +=; bit 1 = superset (slots 0 / 16 = primary
+ * paired reads among those counted, slot 9 = selected[i] minus slot 25).  nseg == 0 succeeds and touches nothing.
+ * Refused (non-zero, message in FLAGSTATS_hip_last_error, out and selected untouched, nothing launched): what the filtered
+ * segmented or the selected segmented entries refuse -- require or exclude above 0xFFFF, min_mapq above 255, sel_bits other than
+ * 1 or 8, flag bits other than 0 and 1, NULL offsets or rows with nseg > 0, an nseg whose rows cannot be allocated, and with
+ * nseg > 0 a NULL array, a NULL mapq with min_mapq > 0 or a NULL selection with n > 0, an odd array pointer, an n with n * 2 not
+ * a size, a sel_offset + n that is no index, host offsets that decrease or end beyond n, an n too large for a wave's uint32
+ * totals; for the device forms also a d_out or d_selected that is not plain device memory, pointers on different devices, a
+ * stream of another device and an allocation shorter than the call needs (d_array: n * 2 bytes, d_mapq: n bytes when
+ * min_mapq > 0, d_sel: from d_sel up to the last byte that holds an element's bit or byte, d_offsets: (nseg + 1) * 8, d_out:
+ * nseg * 256, d_selected: nseg * 8).  Device offsets are not checked (that would synchronise): every offset the kernel reads is
+ * clamped to [0, n], so bad offsets give undefined counters and never an access outside the array, the column's and the
+ * selection's bytes of elements, the rows or the counts. */
+/* DEVICE array, column, selection and offsets, DEVICE d_out[nseg][32] and d_selected[nseg] (uint64); asynchronous on `stream`: ONE
+ * kernel (the store form puts one memset per pointer in front of it), no workspace, so a captured launch holds no pointer of the
+ * library's; make one plain call before capturing.  Adds are atomic: launches on several streams may share d_out and
+ * d_selected in the += form. */
+int FLAGSTATS_hip_device_u16_segments_filter_where(const uint16_t* d_array, uint64_t n, const uint64_t* d_offsets, uint64_t nseg,
+                                                   uint32_t require, uint32_t exclude, const uint8_t* d_mapq, uint32_t min_mapq,
+                                                   const void* d_sel, uint64_t sel_offset, int sel_bits, uint64_t* d_out,
+                                                   uint64_t* d_selected, int flags, void* stream);
+/* DEVICE array, column and selection, HOST offsets, HOST out[nseg][32] and selected[nseg]; synchronous */
+int FLAGSTATS_hip_device_u16_segments_filter_where_sync(const uint16_t* d_array, uint64_t n, const uint64_t* offsets, uint64_t nseg,
+                                                        uint32_t require, uint32_t exclude, const uint8_t* d_mapq, uint32_t min_mapq,
+                                                        const void* d_sel, uint64_t sel_offset, int sel_bits, uint64_t* out,
+                                                        uint64_t* selected, int flags);
+/* HOST array, column, selection and offsets, HOST out[nseg][32] and selected[nseg]; synchronous.  Only [offsets[0], offsets[nseg])
+ * of the array, of the column (when min_mapq > 0) and the selection bytes that cover it cross the bus, in the engine's chunks
+ * (knob "chunk_flags"), each chunk's slices of the column and of the selection behind its flags; a segment that spans chunks is
+ * summed on the device. */
+int FLAGSTATS_hip_u16_x64_segments_filter_where(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint64_t nseg,
+                                                uint32_t require, uint32_t exclude, const uint8_t* mapq, uint32_t min_mapq,
+                                                const void* sel, uint64_t sel_offset, int sel_bits, uint64_t* out, uint64_t* selected,
+                                                int flags);
+
 /* ================= filtered wide input: -f / -F / -q on a FLAG column held as 4-byte or 8-byte integers =================
  * The two normal cases at once: the column arrives as int32 or int64 (the wide entries) and the table wanted is that of
  * `samtools view -F 0x904 -q 30` (the filtered entries).  One pass over the array as it is, no uint16 copy, no mask array.

@@ -21,6 +21,8 @@ Only what the path needs:
                      every CSR segment in one launch
 * ``segments_where`` the mask or bitmap per segment: rows of counters and the number of selected reads, for every CSR
                      segment in one launch (the selection is indexed by array element)
+* ``segments_filter_where`` the filter and the mask or bitmap together per segment: rows of counters and the number of reads
+                     that pass AND are selected, for every CSR segment in one launch
 * ``wide_filter``    the filter on int32 / int64 (and 16-bit) arrays and tensors in place: counters, the number of
                      reads that pass and the mask of bits seen above bit 15, in one pass
 * ``wide_where``     the mask or bitmap on int32 / int64 (and 16-bit) arrays and tensors in place: counters, the number
@@ -75,6 +77,12 @@ from .segments_where import (  # noqa: F401
     counters_segments_where,
     flagstats_segments_where,
 )
+from .segments_filter_where import (  # noqa: F401
+    count_segments_device_ptr_filter_where,
+    count_segments_torch_filter_where,
+    counters_segments_filter_where,
+    flagstats_segments_filter_where,
+)
 from .segments_wide_where import (  # noqa: F401
     count_segments_device_ptr_ints_where,
     count_segments_torch_ints_where,
@@ -108,4 +116,6 @@ __all__ = ["flagstats", "flagstats_x64", "SAM_FLAG_NAMES", "flagstats_segments",
            "count_segments_device_ptr_where", "count_segments_torch_where", "counters_ints_where", "flagstats_ints_where",
            "count_device_ptr_ints_where", "count_torch_ints_where", "counters_segments_ints_where", "flagstats_segments_ints_where",
            "count_segments_device_ptr_ints_where", "count_segments_torch_ints_where", "counters_filter_where",
-           "flagstats_filter_where", "count_device_ptr_filter_where", "count_torch_filter_where"]
+           "flagstats_filter_where", "count_device_ptr_filter_where", "count_torch_filter_where",
+           "counters_segments_filter_where", "flagstats_segments_filter_where", "count_segments_device_ptr_filter_where",
+           "count_segments_torch_filter_where"]

@@ -15,7 +15,8 @@
 // back at bit 0, so an edge step runs unfunnelled.
 //
 // Predicate.  The filtered kernel's test ends in p = ~q & 0x80808080 (pass4, flagstat_filter_device.h): 0x80 per passing flag
-// of 4.  The selection joins p in registers, in front of the popcount and of the v_perm_b32 that makes the byte masks; the
+// of 4.  The selection joins p in registers (counted_bits / counted_bytes of flagstat_filter_where_device.h, shared with
+// flagstat_segments_filter_where.hip), in front of the popcount and of the v_perm_b32 that makes the byte masks; the
 // bitmap kernel's selector table in LDS is not used (the pass word exists anyway, and the table would cost LDS traffic per
 // vector on top).  Per 4 flags:
 //   bitmap:  b  = v_bfe_u32(x, sh | sh + 4, 4)       the 4 selection bits (shift 0: v_and_b32 / v_lshrrev_b32)
@@ -36,27 +37,13 @@
 #include "flagstat_derived_host.h"
 #include "flagstat_filter_device.h"
 #include "flagstat_filter_where.h"
+#include "flagstat_filter_where_device.h"
 #include "flagstat_where.h"
 #include "flagstat_where_device.h"
 
 namespace fsk {
 
 constexpr int kFilterWhereDepth = 8;  // chain depth as K1: epochs of 255 steps
-
-// 0x80 per flag of 4 that passes (p: 0x80 per passing flag, nothing else) and whose selection bit is set; b: the 4 bits.  The
-// compiler folds the shift into the multiplier (one v_mul_lo_u32 by 0x10204080).  Shifting p instead, which keeps the multiply a
-// v_mul_u32_u24, measured 1.6-2.0 % slower without MAPQ and the same with it (profiles/r20/filter_where_ab.log)
-__device__ __forceinline__ uint32_t counted_bits(uint32_t p, uint32_t b)
-{
-    return p & (__umul24(b, 0x204081u) << 7);
-}
-
-// 0x80 per flag of 4 that passes and whose selection byte in x is not zero
-__device__ __forceinline__ uint32_t counted_bytes(uint32_t p, uint32_t x)
-{
-    const uint32_t t = (x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;   // no carry leaves a byte
-    return __builtin_amdgcn_bitop3_b32(t, x, p, kTtOrAnd);
-}
 
 // One step: 8 vectors of 16 B per lane = 64 flags through K1's tree (tree_step, flagstat_count_core.h), predicate and selection
 // applied in the per-vector front.  ROLL 0 (edge steps): the vectors are in v[], their MAPQ bytes in m[], their selection in
