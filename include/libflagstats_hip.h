@@ -458,6 +458,55 @@ int FLAGSTATS_hip_device_wide_where_sync(const void* d_array, uint64_t n, int el
 int FLAGSTATS_hip_wide_x64_where(const void* array, uint64_t n, int elem_bytes, const void* sel, uint64_t sel_offset, int sel_bits,
                                  uint64_t* out, uint64_t* selected, uint64_t* high, int flags);
 
+/* ================= filter AND selection on wide input: -f / -F / -q under a bitmap or byte mask, int32 / int64 column ==========
+ * What an Arrow / Parquet / pandas / torch reader holds: the FLAG column as int32 or int64, an LSB-first validity bitmap (often
+ * sliced to an odd bit offset) and a uint8 MAPQ column -- and it wants `samtools view -F 0x904 -q 30 | samtools flagstat` over the
+ * valid rows.  One pass and one kernel over the three as they are.  With f(i) = the low 16 bits of element i (little-endian
+ * elements of `elem_bytes` = 4 or 8 bytes, aligned to elem_bytes), pass(i) exactly as in FLAGSTATS_hip_device_wide_filter and
+ * sel(i) exactly as in FLAGSTATS_hip_device_wide_where:
+ *   out      : FLAGSTAT_scalar's 32 counters over {f(i) : pass(i) && sel(i), 0 <= i < n}
+ *   selected : the number of i with pass(i) && sel(i)
+ *   high     : OR of (element & ~0xFFFF), taken as unsigned, over the elements with sel(i), PASSING OR NOT.  Both parents' rules at
+ *              once: the filter never restricts the mask (the predicate sees the low 16 bits only), the selection always does (the
+ *              value of a null slot is unspecified).  With an all-ones selection the three are FLAGSTATS_hip_device_wide_filter's,
+ *              with require == exclude == min_mapq == 0 they are FLAGSTATS_hip_device_wide_where's.
+ * min_mapq == 0 reads no MAPQ byte and `mapq` may be NULL; otherwise only mapq[0 .. n) is read, at any alignment.  Only bytes of
+ * `sel` that hold the bit or byte of an element of [0, n) and only dwords of elements of [0, n) are ever read; the FLAG or MAPQ
+ * of an element that is not selected may be read but enters nothing.  require & exclude != 0 is legal: it counts nothing,
+ * launches nothing and READS NOTHING, so `high` is 0 in the store form and untouched otherwise.
+ * `flags`: bit 0 = store (out = counters, all 32 slots written; selected = count; high = mask) instead of out += counters,
+ * selected += count, high |= mask; bit 1 = superset (slots 0 / 16 = primary paired reads among the counted, slot 9 = selected
+ * minus slot 25).  `selected` / `d_selected` and `high` / `d_high` may each be NULL: that value is not reported.
+ * n == 0 succeeds and touches nothing (the store form writes zeros to all three).
+ * Refused (non-zero, message in FLAGSTATS_hip_last_error, outputs untouched, nothing launched): everything the filtered wide
+ * entries and the selected wide entries refuse, in their words -- elem_bytes other than 4 or 8 (2: use the u16 filter_where
+ * entries), require or exclude above 0xFFFF, min_mapq above 255, sel_bits other than 1 or 8, an array pointer not aligned to
+ * elem_bytes, an n with n * elem_bytes not a size or too large for a wave's uint32 totals, a sel_offset + n that is no index, a
+ * NULL array with n > 0, a NULL mapq with min_mapq > 0 and n > 0, a NULL selection with n > 0 (no selection: use the filtered
+ * wide entries), flag bits other than 0 and 1, NULL counters; for the device form also a d_out, d_selected or d_high that is not
+ * plain device memory, host memory for d_array, d_sel or d_mapq, pointers on different devices, a stream of another device and
+ * an allocation shorter than the call needs (d_array: n * elem_bytes bytes, d_mapq: n, d_sel: from d_sel up to the last byte
+ * that holds an element's bit or byte, d_out: 256, d_selected: 8, d_high: 8). */
+/* DEVICE array, MAPQ column and selection, DEVICE d_out[32], d_selected[1] and d_high[1] (uint64); asynchronous on `stream`: ONE
+ * kernel (the store form puts one zeroing per pointer in front of it; one in all when d_selected == d_out + 32 and d_high ==
+ * d_out + 33), no workspace, nothing synchronised, so a captured launch holds no pointer of the library's (capture and replay:
+ * tests/test_gpu_wide_filter_where_graphs.py; make one plain call before capturing).  Adds and ORs are atomic: launches on
+ * several streams may share the three in the += form. */
+int FLAGSTATS_hip_device_wide_filter_where(const void* d_array, uint64_t n, int elem_bytes, uint32_t require, uint32_t exclude,
+                                           const uint8_t* d_mapq, uint32_t min_mapq, const void* d_sel, uint64_t sel_offset, int sel_bits,
+                                           uint64_t* d_out, uint64_t* d_selected, uint64_t* d_high, int flags, void* stream);
+/* DEVICE array, MAPQ column and selection, HOST out[32], selected[1] and high[1]; synchronous */
+int FLAGSTATS_hip_device_wide_filter_where_sync(const void* d_array, uint64_t n, int elem_bytes, uint32_t require, uint32_t exclude,
+                                                const uint8_t* d_mapq, uint32_t min_mapq, const void* d_sel, uint64_t sel_offset,
+                                                int sel_bits, uint64_t* out, uint64_t* selected, uint64_t* high, int flags);
+/* HOST array, MAPQ column and selection, HOST out[32], selected[1] and high[1]; synchronous.  The array crosses the bus as it is
+ * in the engine's chunks (knob "chunk_flags": chunk_flags * 2 bytes of elements each), each chunk's slices of the MAPQ column and
+ * of the selection behind its elements (a bitmap slice from the byte that holds the chunk's first bit); counters, count and mask
+ * are summed / ORed on the device. */
+int FLAGSTATS_hip_wide_x64_filter_where(const void* array, uint64_t n, int elem_bytes, uint32_t require, uint32_t exclude,
+                                        const uint8_t* mapq, uint32_t min_mapq, const void* sel, uint64_t sel_offset, int sel_bits,
+                                        uint64_t* out, uint64_t* selected, uint64_t* high, int flags);
+
 /* ================= wide input per segment: a row and a high mask for every segment of an int32 / int64 column =================
  * The union of the segmented and the wide entries: segment i (i < nseg) is [offsets[i], offsets[i+1]) of an array of 4-byte or
  * 8-byte little-endian elements (aligned to elem_bytes), read as it is.  With f(j) = the low 16 bits of element j,

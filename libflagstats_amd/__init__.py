@@ -27,6 +27,9 @@ Only what the path needs:
                      reads that pass and the mask of bits seen above bit 15, in one pass
 * ``wide_where``     the mask or bitmap on int32 / int64 (and 16-bit) arrays and tensors in place: counters, the number
                      selected and the mask of bits seen above bit 15 of the selected elements, in one pass
+* ``wide_filter_where`` the filter and the mask or bitmap together on int32 / int64 (and 16-bit) arrays and tensors in place:
+                     counters, the number of reads that pass AND are selected and the mask of bits seen above bit 15 of the
+                     selected elements, in one pass
 * ``segments_wide``  rows of counters and one high-bit mask per CSR segment of an int32 / int64 (or 16-bit) array or
                      tensor, in one launch
 * ``segments_wide_filter`` the filter per segment of an int32 / int64 (or 16-bit) array or tensor in place: rows of counters,
@@ -97,6 +100,12 @@ from .wide_filter import (  # noqa: F401
     counters_ints_filter,
     flagstats_ints_filter,
 )
+from .wide_filter_where import (  # noqa: F401
+    count_device_ptr_ints_filter_where,
+    count_torch_ints_filter_where,
+    counters_ints_filter_where,
+    flagstats_ints_filter_where,
+)
 from .wide_where import (  # noqa: F401
     count_device_ptr_ints_where,
     count_torch_ints_where,
@@ -118,4 +127,5 @@ __all__ = ["flagstats", "flagstats_x64", "SAM_FLAG_NAMES", "flagstats_segments",
            "count_segments_device_ptr_ints_where", "count_segments_torch_ints_where", "counters_filter_where",
            "flagstats_filter_where", "count_device_ptr_filter_where", "count_torch_filter_where",
            "counters_segments_filter_where", "flagstats_segments_filter_where", "count_segments_device_ptr_filter_where",
-           "count_segments_torch_filter_where"]
+           "count_segments_torch_filter_where", "counters_ints_filter_where", "flagstats_ints_filter_where",
+           "count_device_ptr_ints_filter_where", "count_torch_ints_filter_where"]

@@ -102,6 +102,17 @@ SIGNATURES = {
                                                             ctypes.c_void_p, ctypes.c_int]),
     "FLAGSTATS_hip_wide_x64_where": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
                                                     ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    "FLAGSTATS_hip_device_wide_filter_where": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32,
+                                                              ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                                              ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                              ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "FLAGSTATS_hip_device_wide_filter_where_sync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32,
+                                                                   ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                                                   ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                                   ctypes.c_void_p, ctypes.c_int]),
+    "FLAGSTATS_hip_wide_x64_filter_where": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
+                                                           ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
     "FLAGSTATS_hip_device_u16_segments_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                                                 ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
                                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
@@ -245,7 +256,7 @@ SIGNATURES = {
 }
 
 # internal launchers the tests and tests/perf drive directly (csrc/flagstat_wide.h, csrc/flagstat_where.h, csrc/flagstat_filter.h,
-# csrc/flagstat_segments_filter.h, csrc/flagstat_wide_filter.h, csrc/flagstat_segments_wide.h, csrc/flagstat_segments_wide_filter.h, csrc/flagstat_segments_where.h, csrc/flagstat_wide_where.h, csrc/flagstat_segments_wide_where.h, csrc/flagstat_filter_where.h, csrc/flagstat_segments_filter_where.h); not part of the public headers, so kept apart from SIGNATURES, which mirrors those
+# csrc/flagstat_segments_filter.h, csrc/flagstat_wide_filter.h, csrc/flagstat_segments_wide.h, csrc/flagstat_segments_wide_filter.h, csrc/flagstat_segments_where.h, csrc/flagstat_wide_where.h, csrc/flagstat_segments_wide_where.h, csrc/flagstat_filter_where.h, csrc/flagstat_segments_filter_where.h, csrc/flagstat_wide_filter_where.h); not part of the public headers, so kept apart from SIGNATURES, which mirrors those
 INTERNAL_SIGNATURES = {
     "fsk_launch_wide": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                        ctypes.c_uint32, ctypes.c_void_p]),
@@ -284,6 +295,10 @@ INTERNAL_SIGNATURES = {
                                              ctypes.c_void_p]),
     "fsk_wide_where_geometry": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_int,
                                                ctypes.c_uint32, _U64P]),
+    "fsk_launch_wide_filter_where": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
+                                                    ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32,
+                                                    ctypes.c_void_p]),
     "fsk_launch_segments_wide_where": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
                                                       ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p]),

@@ -1,0 +1,138 @@
+"""Flagstat of the reads that pass samtools' view filter AND that a mask selects, on a FLAG column in the integer dtype it
+arrives in: ``-f require -F exclude -q min_mapq`` over the valid rows of an Arrow ``int32`` column under its validity bitmap, or
+of an ``int64`` tensor under a ``torch.bool`` mask -- read once and in place, by one kernel, with no ``astype(np.uint16)`` copy,
+no combined mask and no ``values[mask]`` compaction in front.
+
+The predicate is that of ``filter`` and sees the low 16 bits of an element; the selection is that of ``where`` (a boolean mask,
+or with ``packed=True`` an LSB-first ``uint8`` bitmap that starts ``bit_offset`` bits into its first byte); the value checks and
+the mask ``high`` are those of ``wide``.  An element is counted when it passes and is selected; ``selected`` is the number of
+those.  ``high`` is the OR of ``element & ~0xFFFF`` over the **selected** elements, passing or not -- ``wide_filter``'s rule (the
+filter never restricts it) and ``wide_where``'s (the selection always does: what lies in a null slot is unspecified) at once.
+One exception: ``require & exclude != 0`` (legal, counts nothing) reads nothing at all, so ``high`` is then 0.  Two-byte dtypes go
+to the ``uint16`` ``filter_where`` entries and cannot carry high bits.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _checks, _lib
+from . import filter as _filter
+from . import filter_where as _filter_where
+from . import where as _where
+from . import wide as _wide
+from .pyflagstats import _as_dict
+
+STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
+
+
+def counters_ints_filter_where(values, where, require: int = 0, exclude: int = 0, mapq=None, min_mapq: int = 0, packed: bool = False,
+                               bit_offset: int = 0, superset: bool = False):
+    """``(uint64[32] counters, int selected, int high)`` of the elements of a 1-D host array of dtype int16, uint16, int32,
+    uint32, int64 or uint64 that pass the filter (``mapq``: a ``uint8`` array of the same length, needed when ``min_mapq > 0``)
+    and that ``where`` selects: a ``bool`` array of the same length, or (``packed=True``) a ``uint8`` LSB-first bitmap of at least
+    ``(bit_offset + n + 7) // 8`` bytes whose bit ``bit_offset + i`` belongs to ``values[i]``.  ``high`` is the OR of the bits
+    above bit 15 of the selected elements, passing or not.  16-bit input goes to ``FLAGSTATS_hip_u16_x64_filter_where``
+    (``high`` = 0), wider input to ``FLAGSTATS_hip_wide_x64_filter_where``."""
+    v = _wide._check_values(values)
+    w, bit_offset = _where._check_selection_numpy(where, v.size, packed, bit_offset)
+    q = _filter._check_mapq_numpy(mapq, v.size)
+    require, exclude, min_mapq = _filter._check_predicate(require, exclude, min_mapq, q is not None)
+    if v.dtype.itemsize == 2:
+        out, selected = _filter_where.counters_filter_where(v.view(np.uint16), w, require=require, exclude=exclude, mapq=q,
+                                                            min_mapq=min_mapq, packed=packed, bit_offset=bit_offset, superset=superset)
+        return out, selected, 0
+    out = np.zeros(32, dtype=np.uint64)
+    selected, high = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _lib.check(_lib.lib().FLAGSTATS_hip_wide_x64_filter_where(v.ctypes.data if v.size else None, v.size, v.dtype.itemsize, require,
+                                                              exclude, q.ctypes.data if q is not None and q.size else None, min_mapq,
+                                                              w.ctypes.data if v.size else None, bit_offset, 1 if packed else 8,
+                                                              out.ctypes.data, ctypes.byref(selected), ctypes.byref(high),
+                                                              STORE | (SUPERSET if superset else 0)),
+               "FLAGSTATS_hip_wide_x64_filter_where")
+    return out, int(selected.value), int(high.value)
+
+
+def flagstats_ints_filter_where(values, where, require: int = 0, exclude: int = 0, mapq=None, min_mapq: int = 0, packed: bool = False,
+                                bit_offset: int = 0, strict: bool = True) -> dict:
+    """The dict of ``pyflagstats.flagstats_x64`` over the counted values: ``n_values`` is their number and ``mapped`` is derived
+    from it.  ``strict`` (default): a SELECTED value outside 0..65535 -- passing or not -- raises ``ValueError`` naming the bits
+    seen above bit 15 (a value that is not selected never does); ``strict=False``: the dict of the truncated values with the
+    mask as an extra key ``"high_bits"``."""
+    counters, selected, high = counters_ints_filter_where(values, where, require=require, exclude=exclude, mapq=mapq, min_mapq=min_mapq,
+                                                          packed=packed, bit_offset=bit_offset)
+    if strict and high:
+        raise ValueError(_wide.high_bits_message(high))
+    ret = _as_dict(counters, selected)
+    if not strict:
+        ret["high_bits"] = high
+    return ret
+
+
+def count_device_ptr_ints_filter_where(ptr: int, n: int, elem_bytes: int, sel_ptr: int, sel_bits: int, require: int = 0, exclude: int = 0,
+                                       mapq_ptr: int = 0, min_mapq: int = 0, sel_offset: int = 0, superset: bool = False):
+    """``(uint64[32], int selected, int high)`` of a device array of ``n`` 4-byte or 8-byte integers under the filter and a
+    device selection, all given as raw pointers: the MAPQ column has ``n`` bytes (``mapq_ptr`` 0: none); ``sel_bits`` 1 =
+    LSB-first bitmap, 8 = one byte per element, element ``i`` being bit / byte ``sel_offset + i``.  ``high`` covers the selected
+    elements, passing or not.  Synchronous (``FLAGSTATS_hip_device_wide_filter_where_sync``)."""
+    if elem_bytes not in (4, 8):
+        raise ValueError("elem_bytes must be 4 or 8 (16-bit arrays: filter_where.count_device_ptr_filter_where), not %r" % (elem_bytes,))
+    _where._check_sel_bits(sel_bits)
+    _checks.check_raw_ints((("ptr", ptr), ("n", n), ("sel_ptr", sel_ptr), ("sel_offset", sel_offset), ("mapq_ptr", mapq_ptr)),
+                           non_negative=("n", "sel_offset"))
+    require, exclude, min_mapq = _filter._check_predicate(require, exclude, min_mapq, mapq_ptr != 0)
+    ptr, n, sel_ptr, sel_offset, mapq_ptr = int(ptr), int(n), int(sel_ptr), int(sel_offset), int(mapq_ptr)
+    out = np.zeros(32, dtype=np.uint64)
+    selected, high = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _lib.check(_lib.lib().FLAGSTATS_hip_device_wide_filter_where_sync(ptr if n else None, n, elem_bytes, require, exclude,
+                                                                      mapq_ptr if n and mapq_ptr else None, min_mapq,
+                                                                      sel_ptr if n else None, sel_offset, sel_bits, out.ctypes.data,
+                                                                      ctypes.byref(selected), ctypes.byref(high),
+                                                                      STORE | (SUPERSET if superset else 0)),
+               "FLAGSTATS_hip_device_wide_filter_where_sync")
+    return out, int(selected.value), int(high.value)
+
+
+def count_torch_ints_filter_where(t, where, require: int = 0, exclude: int = 0, mapq=None, min_mapq: int = 0, packed: bool = False,
+                                  bit_offset: int = 0, out=None, selected=None, high=None, store: bool = False, superset: bool = False):
+    """Counters, counted elements and high-bit mask of the elements of a 1-D contiguous integer CUDA tensor of 2-, 4- or 8-byte
+    elements that pass the filter (``mapq``: a 1-D contiguous ``torch.uint8`` tensor of ``t.numel()`` elements on ``t``'s
+    device, needed when ``min_mapq > 0``) and that ``where`` selects -- a ``torch.bool`` tensor of ``t.numel()`` elements or
+    (``packed=True``) a ``torch.uint8`` LSB-first bitmap of at least ``(bit_offset + n + 7) // 8`` bytes -- on torch's current
+    stream, nothing synchronised.
+
+    Returns ``(out, selected, high)``: ``int64[32]``, ``int64[1]`` and ``int64[1]`` CUDA tensors on ``t``'s device (made zeroed
+    when not given).  ``store=False`` adds into ``out`` and ``selected`` and ORs into ``high``; ``store=True`` overwrites all
+    three.  ``high`` is the OR of the bits above bit 15 of the selected elements, passing or not.  A 2-byte tensor goes to the
+    ``uint16`` ``filter_where`` entry and cannot carry high bits: ``high`` is left as it is (zeroed with ``store``).
+    ``int(high)`` reads the mask as a signed 64-bit number: compare with 0, or take ``int(high) & (2**64 - 1)``."""
+    import torch
+
+    _wide._check_tensor(t)
+    bit_offset = _where._check_selection_torch(where, t.numel(), packed, bit_offset)
+    _filter._check_mapq_torch(mapq, t.numel())
+    require, exclude, min_mapq = _filter._check_predicate(require, exclude, min_mapq, mapq is not None)
+    _checks.check_result_pair(out, "selected", selected)
+    _checks.check_result_pair(None, "high", high)
+    out, selected = _checks.place_result_pair(t, out, "selected", selected, others=(("where", where), ("mapq", mapq), ("high", high)))
+    if high is None:
+        high = torch.zeros(1, dtype=torch.int64, device=t.device)
+    if t.element_size() == 2:
+        if store:
+            with torch.cuda.device(t.device):
+                high.zero_()
+        _filter_where.count_torch_filter_where(t, where, require=require, exclude=exclude, mapq=mapq, min_mapq=min_mapq, packed=packed,
+                                               bit_offset=bit_offset, out=out, selected=selected, store=store, superset=superset)
+        return out, selected, high
+    lib = _lib.lib()
+    with torch.cuda.device(t.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+        n = t.numel()
+        flags = (STORE if store else 0) | (SUPERSET if superset else 0)
+        _lib.check(lib.FLAGSTATS_hip_device_wide_filter_where(t.data_ptr() if n else None, n, t.element_size(), require, exclude,
+                                                              mapq.data_ptr() if mapq is not None and n else None, min_mapq,
+                                                              where.data_ptr() if n else None, bit_offset, 1 if packed else 8,
+                                                              out.data_ptr(), selected.data_ptr(), high.data_ptr(), flags, stream),
+                   "FLAGSTATS_hip_device_wide_filter_where")
+    return out, selected, high
