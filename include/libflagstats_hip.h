@@ -644,6 +644,68 @@ int FLAGSTATS_hip_wide_x64_segments_where(const void* array, uint64_t n, int ele
                                           const void* sel, uint64_t sel_offset, int sel_bits, uint64_t* out, uint64_t* selected,
                                           uint64_t* high, int flags);
 
+/* ================= filtered and selected wide input per segment: -f / -F / -q under a bitmap or byte mask for every segment of
+ * an int32 / int64 column =================
+ * The last cell of the grid {uint16, wide} x {whole array, per segment} x {no predicate, filter, mask, filter and mask}: what an
+ * Arrow / Parquet reader wants of an int32 (or int64) FLAG column, its validity bitmap at some bit offset, a uint8 MAPQ column
+ * and row-group, contig or sample offsets -- the `-F 0x904 -q 30` table per segment over the non-null rows -- in one pass over
+ * the three columns as they are and one launch: no uint16 copy, no combined mask, no launch per segment.  Segment i (i < nseg) is
+ * [offsets[i], offsets[i+1]) of an array of 4-byte or 8-byte little-endian elements (aligned to elem_bytes).  The predicate is
+ * FLAGSTATS_hip_device_wide_segments_filter's (`mapq`: one uint8 per element of the whole array, at any byte alignment;
+ * min_mapq == 0 reads no byte of it and it may then be NULL), the selection FLAGSTATS_hip_device_wide_segments_where's, indexed
+ * by ARRAY ELEMENT (sel_bits == 1: bit sel_offset + j of an LSB-first bitmap, any bit offset; sel_bits == 8: byte sel_offset + j,
+ * any non-zero byte selects).  With f(j) = the low 16 bits of element j:
+ *   out[i * 32 + slot] : FLAGSTAT_scalar's 32 counters over {f(j) : pass(j) && sel(j), offsets[i] <= j < offsets[i+1]}
+ *   selected[i]        : the number of j in segment i with pass(j) && sel(j)
+ *   high[i]            : OR of (element & ~0xFFFF), taken as unsigned, over the SELECTED elements ONLY of segment i and of no
+ *                        other, PASSING OR NOT -- FLAGSTATS_hip_device_wide_filter_where's meaning per segment, both parents'
+ *                        rules at once: the filter never restricts the mask (it sees the low 16 bits only), the selection always
+ *                        does (the value of a null slot is unspecified and must not make high[i] != 0)
+ * Garbage in a null slot, an unselected element, an element of a neighbouring segment or of a gap, elements before offsets[0] and
+ * after offsets[nseg] and the bytes around the array enter no counter, no count and no mask; empty segments read 0.  Only bytes
+ * of `sel` and of `mapq` that hold the bit or byte of an element of [0, n) and only dwords of elements of [0, n) are ever read.
+ * `selected` / `d_selected` and `high` / `d_high` may each be NULL: that value is not reported.
+ * require & exclude != 0 is legal and counts nothing: nothing is launched and NOTHING IS READ, so in the store form rows, counts
+ * and masks are 0 and in the += form they are untouched -- `high` then says nothing about the column.
+ * `flags`: bit 0 = store (every slot of every row, every selected[i] and every high[i] written) instead of out += counters,
+ * selected += count, high |= mask; bit 1 = superset (slots 0 / 16 = primary paired reads among the counted, slot 9 =
+ * selected[i] minus slot 25).  nseg == 0 succeeds and touches nothing.
+ * DEVICE offsets are clamped to [0, n] and not checked for order, as documented for FLAGSTATS_hip_device_u16_segments: malformed
+ * offsets give undefined rows, counts and masks, never an access outside the array, the columns or the outputs.  HOST offsets are
+ * validated first (non-decreasing, offsets[nseg] <= n); on failure the outputs are left untouched.
+ * Refused (non-zero, message in FLAGSTATS_hip_last_error, outputs untouched, nothing launched): elem_bytes other than 4 or 8 (2:
+ * use the u16 segments_filter_where entries), sel_bits other than 1 or 8, flag bits other than 0 and 1, require or exclude above
+ * 0xFFFF, min_mapq above 255, NULL offsets or out with nseg > 0, an nseg whose counters are not a size, a NULL array or selection
+ * with n > 0, a NULL mapq with min_mapq > 0 and n > 0, an array pointer not aligned to elem_bytes, an n with n * elem_bytes not a
+ * size or too large for a wave's uint32 totals, a sel_offset + n that is no index; for the device form also a d_out, d_selected
+ * or d_high that is not plain device memory, host memory for d_array, d_mapq, d_sel or d_offsets, pointers on different devices,
+ * a stream of another device and an allocation shorter than the call needs (d_array: n * elem_bytes bytes, d_mapq: n bytes when
+ * min_mapq > 0, d_sel: from d_sel up to the last byte that holds an element's bit or byte, d_offsets: (nseg + 1) * 8, d_out:
+ * nseg * 256, d_selected: nseg * 8, d_high: nseg * 8). */
+/* DEVICE array, MAPQ column, selection and offsets, DEVICE d_out[nseg][32], d_selected[nseg] and d_high[nseg] (uint64);
+ * asynchronous on `stream`: ONE kernel (the store form puts one zeroing per pointer in front of it; one in all when d_selected ==
+ * d_out + nseg * 32 and d_high == d_selected + nseg), no workspace, nothing synchronised, so a captured launch holds no pointer of
+ * the library's (make one plain call before capturing).  Adds and ORs are atomic: launches on several streams may share the three
+ * in the += form. */
+int FLAGSTATS_hip_device_wide_segments_filter_where(const void* d_array, uint64_t n, int elem_bytes, const uint64_t* d_offsets,
+                                                    uint64_t nseg, uint32_t require, uint32_t exclude, const uint8_t* d_mapq,
+                                                    uint32_t min_mapq, const void* d_sel, uint64_t sel_offset, int sel_bits,
+                                                    uint64_t* d_out, uint64_t* d_selected, uint64_t* d_high, int flags, void* stream);
+/* DEVICE array, MAPQ column and selection, HOST offsets, HOST out[nseg][32], selected[nseg] and high[nseg]; synchronous */
+int FLAGSTATS_hip_device_wide_segments_filter_where_sync(const void* d_array, uint64_t n, int elem_bytes, const uint64_t* offsets,
+                                                         uint64_t nseg, uint32_t require, uint32_t exclude, const uint8_t* d_mapq,
+                                                         uint32_t min_mapq, const void* d_sel, uint64_t sel_offset, int sel_bits,
+                                                         uint64_t* out, uint64_t* selected, uint64_t* high, int flags);
+/* HOST array, MAPQ column, selection and offsets, HOST out[nseg][32], selected[nseg] and high[nseg]; synchronous.  Only
+ * [offsets[0], offsets[nseg]) of the array and of the column and the selection bytes that cover it cross the bus, in the engine's
+ * chunks (knob "chunk_flags": chunk_flags * 2 bytes of elements each), each chunk's slices of the column and of the selection
+ * behind its elements (a bitmap slice from the byte that holds the chunk's first bit); a segment that spans chunks is summed and
+ * ORed on the device. */
+int FLAGSTATS_hip_wide_x64_segments_filter_where(const void* array, uint64_t n, int elem_bytes, const uint64_t* offsets, uint64_t nseg,
+                                                 uint32_t require, uint32_t exclude, const uint8_t* mapq, uint32_t min_mapq,
+                                                 const void* sel, uint64_t sel_offset, int sel_bits, uint64_t* out,
+                                                 uint64_t* selected, uint64_t* high, int flags);
+
 /* 64-bit positional popcount in this library's convention: out[16] += bit counts (host array / device array) */
 int FLAGSTATS_hip_pospopcnt_u16_x64(const uint16_t* array, uint64_t n, uint64_t* out);
 int FLAGSTATS_hip_device_pospopcnt_u16(const uint16_t* d_array, uint64_t n, uint64_t* d_out, void* stream);

@@ -36,6 +36,9 @@ Only what the path needs:
                      the number of reads that pass and one high-bit mask per CSR segment, in one launch
 * ``segments_wide_where`` the mask or bitmap per segment of an int32 / int64 (or 16-bit) array or tensor in place: rows of
                      counters, the number selected and one high-bit mask of the selected elements per CSR segment, in one launch
+* ``segments_wide_filter_where`` the filter and the mask or bitmap together per segment of an int32 / int64 (or 16-bit) array or
+                     tensor in place: rows of counters, the number of reads that pass AND are selected and one high-bit mask of
+                     the selected elements per CSR segment, in one launch
 * ``dist``          shard + single all-reduce for multi-GPU runs
 
 The hot path has no CPU fallback: importing the compute entry points without the
@@ -86,6 +89,12 @@ from .segments_filter_where import (  # noqa: F401
     counters_segments_filter_where,
     flagstats_segments_filter_where,
 )
+from .segments_wide_filter_where import (  # noqa: F401
+    count_segments_device_ptr_ints_filter_where,
+    count_segments_torch_ints_filter_where,
+    counters_segments_ints_filter_where,
+    flagstats_segments_ints_filter_where,
+)
 from .segments_wide_where import (  # noqa: F401
     count_segments_device_ptr_ints_where,
     count_segments_torch_ints_where,
@@ -128,4 +137,6 @@ __all__ = ["flagstats", "flagstats_x64", "SAM_FLAG_NAMES", "flagstats_segments",
            "flagstats_filter_where", "count_device_ptr_filter_where", "count_torch_filter_where",
            "counters_segments_filter_where", "flagstats_segments_filter_where", "count_segments_device_ptr_filter_where",
            "count_segments_torch_filter_where", "counters_ints_filter_where", "flagstats_ints_filter_where",
-           "count_device_ptr_ints_filter_where", "count_torch_ints_filter_where"]
+           "count_device_ptr_ints_filter_where", "count_torch_ints_filter_where", "counters_segments_ints_filter_where",
+           "flagstats_segments_ints_filter_where", "count_segments_device_ptr_ints_filter_where",
+           "count_segments_torch_ints_filter_where"]

@@ -113,6 +113,21 @@ SIGNATURES = {
     "FLAGSTATS_hip_wide_x64_filter_where": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
                                                            ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
                                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    # array, n, elem_bytes, offsets, nseg, require, exclude, mapq, min_mapq, sel, sel_offset, sel_bits, out, selected, high, flags
+    "FLAGSTATS_hip_device_wide_segments_filter_where": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p,
+                                                                       ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                                                       ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                                       ctypes.c_void_p]),
+    "FLAGSTATS_hip_device_wide_segments_filter_where_sync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p,
+                                                                            ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                                                            ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                                                            ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                                            ctypes.c_void_p, ctypes.c_int]),
+    "FLAGSTATS_hip_wide_x64_segments_filter_where": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p,
+                                                                    ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                                                    ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
     "FLAGSTATS_hip_device_u16_segments_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                                                 ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
                                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
@@ -256,7 +271,7 @@ SIGNATURES = {
 }
 
 # internal launchers the tests and tests/perf drive directly (csrc/flagstat_wide.h, csrc/flagstat_where.h, csrc/flagstat_filter.h,
-# csrc/flagstat_segments_filter.h, csrc/flagstat_wide_filter.h, csrc/flagstat_segments_wide.h, csrc/flagstat_segments_wide_filter.h, csrc/flagstat_segments_where.h, csrc/flagstat_wide_where.h, csrc/flagstat_segments_wide_where.h, csrc/flagstat_filter_where.h, csrc/flagstat_segments_filter_where.h, csrc/flagstat_wide_filter_where.h); not part of the public headers, so kept apart from SIGNATURES, which mirrors those
+# csrc/flagstat_segments_filter.h, csrc/flagstat_wide_filter.h, csrc/flagstat_segments_wide.h, csrc/flagstat_segments_wide_filter.h, csrc/flagstat_segments_where.h, csrc/flagstat_wide_where.h, csrc/flagstat_segments_wide_where.h, csrc/flagstat_filter_where.h, csrc/flagstat_segments_filter_where.h, csrc/flagstat_wide_filter_where.h, csrc/flagstat_segments_wide_filter_where.h); not part of the public headers, so kept apart from SIGNATURES, which mirrors those
 INTERNAL_SIGNATURES = {
     "fsk_launch_wide": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                        ctypes.c_uint32, ctypes.c_void_p]),
@@ -304,6 +319,13 @@ INTERNAL_SIGNATURES = {
                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p]),
     "fsk_segments_wide_where_geometry": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_int,
                                                         ctypes.c_uint32, _U64P]),
+    # chunk, elem_bytes, mapq, sel, sel_offset, sel_bits, base, m, offsets, nseg, require, exclude, min_mapq, out, selected, high,
+    # mode, grid, stream
+    "fsk_launch_segments_wide_masked_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                              ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
+                                                              ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                                              ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                              ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p]),
 }
 
 _lib = None
