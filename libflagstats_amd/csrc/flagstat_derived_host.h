@@ -1,9 +1,12 @@
-// flagstat_derived_host.h -- internal: the host code that the kernels derived from K1 share (flagstat_wide.hip, flagstat_where.hip,
-// flagstat_filter.hip, flagstat_wide_filter.hip): the launcher's step split and store-form memset, the device row of a synchronous
-// call (32 counters and one trailing word, or two: kRowWords / kRowWords2), and the bodies of the three entry forms -- on the caller's stream, synchronous over device memory, chunked over host memory.  What
-// differs between the kernels arrives as arguments and callables: the names of their pointers, the text of their refusals, how
-// a chunk's inputs are copied and launched.  A HIP call that a callable makes goes through FS_HIP_TRY there, so the text of its
-// failure names the caller's own expression.
+// flagstat_derived_host.h -- internal: the host code that the kernels derived from K1 share.  All fifteen derived units use it:
+// the seven flat ones (flagstat_{wide,where,filter,filter_where,wide_filter,wide_where,wide_filter_where}.hip) directly, the
+// eight segmented ones (flagstat_segments*.hip) through flagstat_segments_shared.h.  It holds the launcher's step split and
+// store-form memset, the rules of an entry's arguments with the text of their refusals (one function per rule; a unit's *_args
+// composes them in its own order), a call's inputs table, the device row of a synchronous call (32 counters and one trailing
+// word, or two: kRowWords / kRowWords2), and the bodies of the three entry forms of the flat units -- on the caller's stream,
+// synchronous over device memory, chunked over host memory.  What differs between the kernels arrives as arguments and
+// callables: the hints of their refusals, how a chunk's inputs are copied and launched.  A HIP call that a callable makes goes
+// through FS_HIP_TRY there, so the text of its failure names the caller's own expression.
 // (Product library only: the entries check allocation extents, which the host-stub build does not have.)
 #ifndef FLAGSTAT_DERIVED_HOST_H_
 #define FLAGSTAT_DERIVED_HOST_H_
@@ -17,6 +20,7 @@
 
 #include "flagstat_engine.h"
 #include "flagstat_kernels.h"
+#include "flagstat_where.h"
 
 namespace fsdrv {
 
@@ -146,6 +150,106 @@ inline void store_nothing(uint64_t* out, uint64_t* word, uint64_t* word2, int fl
     if ((flags & 1) && word2) *word2 = 0;
 }
 
+// ------------------------------------------------------------------ argument rules
+// What an entry refuses before it touches the GPU, one function per rule and each the only home of its text.  A unit's *_args is
+// refused(rule || rule || ...) in that unit's order: the first broken rule is the one reported and no later one is asked.  The
+// array's rules are two functions because the MAPQ and selection pointers are asked for between them.
+using fsint::fail_text;
+
+// the return value of a unit's *_args: fail_text's -1 when some rule of the chain refused
+inline int refused(bool any) { return any ? -1 : 0; }
+
+// `u16_hint`: the unit's own text for elem_bytes == 2, naming the 16-bit entries that take such an array
+inline int check_elem_bytes(int elem_bytes, const char* u16_hint)
+{
+    if (elem_bytes == 2) return fail_text(u16_hint);
+    if (elem_bytes != 4 && elem_bytes != 8) return fail_text("elem_bytes must be 4 or 8");
+    return 0;
+}
+
+inline int check_predicate(uint32_t require, uint32_t exclude, uint32_t min_mapq)
+{
+    if (require > 0xFFFFu) return fail_text("require must be a 16-bit FLAG mask (at most 0xFFFF)");
+    if (exclude > 0xFFFFu) return fail_text("exclude must be a 16-bit FLAG mask (at most 0xFFFF)");
+    if (min_mapq > 255u) return fail_text("min_mapq must be at most 255 (MAPQ is one byte)");
+    return 0;
+}
+
+inline int check_sel_bits(int sel_bits)
+{
+    if (sel_bits != 1 && sel_bits != 8) return fail_text("sel_bits must be 1 (an LSB-first bitmap) or 8 (one byte per element)");
+    return 0;
+}
+
+inline int check_flags(int flags)
+{
+    return (flags & ~3) ? fail_text("flags: bit 0 store, bit 1 superset; no other bits") : 0;
+}
+
+inline int check_array_given(const void* array, uint64_t n)
+{
+    return (n && !array) ? fail_text("NULL array with n > 0") : 0;
+}
+
+inline int check_mapq_given(const void* mapq, uint64_t n, uint32_t min_mapq)
+{
+    return (n && min_mapq && !mapq) ? fail_text("NULL mapq with min_mapq > 0 and n > 0") : 0;
+}
+
+// `text`: a unit's own wording where it names the entries that take no selection
+inline int check_sel_given(const void* sel, uint64_t n, const char* text = "NULL selection with n > 0")
+{
+    return (n && !sel) ? fail_text(text) : 0;
+}
+
+// an array of elements of W bytes (2: the uint16 units, in their words; 4 or 8) is aligned
+inline int check_array_aligned(const void* array, int W)
+{
+    if ((reinterpret_cast<uintptr_t>(array) & static_cast<uintptr_t>(W - 1)) == 0) return 0;
+    return fail_text(W == 2   ? "array must be 2-byte aligned"
+                     : W == 4 ? "array must be 4-byte aligned (elem_bytes 4)"
+                              : "array must be 8-byte aligned (elem_bytes 8)");
+}
+
+// it is aligned and its n * W bytes are a size
+inline int check_array_layout(const void* array, uint64_t n, int W)
+{
+    if (check_array_aligned(array, W)) return -1;
+    if (n > (~0ull - 64) / static_cast<uint64_t>(W)) return fail_text(W == 2 ? "n * 2 is not a size" : "n * elem_bytes is not a size");
+    return 0;
+}
+
+inline int check_sel_range(uint64_t sel_offset, uint64_t n)
+{
+    return sel_offset > ~0ull - 64 - n ? fail_text("sel_offset + n is not an index") : 0;
+}
+
+// the counters of a flat entry: needed whenever something is written
+inline int check_counters(const void* out, uint64_t n, int flags)
+{
+    return (!out && (n || (flags & 1))) ? fail_text("NULL counters") : 0;
+}
+
+// a wave's totals are uint32: the one thing the step split still refuses once a unit's *_args has passed
+inline int fail_wave_totals()
+{
+    return fail_text("n is too large for this grid: a wave's uint32 totals could overflow (split the array)");
+}
+
+inline int step_fits(const void* array, uint64_t n, int elem_bytes, uint32_t grid)
+{
+    uint64_t geo[6];
+    return step_split(reinterpret_cast<uintptr_t>(array), n, elem_bytes, grid, geo) != hipSuccess ? fail_wave_totals() : 0;
+}
+
+// the bytes of d_sel a call over the whole array needs, from d_sel itself on (n > 0)
+inline uint64_t sel_bytes(uint64_t n, uint64_t sel_offset, int sel_bits)
+{
+    uint64_t first = 0, bytes = 0;
+    where_extent(n, sel_offset, sel_bits, &first, &bytes);
+    return first + bytes;
+}
+
 // an input array of a call: its pointer, the name the refusals use for it, the bytes the call reads from it on
 struct Input {
     const void* p;
@@ -158,6 +262,24 @@ struct DeviceWord {
     const void* p;
     const char* name;
     const char* why;
+};
+
+// a call's inputs in the order its refusals name them: what the unit puts in front (the segmented device entries: the offsets),
+// then the columns
+struct Inputs {
+    Input in[4];
+    int count = 0;
+    void add(const void* p, const char* name, uint64_t bytes) { in[count++] = Input{p, name, bytes}; }
+    // the columns of a call over n elements of W bytes: the array, the selection (sel_bits 0: the unit has none) up to the byte
+    // that holds the last element's bit or byte, the MAPQ column (last: it is an input only when min_mapq > 0).  n == 0: none.
+    void add_columns(const void* d_array, uint64_t n, uint64_t W, const void* d_sel, uint64_t sel_offset, int sel_bits,
+                     const void* d_mapq, uint32_t min_mapq)
+    {
+        if (n == 0) return;
+        add(d_array, "d_array", n * W);
+        if (sel_bits) add(d_sel, "d_sel", sel_bytes(n, sel_offset, sel_bits));
+        if (min_mapq) add(d_mapq, "d_mapq", n);
+    }
 };
 
 inline int fail_devices(const char* a, const char* b)

@@ -227,28 +227,12 @@ namespace {
 int filter_args(const uint16_t* array, uint64_t n, uint32_t require, uint32_t exclude, const uint8_t* mapq, uint32_t min_mapq,
                 const void* out, int flags)
 {
-    if (require > 0xFFFFu) return fail_text("require must be a 16-bit FLAG mask (at most 0xFFFF)");
-    if (exclude > 0xFFFFu) return fail_text("exclude must be a 16-bit FLAG mask (at most 0xFFFF)");
-    if (min_mapq > 255u) return fail_text("min_mapq must be at most 255 (MAPQ is one byte)");
-    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
-    if (n && !array) return fail_text("NULL array with n > 0");
-    if (n && min_mapq && !mapq) return fail_text("NULL mapq with min_mapq > 0 and n > 0");
-    if (reinterpret_cast<uintptr_t>(array) & 1u) return fail_text("array must be 2-byte aligned");
-    if (n > (~0ull - 64) / 2) return fail_text("n * 2 is not a size");
-    if (!out && (n || (flags & 1))) return fail_text("NULL counters");
-    return 0;
+    using namespace fsdrv;
+    return refused(check_predicate(require, exclude, min_mapq) || check_flags(flags) || check_array_given(array, n) ||
+                   check_mapq_given(mapq, n, min_mapq) || check_array_layout(array, n, 2) || check_counters(out, n, flags));
 }
 
 constexpr const char* kFilterAlloc = "hipMalloc(filter counters)";
-
-// a wave's totals are uint32: the one thing the step split still refuses once filter_args has passed
-int filter_fits(const uint16_t* array, uint64_t n, uint32_t grid)
-{
-    uint64_t geo[6];
-    if (fsdrv::step_split(reinterpret_cast<uintptr_t>(array), n, 2, grid, geo) != hipSuccess)
-        return fail_text("n is too large for this grid: a wave's uint32 totals could overflow (split the array)");
-    return 0;
-}
 
 }  // namespace
 
@@ -262,14 +246,14 @@ int FLAGSTATS_hip_device_u16_filter(const uint16_t* d_array, uint64_t n, uint32_
     if (rc) return rc;
     if (n == 0 && !(flags & 1)) return 0;
     const fsdrv::DeviceWord word{d_selected, "d_selected", "the count is added with a device atomic"};
-    const fsdrv::Input in[] = {{d_array, "d_array", n * 2}, {d_mapq, "d_mapq", n}};
-    const int inputs = n ? (min_mapq ? 2 : 1) : 0;
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, 2, nullptr, 0, 0, d_mapq, min_mapq);
     fsdrv::DeviceCall call;
-    if ((rc = call.open(d_out, word, in, inputs, stream))) return rc;
+    if ((rc = call.open(d_out, word, in.in, in.count, stream))) return rc;
     Engine* e = call.e;
     hipStream_t s = call.s;
-    if ((rc = filter_fits(d_array, n, fsint::grid_for(*e)))) return rc;
-    if ((rc = fsdrv::check_extents(d_out, word, in, inputs))) return rc;
+    if ((rc = fsdrv::step_fits(d_array, n, 2, fsint::grid_for(*e)))) return rc;
+    if ((rc = fsdrv::check_extents(d_out, word, in.in, in.count))) return rc;
     FS_HIP_TRY(fsk_launch_filter(d_array, n, require, exclude, d_mapq, min_mapq, d_out, d_selected, flags & 3, fsint::grid_for(*e), s));
     return 0;
 }
@@ -284,10 +268,11 @@ int FLAGSTATS_hip_device_u16_filter_sync(const uint16_t* d_array, uint64_t n, ui
         fsdrv::store_nothing(out, selected, flags);
         return 0;
     }
-    const fsdrv::Input in[] = {{d_array, "d_array", n * 2}, {d_mapq, "d_mapq", n}};
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, 2, nullptr, 0, 0, d_mapq, min_mapq);
     return fsdrv::sync_call(
-        in, min_mapq ? 2 : 1, kFilterAlloc, out, selected, flags, fsdrv::kWordAdd,
-        [&](Engine& e) { return filter_fits(d_array, n, fsint::grid_for(e)); },
+        in.in, in.count, kFilterAlloc, out, selected, flags, fsdrv::kWordAdd,
+        [&](Engine& e) { return fsdrv::step_fits(d_array, n, 2, fsint::grid_for(e)); },
         [&](Engine& e, fsdrv::Row& row, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_filter(d_array, n, require, exclude, d_mapq, min_mapq, row.d, row.d + 32, 1 | (flags & 2), fsint::grid_for(e), s));
             return 0;
@@ -311,7 +296,7 @@ int FLAGSTATS_hip_u16_x64_filter(const uint16_t* array, uint64_t n, uint32_t req
     const int mode = flags & 2;
     return fsdrv::host_call(
         n, chunk, cap + (mapq_cap + 1) / 2, kFilterAlloc, out, selected, flags, fsdrv::kWordAdd,
-        [&](Engine& e) { return filter_fits(nullptr, cap, fsint::grid_for(e)); },
+        [&](Engine& e) { return fsdrv::step_fits(nullptr, cap, 2, fsint::grid_for(e)); },
         [&](Engine& e, fsdrv::Row& row, int sl, uint64_t pos, uint64_t c) {
             const uint32_t grid = fsint::grid_for(e);
             uint8_t* d_mapq = reinterpret_cast<uint8_t*>(e.stage[sl] + cap);

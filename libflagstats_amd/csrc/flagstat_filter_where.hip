@@ -270,44 +270,13 @@ namespace {
 int filter_where_args(const uint16_t* array, uint64_t n, uint32_t require, uint32_t exclude, const uint8_t* mapq, uint32_t min_mapq,
                       const void* sel, uint64_t sel_offset, int sel_bits, const void* out, int flags)
 {
-    if (require > 0xFFFFu) return fail_text("require must be a 16-bit FLAG mask (at most 0xFFFF)");
-    if (exclude > 0xFFFFu) return fail_text("exclude must be a 16-bit FLAG mask (at most 0xFFFF)");
-    if (min_mapq > 255u) return fail_text("min_mapq must be at most 255 (MAPQ is one byte)");
-    if (sel_bits != 1 && sel_bits != 8) return fail_text("sel_bits must be 1 (an LSB-first bitmap) or 8 (one byte per element)");
-    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
-    if (n && !array) return fail_text("NULL array with n > 0");
-    if (n && min_mapq && !mapq) return fail_text("NULL mapq with min_mapq > 0 and n > 0");
-    if (n && !sel) return fail_text("NULL selection with n > 0");
-    if (reinterpret_cast<uintptr_t>(array) & 1u) return fail_text("array must be 2-byte aligned");
-    if (n > (~0ull - 64) / 2) return fail_text("n * 2 is not a size");
-    if (sel_offset > ~0ull - 64 - n) return fail_text("sel_offset + n is not an index");
-    if (!out && (n || (flags & 1))) return fail_text("NULL counters");
-    return 0;
+    using namespace fsdrv;
+    return refused(check_predicate(require, exclude, min_mapq) || check_sel_bits(sel_bits) || check_flags(flags) ||
+                   check_array_given(array, n) || check_mapq_given(mapq, n, min_mapq) || check_sel_given(sel, n) ||
+                   check_array_layout(array, n, 2) || check_sel_range(sel_offset, n) || check_counters(out, n, flags));
 }
 
 constexpr const char* kFilterWhereAlloc = "hipMalloc(filter_where counters)";
-
-// a wave's totals are uint32: the one thing the step split still refuses once filter_where_args has passed
-int filter_where_fits(const uint16_t* array, uint64_t n, uint32_t grid)
-{
-    uint64_t geo[6];
-    if (fsdrv::step_split(reinterpret_cast<uintptr_t>(array), n, 2, grid, geo) != hipSuccess)
-        return fail_text("n is too large for this grid: a wave's uint32 totals could overflow (split the array)");
-    return 0;
-}
-
-// the array, the selection and the MAPQ column (last: it is an input only when min_mapq > 0) as a call's inputs (n > 0)
-struct FilterWhereInputs {
-    fsdrv::Input in[3];
-    FilterWhereInputs(const uint16_t* d_array, uint64_t n, const uint8_t* d_mapq, const void* d_sel, uint64_t sel_offset, int sel_bits)
-    {
-        uint64_t first = 0, bytes = 0;
-        if (n) where_extent(n, sel_offset, sel_bits, &first, &bytes);
-        in[0] = fsdrv::Input{d_array, "d_array", n * 2};
-        in[1] = fsdrv::Input{d_sel, "d_sel", first + bytes};
-        in[2] = fsdrv::Input{d_mapq, "d_mapq", n};
-    }
-};
 
 }  // namespace
 
@@ -322,14 +291,14 @@ int FLAGSTATS_hip_device_u16_filter_where(const uint16_t* d_array, uint64_t n, u
     if (rc) return rc;
     if (n == 0 && !(flags & 1)) return 0;
     const fsdrv::DeviceWord word{d_selected, "d_selected", "the count is added with a device atomic"};
-    const FilterWhereInputs w(d_array, n, d_mapq, d_sel, sel_offset, sel_bits);
-    const int inputs = n ? (min_mapq ? 3 : 2) : 0;
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, 2, d_sel, sel_offset, sel_bits, d_mapq, min_mapq);
     fsdrv::DeviceCall call;
-    if ((rc = call.open(d_out, word, w.in, inputs, stream))) return rc;
+    if ((rc = call.open(d_out, word, in.in, in.count, stream))) return rc;
     Engine* e = call.e;
     hipStream_t s = call.s;
-    if ((rc = filter_where_fits(d_array, n, fsint::grid_for(*e)))) return rc;
-    if ((rc = fsdrv::check_extents(d_out, word, w.in, inputs))) return rc;
+    if ((rc = fsdrv::step_fits(d_array, n, 2, fsint::grid_for(*e)))) return rc;
+    if ((rc = fsdrv::check_extents(d_out, word, in.in, in.count))) return rc;
     FS_HIP_TRY(fsk_launch_filter_where(d_array, n, require, exclude, d_mapq, min_mapq, d_sel, sel_offset, sel_bits, d_out, d_selected,
                                        flags & 3, fsint::grid_for(*e), s));
     return 0;
@@ -346,10 +315,11 @@ int FLAGSTATS_hip_device_u16_filter_where_sync(const uint16_t* d_array, uint64_t
         fsdrv::store_nothing(out, selected, flags);
         return 0;
     }
-    const FilterWhereInputs w(d_array, n, d_mapq, d_sel, sel_offset, sel_bits);
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, 2, d_sel, sel_offset, sel_bits, d_mapq, min_mapq);
     return fsdrv::sync_call(
-        w.in, min_mapq ? 3 : 2, kFilterWhereAlloc, out, selected, flags, fsdrv::kWordAdd,
-        [&](Engine& e) { return filter_where_fits(d_array, n, fsint::grid_for(e)); },
+        in.in, in.count, kFilterWhereAlloc, out, selected, flags, fsdrv::kWordAdd,
+        [&](Engine& e) { return fsdrv::step_fits(d_array, n, 2, fsint::grid_for(e)); },
         [&](Engine& e, fsdrv::Row& row, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_filter_where(d_array, n, require, exclude, d_mapq, min_mapq, d_sel, sel_offset, sel_bits, row.d, row.d + 32,
                                                1 | (flags & 2), fsint::grid_for(e), s));
@@ -379,7 +349,7 @@ int FLAGSTATS_hip_u16_x64_filter_where(const uint16_t* array, uint64_t n, uint32
     const uint8_t* sel_src = static_cast<const uint8_t*>(sel);
     return fsdrv::host_call(
         n, chunk, cap + mapq_slot + (sel_cap + 1) / 2, kFilterWhereAlloc, out, selected, flags, fsdrv::kWordAdd,
-        [&](Engine& e) { return filter_where_fits(nullptr, cap, fsint::grid_for(e)); },
+        [&](Engine& e) { return fsdrv::step_fits(nullptr, cap, 2, fsint::grid_for(e)); },
         [&](Engine& e, fsdrv::Row& row, int sl, uint64_t pos, uint64_t c) {
             const uint32_t grid = fsint::grid_for(e);
             uint64_t first, bytes;

@@ -179,14 +179,16 @@ int FLAGSTATS_hip_device_u16_segments(const uint16_t* d_array, uint64_t n, const
                                       int flags, void* stream)
 {
     FS_ENTRY();
-    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
+    if (fsdrv::check_flags(flags)) return -1;
     if (nseg == 0) return 0;
-    if (!d_offsets || !d_out) return fail_text("NULL d_offsets or d_out with nseg > 0");
-    if (n && !d_array) return fail_text("NULL array with n > 0");
+    // this entry asks for the array before it looks at nseg, and words the latter its own way
+    if (!d_offsets || !d_out) return fail_text(fsseg::kNullDevice);
+    if (fsdrv::check_array_given(d_array, n)) return -1;
     if (nseg > fsseg::kMaxSegments) return fail_text("nseg is too large for its counters to be a size");
-    if (reinterpret_cast<uintptr_t>(d_array) & 1u) return fail_text("array must be 2-byte aligned");
-    const fsdrv::Input in[] = {{d_offsets, "d_offsets", (nseg + 1) * sizeof(uint64_t)}, {d_array, "d_array", n * sizeof(uint16_t)}};
-    return fsseg::device_call(d_out, nullptr, 0, in, n ? 2 : 1, nseg, stream, [](uint32_t) { return 0; },
+    if (fsdrv::check_array_aligned(d_array, 2)) return -1;
+    fsdrv::Inputs in = fsseg::offsets_input(d_offsets, nseg);
+    in.add_columns(d_array, n, 2, nullptr, 0, 0, nullptr, 0);
+    return fsseg::device_call(d_out, nullptr, 0, in.in, in.count, nseg, stream, [](uint32_t) { return 0; },
                               [&](uint32_t grid, hipStream_t s) {
                                   FS_HIP_TRY(fsk_launch_segments(d_array, 0, n, d_offsets, nseg, d_out, flags & 3, grid, s));
                                   return 0;
@@ -197,15 +199,15 @@ int FLAGSTATS_hip_device_u16_segments_sync(const uint16_t* d_array, uint64_t n, 
                                            int flags)
 {
     FS_ENTRY();
-    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
+    if (fsdrv::check_flags(flags)) return -1;
     if (nseg == 0) return 0;
-    int rc = fsseg::host_args(offsets, nseg, out);
-    if (rc) return rc;
-    if (n && !d_array) return fail_text("NULL array with n > 0");
-    if (reinterpret_cast<uintptr_t>(d_array) & 1u) return fail_text("array must be 2-byte aligned");
-    const fsdrv::Input in[] = {{d_array, "d_array", n * sizeof(uint16_t)}};
+    if (fsseg::check_segments(offsets, out, nseg, fsseg::kNullHost, fsseg::kMaxSegments) || fsdrv::check_array_given(d_array, n) ||
+        fsdrv::check_array_aligned(d_array, 2))
+        return -1;
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, 2, nullptr, 0, 0, nullptr, 0);
     return fsseg::sync_call(
-        in, n ? 1 : 0, n, offsets, nseg, 32, [](uint32_t) { return 0; },
+        in.in, in.count, n, offsets, nseg, 32, [](uint32_t) { return 0; },
         [&](fsseg::SegBuffers& buf, uint32_t grid, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_segments(d_array, 0, n, buf.off, nseg, buf.cnt, 1 | (flags & 2), grid, s));
             return 0;
@@ -216,11 +218,9 @@ int FLAGSTATS_hip_device_u16_segments_sync(const uint16_t* d_array, uint64_t n, 
 int FLAGSTATS_hip_u16_x64_segments(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint64_t nseg, uint64_t* out, int flags)
 {
     FS_ENTRY();
-    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
+    if (fsdrv::check_flags(flags)) return -1;
     if (nseg == 0) return 0;
-    int rc = fsseg::host_args(offsets, nseg, out);
-    if (rc) return rc;
-    if (n && !array) return fail_text("NULL array with n > 0");
+    if (fsseg::check_segments(offsets, out, nseg, fsseg::kNullHost, fsseg::kMaxSegments) || fsdrv::check_array_given(array, n)) return -1;
     const int mode = flags & 2;
     return fsseg::host_call(
         n, offsets, nseg, 32, fsdrv::chunk_flags(), [&] { return offsets[nseg]; }, [](uint64_t cap) { return cap; },

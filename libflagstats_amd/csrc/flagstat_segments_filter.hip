@@ -299,18 +299,11 @@ namespace {
 int segf_args(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint64_t nseg, uint32_t require, uint32_t exclude,
               const uint8_t* mapq, uint32_t min_mapq, const void* out, int flags, const char* null_text)
 {
-    if (require > 0xFFFFu) return fail_text("require must be a 16-bit FLAG mask (at most 0xFFFF)");
-    if (exclude > 0xFFFFu) return fail_text("exclude must be a 16-bit FLAG mask (at most 0xFFFF)");
-    if (min_mapq > 255u) return fail_text("min_mapq must be at most 255 (MAPQ is one byte)");
-    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
+    using namespace fsdrv;
+    if (check_predicate(require, exclude, min_mapq) || check_flags(flags)) return -1;
     if (nseg == 0) return 0;
-    if (!offsets || !out) return fail_text(null_text);
-    if (nseg > fsseg::kMaxSegments / 2) return fail_text("nseg is too large: its counters cannot be allocated");   // 33 words each
-    if (n && !array) return fail_text("NULL array with n > 0");
-    if (n && min_mapq && !mapq) return fail_text("NULL mapq with min_mapq > 0 and n > 0");
-    if (reinterpret_cast<uintptr_t>(array) & 1u) return fail_text("array must be 2-byte aligned");
-    if (n > (~0ull - 64) / 2) return fail_text("n * 2 is not a size");
-    return 0;
+    return refused(fsseg::check_segments(offsets, out, nseg, null_text, fsseg::kMaxSegments / 2) || check_array_given(array, n) ||
+                   check_mapq_given(mapq, n, min_mapq) || check_array_layout(array, n, 2));
 }
 
 }  // namespace
@@ -322,12 +315,13 @@ int FLAGSTATS_hip_device_u16_segments_filter(const uint16_t* d_array, uint64_t n
                                              uint64_t* d_out, uint64_t* d_selected, int flags, void* stream)
 {
     FS_ENTRY();
-    int rc = segf_args(d_array, n, d_offsets, nseg, require, exclude, d_mapq, min_mapq, d_out, flags, "NULL d_offsets or d_out with nseg > 0");
+    int rc = segf_args(d_array, n, d_offsets, nseg, require, exclude, d_mapq, min_mapq, d_out, flags, fsseg::kNullDevice);
     if (rc || nseg == 0) return rc;
     const fsdrv::DeviceWord word{d_selected, "d_selected", "the counts are added with device atomics"};
-    const fsdrv::Input in[] = {{d_offsets, "d_offsets", (nseg + 1) * sizeof(uint64_t)}, {d_array, "d_array", n * 2}, {d_mapq, "d_mapq", n}};
+    fsdrv::Inputs in = fsseg::offsets_input(d_offsets, nseg);
+    in.add_columns(d_array, n, 2, nullptr, 0, 0, d_mapq, min_mapq);
     return fsseg::device_call(
-        d_out, &word, 1, in, n ? (min_mapq ? 3 : 2) : 1, nseg, stream,
+        d_out, &word, 1, in.in, in.count, nseg, stream,
         [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWaveFlags, grid); },
         [&](uint32_t grid, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_segments_filter(d_array, d_mapq, 0, n, d_offsets, nseg, require, exclude, min_mapq, d_out, d_selected,
@@ -341,11 +335,12 @@ int FLAGSTATS_hip_device_u16_segments_filter_sync(const uint16_t* d_array, uint6
                                                   uint64_t* out, uint64_t* selected, int flags)
 {
     FS_ENTRY();
-    int rc = segf_args(d_array, n, offsets, nseg, require, exclude, d_mapq, min_mapq, out, flags, "NULL offsets or out with nseg > 0");
+    int rc = segf_args(d_array, n, offsets, nseg, require, exclude, d_mapq, min_mapq, out, flags, fsseg::kNullHost);
     if (rc || nseg == 0) return rc;
-    const fsdrv::Input in[] = {{d_array, "d_array", n * sizeof(uint16_t)}, {d_mapq, "d_mapq", n}};
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, 2, nullptr, 0, 0, d_mapq, min_mapq);
     return fsseg::sync_call(
-        in, n ? (min_mapq ? 2 : 1) : 0, n, offsets, nseg, 33,
+        in.in, in.count, n, offsets, nseg, 33,
         [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWaveFlags, grid); },
         [&](fsseg::SegBuffers& buf, uint32_t grid, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_segments_filter(d_array, d_mapq, 0, n, buf.off, nseg, require, exclude, min_mapq, buf.cnt,
@@ -360,7 +355,7 @@ int FLAGSTATS_hip_u16_x64_segments_filter(const uint16_t* array, uint64_t n, con
                                           int flags)
 {
     FS_ENTRY();
-    int rc = segf_args(array, n, offsets, nseg, require, exclude, mapq, min_mapq, out, flags, "NULL offsets or out with nseg > 0");
+    int rc = segf_args(array, n, offsets, nseg, require, exclude, mapq, min_mapq, out, flags, fsseg::kNullHost);
     if (rc || nseg == 0) return rc;
     // a chunk's slice of the MAPQ column rides in the same staging buffer, behind the flags.  An overlapping pair selects
     // nothing: nothing is moved.

@@ -311,29 +311,12 @@ int segfw_args(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint6
                const uint8_t* mapq, uint32_t min_mapq, const void* sel, uint64_t sel_offset, int sel_bits, const void* out, int flags,
                const char* null_text)
 {
-    if (require > 0xFFFFu) return fail_text("require must be a 16-bit FLAG mask (at most 0xFFFF)");
-    if (exclude > 0xFFFFu) return fail_text("exclude must be a 16-bit FLAG mask (at most 0xFFFF)");
-    if (min_mapq > 255u) return fail_text("min_mapq must be at most 255 (MAPQ is one byte)");
-    if (sel_bits != 1 && sel_bits != 8) return fail_text("sel_bits must be 1 (an LSB-first bitmap) or 8 (one byte per element)");
-    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
+    using namespace fsdrv;
+    if (check_predicate(require, exclude, min_mapq) || check_sel_bits(sel_bits) || check_flags(flags)) return -1;
     if (nseg == 0) return 0;
-    if (!offsets || !out) return fail_text(null_text);
-    if (nseg > fsseg::kMaxSegments / 2) return fail_text("nseg is too large: its counters cannot be allocated");   // 33 words each
-    if (n && !array) return fail_text("NULL array with n > 0");
-    if (n && min_mapq && !mapq) return fail_text("NULL mapq with min_mapq > 0 and n > 0");
-    if (n && !sel) return fail_text("NULL selection with n > 0");
-    if (reinterpret_cast<uintptr_t>(array) & 1u) return fail_text("array must be 2-byte aligned");
-    if (n > (~0ull - 64) / 2) return fail_text("n * 2 is not a size");
-    if (sel_offset > ~0ull - 64 - n) return fail_text("sel_offset + n is not an index");
-    return 0;
-}
-
-// the bytes of d_sel a call over the whole array needs, from d_sel itself on (n > 0)
-uint64_t sel_bytes(uint64_t n, uint64_t sel_offset, int sel_bits)
-{
-    uint64_t first = 0, bytes = 0;
-    where_extent(n, sel_offset, sel_bits, &first, &bytes);
-    return first + bytes;
+    return refused(fsseg::check_segments(offsets, out, nseg, null_text, fsseg::kMaxSegments / 2) || check_array_given(array, n) ||
+                   check_mapq_given(mapq, n, min_mapq) || check_sel_given(sel, n) || check_array_layout(array, n, 2) ||
+                   check_sel_range(sel_offset, n));
 }
 
 }  // namespace
@@ -347,16 +330,13 @@ int FLAGSTATS_hip_device_u16_segments_filter_where(const uint16_t* d_array, uint
 {
     FS_ENTRY();
     int rc = segfw_args(d_array, n, d_offsets, nseg, require, exclude, d_mapq, min_mapq, d_sel, sel_offset, sel_bits, d_out, flags,
-                        "NULL d_offsets or d_out with nseg > 0");
+                        fsseg::kNullDevice);
     if (rc || nseg == 0) return rc;
     const fsdrv::DeviceWord word{d_selected, "d_selected", "the counts are added with device atomics"};
-    // the MAPQ column last: it is an input only when min_mapq > 0
-    const fsdrv::Input in[] = {{d_offsets, "d_offsets", (nseg + 1) * sizeof(uint64_t)},
-                               {d_array, "d_array", n * 2},
-                               {d_sel, "d_sel", n ? sel_bytes(n, sel_offset, sel_bits) : 0},
-                               {d_mapq, "d_mapq", n}};
+    fsdrv::Inputs in = fsseg::offsets_input(d_offsets, nseg);
+    in.add_columns(d_array, n, 2, d_sel, sel_offset, sel_bits, d_mapq, min_mapq);
     return fsseg::device_call(
-        d_out, &word, 1, in, n ? (min_mapq ? 4 : 3) : 1, nseg, stream,
+        d_out, &word, 1, in.in, in.count, nseg, stream,
         [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWaveFlags, grid); },
         [&](uint32_t grid, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_segments_filter_where(d_array, d_mapq, d_sel, sel_offset, sel_bits, 0, n, d_offsets, nseg, require, exclude,
@@ -372,13 +352,12 @@ int FLAGSTATS_hip_device_u16_segments_filter_where_sync(const uint16_t* d_array,
 {
     FS_ENTRY();
     int rc = segfw_args(d_array, n, offsets, nseg, require, exclude, d_mapq, min_mapq, d_sel, sel_offset, sel_bits, out, flags,
-                        "NULL offsets or out with nseg > 0");
+                        fsseg::kNullHost);
     if (rc || nseg == 0) return rc;
-    const fsdrv::Input in[] = {{d_array, "d_array", n * sizeof(uint16_t)},
-                               {d_sel, "d_sel", n ? sel_bytes(n, sel_offset, sel_bits) : 0},
-                               {d_mapq, "d_mapq", n}};
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, 2, d_sel, sel_offset, sel_bits, d_mapq, min_mapq);
     return fsseg::sync_call(
-        in, n ? (min_mapq ? 3 : 2) : 0, n, offsets, nseg, 33,
+        in.in, in.count, n, offsets, nseg, 33,
         [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWaveFlags, grid); },
         [&](fsseg::SegBuffers& buf, uint32_t grid, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_segments_filter_where(d_array, d_mapq, d_sel, sel_offset, sel_bits, 0, n, buf.off, nseg, require, exclude,
@@ -395,7 +374,7 @@ int FLAGSTATS_hip_u16_x64_segments_filter_where(const uint16_t* array, uint64_t 
 {
     FS_ENTRY();
     int rc = segfw_args(array, n, offsets, nseg, require, exclude, mapq, min_mapq, sel, sel_offset, sel_bits, out, flags,
-                        "NULL offsets or out with nseg > 0");
+                        fsseg::kNullHost);
     if (rc || nseg == 0) return rc;
     // a chunk's slices of the MAPQ column and of the selection ride in the same staging buffer, behind the flags: the column's
     // first, then the selection's -- a bitmap slice from the byte that holds the chunk's first bit (the launch then starts

@@ -1,10 +1,11 @@
-// flagstat_segments_shared.h -- internal: what the five segmented kernels share (flagstat_segments.hip, flagstat_segments_filter.hip,
-// flagstat_segments_wide.hip, flagstat_segments_wide_filter.hip, flagstat_segments_where.hip).
+// flagstat_segments_shared.h -- internal: what the eight segmented kernels share (flagstat_segments.hip and its derivations
+// flagstat_segments_{filter,where,filter_where,wide,wide_filter,wide_where,wide_filter_where}.hip).
 // Device code: the geometry of a wave's unit, the per-flag count of a vector, the clamped grid position of an offset, the search
 // and window over the offsets (SegWalk), the walk of a writer over the segments that intersect it (seg_walk<UE>: the kernels hand in
 // their chain run, their unit load, their piece count and their emission), the map from a wave's 21 totals to the 32 slots of a
-// row and the one emission (seg_emit<COUNT, MASK>).  Host code: launch_shape / wave_totals_fit / fits, the checks and buffers over
-// host offsets, and the bodies of the three entry forms (device_call, sync_call, host_call).
+// row and the one emission (seg_emit<COUNT, MASK>).  Host code: launch_shape / wave_totals_fit / fits, the segmented rule of an
+// entry's arguments (check_segments), the checks and buffers over host offsets, and the bodies of the three entry forms
+// (device_call, sync_call, host_call).
 // (Product library only: the entries check allocation extents, which the host-stub build does not have.)
 #ifndef FLAGSTAT_SEGMENTS_SHARED_H_
 #define FLAGSTAT_SEGMENTS_SHARED_H_
@@ -386,12 +387,19 @@ struct SegBuffers {
     }
 };
 
-inline int host_args(const uint64_t* offsets, uint64_t nseg, const void* out)
+// The segmented rule of an entry's arguments, asked once nseg > 0 (a unit's *_args returns 0 for nseg == 0 in front of it; the
+// other rules are flagstat_derived_host.h's): offsets and rows are given -- `null_text` names them as the entry does, d_offsets /
+// d_out on the caller's stream -- and the counters of nseg segments can be allocated: at most `max_nseg`, kMaxSegments for rows of
+// 32 words, half of it for rows with trailing words (33 or 34).
+inline int check_segments(const void* offsets, const void* out, uint64_t nseg, const char* null_text, uint64_t max_nseg)
 {
-    if (!offsets || !out) return fsint::fail_text("NULL offsets or out with nseg > 0");
-    if (nseg > kMaxSegments) return fsint::fail_text("nseg is too large: its counters cannot be allocated");
+    if (!offsets || !out) return fsint::fail_text(null_text);
+    if (nseg > max_nseg) return fsint::fail_text("nseg is too large: its counters cannot be allocated");
     return 0;
 }
+
+constexpr const char* kNullHost = "NULL offsets or out with nseg > 0";        // the entries that take host offsets
+constexpr const char* kNullDevice = "NULL d_offsets or d_out with nseg > 0";  // the entries on the caller's stream
 
 // host copy of the device rows: allocated without exceptions (none may cross the C boundary), before any GPU work is queued
 struct HostRows {
@@ -434,6 +442,14 @@ inline void apply_masks(uint64_t* high, const uint64_t* got, uint64_t nseg, int 
     for (uint64_t i = 0; i < nseg; ++i) high[i] = (flags & 1) ? got[i] : (high[i] | got[i]);
 }
 
+// rows, selected counts, then masks (34 words per segment) of a synchronous call into the caller's host words: rows and counts
+// stored or added, masks stored or ORed
+inline void apply_all(uint64_t* out, uint64_t* selected, uint64_t* high, const fsseg::HostRows& got, uint64_t nseg, int flags)
+{
+    apply_both(out, selected, got, nseg, flags);
+    apply_masks(high, got.p.get() + nseg * 33, nseg, flags);
+}
+
 // a wave's totals are uint32: every wave must own fewer than 2^32 elements (ue: elements per unit)
 inline bool wave_totals_fit(uint64_t nunits, uint32_t g, uint64_t ue)
 {
@@ -459,12 +475,18 @@ inline int fits(const void* array, uint64_t n, uint64_t ue, uint32_t grid)
     uint64_t lo0 = 0, nunits = 0;
     uint32_t g = 0;
     launch_shape(reinterpret_cast<uintptr_t>(array), n, ue, grid, &lo0, &nunits, &g);
-    if (!wave_totals_fit(nunits, g, ue))
-        return fsint::fail_text("n is too large for this grid: a wave's uint32 totals could overflow (split the array)");
-    return 0;
+    return wave_totals_fit(nunits, g, ue) ? 0 : fsdrv::fail_wave_totals();
 }
 
-// ------------------------------------------------------------------ the bodies of the three entry forms, for all five units
+// the inputs table of an entry on the caller's stream: the device offsets, in front of the columns the unit then adds
+inline fsdrv::Inputs offsets_input(const uint64_t* d_offsets, uint64_t nseg)
+{
+    fsdrv::Inputs in;
+    in.add(d_offsets, "d_offsets", (nseg + 1) * sizeof(uint64_t));
+    return in;
+}
+
+// ------------------------------------------------------------------ the bodies of the three entry forms, for all eight units
 // What differs between the units arrives as arguments and callables (the pattern of flagstat_derived_host.h): the unit's own
 // argument check runs in front; its trailing words (none, selected, high, or both), its inputs with the names its refusals use,
 // its fit check, its words per segment (32 / 33 / 34), how a chunk's extra column is staged, its launch and how its result is

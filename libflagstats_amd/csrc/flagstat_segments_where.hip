@@ -253,25 +253,11 @@ namespace {
 int segw_args(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint64_t nseg, const void* sel, uint64_t sel_offset, int sel_bits,
               const void* out, int flags, const char* null_text)
 {
-    if (sel_bits != 1 && sel_bits != 8) return fail_text("sel_bits must be 1 (an LSB-first bitmap) or 8 (one byte per element)");
-    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
+    using namespace fsdrv;
+    if (check_sel_bits(sel_bits) || check_flags(flags)) return -1;
     if (nseg == 0) return 0;
-    if (!offsets || !out) return fail_text(null_text);
-    if (nseg > fsseg::kMaxSegments / 2) return fail_text("nseg is too large: its counters cannot be allocated");   // 33 words each
-    if (n && !array) return fail_text("NULL array with n > 0");
-    if (n && !sel) return fail_text("NULL selection with n > 0");
-    if (reinterpret_cast<uintptr_t>(array) & 1u) return fail_text("array must be 2-byte aligned");
-    if (n > (~0ull - 64) / 2) return fail_text("n * 2 is not a size");
-    if (sel_offset > ~0ull - 64 - n) return fail_text("sel_offset + n is not an index");
-    return 0;
-}
-
-// the bytes of d_sel a call over the whole array needs, from d_sel itself on (n > 0)
-uint64_t sel_bytes(uint64_t n, uint64_t sel_offset, int sel_bits)
-{
-    uint64_t first = 0, bytes = 0;
-    where_extent(n, sel_offset, sel_bits, &first, &bytes);
-    return first + bytes;
+    return refused(fsseg::check_segments(offsets, out, nseg, null_text, fsseg::kMaxSegments / 2) || check_array_given(array, n) ||
+                   check_sel_given(sel, n) || check_array_layout(array, n, 2) || check_sel_range(sel_offset, n));
 }
 
 }  // namespace
@@ -283,14 +269,13 @@ int FLAGSTATS_hip_device_u16_segments_where(const uint16_t* d_array, uint64_t n,
                                             int flags, void* stream)
 {
     FS_ENTRY();
-    int rc = segw_args(d_array, n, d_offsets, nseg, d_sel, sel_offset, sel_bits, d_out, flags, "NULL d_offsets or d_out with nseg > 0");
+    int rc = segw_args(d_array, n, d_offsets, nseg, d_sel, sel_offset, sel_bits, d_out, flags, fsseg::kNullDevice);
     if (rc || nseg == 0) return rc;
     const fsdrv::DeviceWord word{d_selected, "d_selected", "the counts are added with device atomics"};
-    const fsdrv::Input in[] = {{d_offsets, "d_offsets", (nseg + 1) * sizeof(uint64_t)},
-                               {d_array, "d_array", n * 2},
-                               {d_sel, "d_sel", n ? sel_bytes(n, sel_offset, sel_bits) : 0}};
+    fsdrv::Inputs in = fsseg::offsets_input(d_offsets, nseg);
+    in.add_columns(d_array, n, 2, d_sel, sel_offset, sel_bits, nullptr, 0);
     return fsseg::device_call(
-        d_out, &word, 1, in, n ? 3 : 1, nseg, stream, [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWaveFlags, grid); },
+        d_out, &word, 1, in.in, in.count, nseg, stream, [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWaveFlags, grid); },
         [&](uint32_t grid, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_segments_where(d_array, d_sel, sel_offset, sel_bits, 0, n, d_offsets, nseg, d_out, d_selected, flags & 3,
                                                  grid, s));
@@ -303,11 +288,12 @@ int FLAGSTATS_hip_device_u16_segments_where_sync(const uint16_t* d_array, uint64
                                                  int flags)
 {
     FS_ENTRY();
-    int rc = segw_args(d_array, n, offsets, nseg, d_sel, sel_offset, sel_bits, out, flags, "NULL offsets or out with nseg > 0");
+    int rc = segw_args(d_array, n, offsets, nseg, d_sel, sel_offset, sel_bits, out, flags, fsseg::kNullHost);
     if (rc || nseg == 0) return rc;
-    const fsdrv::Input in[] = {{d_array, "d_array", n * sizeof(uint16_t)}, {d_sel, "d_sel", n ? sel_bytes(n, sel_offset, sel_bits) : 0}};
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, 2, d_sel, sel_offset, sel_bits, nullptr, 0);
     return fsseg::sync_call(
-        in, n ? 2 : 0, n, offsets, nseg, 33, [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWaveFlags, grid); },
+        in.in, in.count, n, offsets, nseg, 33, [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWaveFlags, grid); },
         [&](fsseg::SegBuffers& buf, uint32_t grid, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_segments_where(d_array, d_sel, sel_offset, sel_bits, 0, n, buf.off, nseg, buf.cnt, buf.cnt + nseg * 32,
                                                  1 | (flags & 2), grid, s));
@@ -320,7 +306,7 @@ int FLAGSTATS_hip_u16_x64_segments_where(const uint16_t* array, uint64_t n, cons
                                          uint64_t sel_offset, int sel_bits, uint64_t* out, uint64_t* selected, int flags)
 {
     FS_ENTRY();
-    int rc = segw_args(array, n, offsets, nseg, sel, sel_offset, sel_bits, out, flags, "NULL offsets or out with nseg > 0");
+    int rc = segw_args(array, n, offsets, nseg, sel, sel_offset, sel_bits, out, flags, fsseg::kNullHost);
     if (rc || nseg == 0) return rc;
     // a chunk's slice of the selection rides in the same staging buffer, behind the flags -- a bitmap slice from the byte that
     // holds the chunk's first bit (the launch then starts (sel_offset + pos) & 7 bits into it)

@@ -167,18 +167,14 @@ namespace {
 int segw_args(const void* array, uint64_t n, int elem_bytes, const uint64_t* offsets, uint64_t nseg, const void* out, int flags,
               const char* null_text)
 {
-    if (elem_bytes == 2)
-        return fail_text("elem_bytes 2: 16-bit arrays go to the u16 entries (FLAGSTATS_hip_u16_x64_segments, FLAGSTATS_hip_device_u16_segments)");
-    if (elem_bytes != 4 && elem_bytes != 8) return fail_text("elem_bytes must be 4 or 8");
-    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
+    using namespace fsdrv;
+    if (check_elem_bytes(elem_bytes, "elem_bytes 2: 16-bit arrays go to the u16 entries (FLAGSTATS_hip_u16_x64_segments, "
+                                     "FLAGSTATS_hip_device_u16_segments)") ||
+        check_flags(flags))
+        return -1;
     if (nseg == 0) return 0;
-    if (!offsets || !out) return fail_text(null_text);
-    if (nseg > fsseg::kMaxSegments / 2) return fail_text("nseg is too large: its counters cannot be allocated");   // 33 words each
-    if (n && !array) return fail_text("NULL array with n > 0");
-    if (reinterpret_cast<uintptr_t>(array) & static_cast<uintptr_t>(elem_bytes - 1))
-        return fail_text(elem_bytes == 4 ? "array must be 4-byte aligned (elem_bytes 4)" : "array must be 8-byte aligned (elem_bytes 8)");
-    if (n > (~0ull - 64) / static_cast<uint64_t>(elem_bytes)) return fail_text("n * elem_bytes is not a size");
-    return 0;
+    return refused(fsseg::check_segments(offsets, out, nseg, null_text, fsseg::kMaxSegments / 2) || check_array_given(array, n) ||
+                   check_array_layout(array, n, elem_bytes));
 }
 
 // rows, then masks, of a synchronous call into the caller's host words: rows stored or added, masks stored or ORed
@@ -196,13 +192,14 @@ int FLAGSTATS_hip_device_wide_segments(const void* d_array, uint64_t n, int elem
                                        uint64_t* d_out, uint64_t* d_high, int flags, void* stream)
 {
     FS_ENTRY();
-    int rc = segw_args(d_array, n, elem_bytes, d_offsets, nseg, d_out, flags, "NULL d_offsets or d_out with nseg > 0");
+    int rc = segw_args(d_array, n, elem_bytes, d_offsets, nseg, d_out, flags, fsseg::kNullDevice);
     if (rc || nseg == 0) return rc;
     const uint64_t W = static_cast<uint64_t>(elem_bytes);
     const fsdrv::DeviceWord word{d_high, "d_high", "the masks are ORed with device atomics"};
-    const fsdrv::Input in[] = {{d_offsets, "d_offsets", (nseg + 1) * sizeof(uint64_t)}, {d_array, "d_array", n * W}};
+    fsdrv::Inputs in = fsseg::offsets_input(d_offsets, nseg);
+    in.add_columns(d_array, n, W, nullptr, 0, 0, nullptr, 0);
     return fsseg::device_call(
-        d_out, &word, 1, in, n ? 2 : 1, nseg, stream,
+        d_out, &word, 1, in.in, in.count, nseg, stream,
         [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWideUnitBytes / W, grid); },
         [&](uint32_t grid, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_segments_wide(d_array, elem_bytes, 0, n, d_offsets, nseg, d_out, d_high, flags & 3, grid, s));
@@ -214,12 +211,13 @@ int FLAGSTATS_hip_device_wide_segments_sync(const void* d_array, uint64_t n, int
                                             uint64_t* out, uint64_t* high, int flags)
 {
     FS_ENTRY();
-    int rc = segw_args(d_array, n, elem_bytes, offsets, nseg, out, flags, "NULL offsets or out with nseg > 0");
+    int rc = segw_args(d_array, n, elem_bytes, offsets, nseg, out, flags, fsseg::kNullHost);
     if (rc || nseg == 0) return rc;
     const uint64_t W = static_cast<uint64_t>(elem_bytes);
-    const fsdrv::Input in[] = {{d_array, "d_array", n * W}};
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, W, nullptr, 0, 0, nullptr, 0);
     return fsseg::sync_call(
-        in, n ? 1 : 0, n, offsets, nseg, 33, [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWideUnitBytes / W, grid); },
+        in.in, in.count, n, offsets, nseg, 33, [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWideUnitBytes / W, grid); },
         [&](fsseg::SegBuffers& buf, uint32_t grid, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_segments_wide(d_array, elem_bytes, 0, n, buf.off, nseg, buf.cnt, buf.cnt + nseg * 32, 1 | (flags & 2), grid, s));
             return 0;
@@ -231,7 +229,7 @@ int FLAGSTATS_hip_wide_x64_segments(const void* array, uint64_t n, int elem_byte
                                     uint64_t* high, int flags)
 {
     FS_ENTRY();
-    int rc = segw_args(array, n, elem_bytes, offsets, nseg, out, flags, "NULL offsets or out with nseg > 0");
+    int rc = segw_args(array, n, elem_bytes, offsets, nseg, out, flags, fsseg::kNullHost);
     if (rc || nseg == 0) return rc;
     // the elements cross the bus as they are, in chunks of "chunk_flags" * 2 bytes (the wide host entry's); every chunk's launch
     // adds to the same device rows and ORs into the same device masks

@@ -331,31 +331,14 @@ namespace {
 int segwf_args(const void* array, uint64_t n, int elem_bytes, const uint64_t* offsets, uint64_t nseg, uint32_t require, uint32_t exclude,
                const uint8_t* mapq, uint32_t min_mapq, const void* out, int flags, const char* null_text)
 {
-    if (elem_bytes == 2)
-        return fail_text("elem_bytes 2: 16-bit arrays go to the u16 segmented filter entries (FLAGSTATS_hip_u16_x64_segments_filter, "
-                         "FLAGSTATS_hip_device_u16_segments_filter)");
-    if (elem_bytes != 4 && elem_bytes != 8) return fail_text("elem_bytes must be 4 or 8");
-    if (require > 0xFFFFu) return fail_text("require must be a 16-bit FLAG mask (at most 0xFFFF)");
-    if (exclude > 0xFFFFu) return fail_text("exclude must be a 16-bit FLAG mask (at most 0xFFFF)");
-    if (min_mapq > 255u) return fail_text("min_mapq must be at most 255 (MAPQ is one byte)");
-    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
+    using namespace fsdrv;
+    if (check_elem_bytes(elem_bytes, "elem_bytes 2: 16-bit arrays go to the u16 segmented filter entries "
+                                     "(FLAGSTATS_hip_u16_x64_segments_filter, FLAGSTATS_hip_device_u16_segments_filter)") ||
+        check_predicate(require, exclude, min_mapq) || check_flags(flags))
+        return -1;
     if (nseg == 0) return 0;
-    if (!offsets || !out) return fail_text(null_text);
-    if (nseg > fsseg::kMaxSegments / 2) return fail_text("nseg is too large: its counters cannot be allocated");   // 34 words each
-    if (n && !array) return fail_text("NULL array with n > 0");
-    if (n && min_mapq && !mapq) return fail_text("NULL mapq with min_mapq > 0 and n > 0");
-    if (reinterpret_cast<uintptr_t>(array) & static_cast<uintptr_t>(elem_bytes - 1))
-        return fail_text(elem_bytes == 4 ? "array must be 4-byte aligned (elem_bytes 4)" : "array must be 8-byte aligned (elem_bytes 8)");
-    if (n > (~0ull - 64) / static_cast<uint64_t>(elem_bytes)) return fail_text("n * elem_bytes is not a size");
-    return 0;
-}
-
-// rows, selected counts, then masks, of a synchronous call into the caller's host words: rows and counts stored or added, masks
-// stored or ORed
-void apply_all(uint64_t* out, uint64_t* selected, uint64_t* high, const fsseg::HostRows& got, uint64_t nseg, int flags)
-{
-    fsseg::apply_both(out, selected, got, nseg, flags);
-    fsseg::apply_masks(high, got.p.get() + nseg * 33, nseg, flags);
+    return refused(fsseg::check_segments(offsets, out, nseg, null_text, fsseg::kMaxSegments / 2) || check_array_given(array, n) ||
+                   check_mapq_given(mapq, n, min_mapq) || check_array_layout(array, n, elem_bytes));
 }
 
 }  // namespace
@@ -368,14 +351,15 @@ int FLAGSTATS_hip_device_wide_segments_filter(const void* d_array, uint64_t n, i
 {
     FS_ENTRY();
     int rc = segwf_args(d_array, n, elem_bytes, d_offsets, nseg, require, exclude, d_mapq, min_mapq, d_out, flags,
-                        "NULL d_offsets or d_out with nseg > 0");
+                        fsseg::kNullDevice);
     if (rc || nseg == 0) return rc;
     const uint64_t W = static_cast<uint64_t>(elem_bytes);
     const fsdrv::DeviceWord words[] = {{d_selected, "d_selected", "the counts are added with device atomics"},
                                        {d_high, "d_high", "the masks are ORed with device atomics"}};
-    const fsdrv::Input in[] = {{d_offsets, "d_offsets", (nseg + 1) * sizeof(uint64_t)}, {d_array, "d_array", n * W}, {d_mapq, "d_mapq", n}};
+    fsdrv::Inputs in = fsseg::offsets_input(d_offsets, nseg);
+    in.add_columns(d_array, n, W, nullptr, 0, 0, d_mapq, min_mapq);
     return fsseg::device_call(
-        d_out, words, 2, in, n ? (min_mapq ? 3 : 2) : 1, nseg, stream,
+        d_out, words, 2, in.in, in.count, nseg, stream,
         [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWideUnitBytes / W, grid); },
         [&](uint32_t grid, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_segments_wide_filter(d_array, elem_bytes, d_mapq, 0, n, d_offsets, nseg, require, exclude, min_mapq, d_out,
@@ -390,19 +374,20 @@ int FLAGSTATS_hip_device_wide_segments_filter_sync(const void* d_array, uint64_t
 {
     FS_ENTRY();
     int rc = segwf_args(d_array, n, elem_bytes, offsets, nseg, require, exclude, d_mapq, min_mapq, out, flags,
-                        "NULL offsets or out with nseg > 0");
+                        fsseg::kNullHost);
     if (rc || nseg == 0) return rc;
     const uint64_t W = static_cast<uint64_t>(elem_bytes);
-    const fsdrv::Input in[] = {{d_array, "d_array", n * W}, {d_mapq, "d_mapq", n}};
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, W, nullptr, 0, 0, d_mapq, min_mapq);
     return fsseg::sync_call(
-        in, n ? (min_mapq ? 2 : 1) : 0, n, offsets, nseg, 34,
+        in.in, in.count, n, offsets, nseg, 34,
         [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWideUnitBytes / W, grid); },
         [&](fsseg::SegBuffers& buf, uint32_t grid, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_segments_wide_filter(d_array, elem_bytes, d_mapq, 0, n, buf.off, nseg, require, exclude, min_mapq, buf.cnt,
                                                        buf.cnt + nseg * 32, buf.cnt + nseg * 33, 1 | (flags & 2), grid, s));
             return 0;
         },
-        [&](const fsseg::HostRows& got) { apply_all(out, selected, high, got, nseg, flags); });
+        [&](const fsseg::HostRows& got) { fsseg::apply_all(out, selected, high, got, nseg, flags); });
 }
 
 int FLAGSTATS_hip_wide_x64_segments_filter(const void* array, uint64_t n, int elem_bytes, const uint64_t* offsets, uint64_t nseg,
@@ -411,7 +396,7 @@ int FLAGSTATS_hip_wide_x64_segments_filter(const void* array, uint64_t n, int el
 {
     FS_ENTRY();
     int rc = segwf_args(array, n, elem_bytes, offsets, nseg, require, exclude, mapq, min_mapq, out, flags,
-                        "NULL offsets or out with nseg > 0");
+                        fsseg::kNullHost);
     if (rc || nseg == 0) return rc;
     // the elements cross the bus as they are, in chunks of "chunk_flags" * 2 bytes (the wide host entries'); a chunk's slice of the
     // MAPQ column rides in the same staging buffer, behind its elements (as FLAGSTATS_hip_wide_x64_filter stages it); every
@@ -431,7 +416,7 @@ int FLAGSTATS_hip_wide_x64_segments_filter(const void* array, uint64_t n, int el
                                                        buf.cnt, buf.cnt + nseg * 32, buf.cnt + nseg * 33, mode, grid, e.stream[sl]));
             return 0;
         },
-        [&](const fsseg::HostRows& got) { apply_all(out, selected, high, got, nseg, flags); });
+        [&](const fsseg::HostRows& got) { fsseg::apply_all(out, selected, high, got, nseg, flags); });
 }
 
 }  // extern "C"

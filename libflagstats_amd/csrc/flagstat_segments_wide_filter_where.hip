@@ -485,42 +485,15 @@ int segwfw_args(const void* array, uint64_t n, int elem_bytes, const uint64_t* o
                 const uint8_t* mapq, uint32_t min_mapq, const void* sel, uint64_t sel_offset, int sel_bits, const void* out, int flags,
                 const char* null_text)
 {
-    if (elem_bytes == 2)
-        return fail_text("elem_bytes 2: 16-bit arrays go to the u16 segments_filter_where entries "
-                         "(FLAGSTATS_hip_u16_x64_segments_filter_where, FLAGSTATS_hip_device_u16_segments_filter_where)");
-    if (elem_bytes != 4 && elem_bytes != 8) return fail_text("elem_bytes must be 4 or 8");
-    if (require > 0xFFFFu) return fail_text("require must be a 16-bit FLAG mask (at most 0xFFFF)");
-    if (exclude > 0xFFFFu) return fail_text("exclude must be a 16-bit FLAG mask (at most 0xFFFF)");
-    if (min_mapq > 255u) return fail_text("min_mapq must be at most 255 (MAPQ is one byte)");
-    if (sel_bits != 1 && sel_bits != 8) return fail_text("sel_bits must be 1 (an LSB-first bitmap) or 8 (one byte per element)");
-    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
+    using namespace fsdrv;
+    if (check_elem_bytes(elem_bytes, "elem_bytes 2: 16-bit arrays go to the u16 segments_filter_where entries "
+                                     "(FLAGSTATS_hip_u16_x64_segments_filter_where, FLAGSTATS_hip_device_u16_segments_filter_where)") ||
+        check_predicate(require, exclude, min_mapq) || check_sel_bits(sel_bits) || check_flags(flags))
+        return -1;
     if (nseg == 0) return 0;
-    if (!offsets || !out) return fail_text(null_text);
-    if (nseg > fsseg::kMaxSegments / 2) return fail_text("nseg is too large: its counters cannot be allocated");   // 34 words each
-    if (n && !array) return fail_text("NULL array with n > 0");
-    if (n && min_mapq && !mapq) return fail_text("NULL mapq with min_mapq > 0 and n > 0");
-    if (n && !sel) return fail_text("NULL selection with n > 0");
-    if (reinterpret_cast<uintptr_t>(array) & static_cast<uintptr_t>(elem_bytes - 1))
-        return fail_text(elem_bytes == 4 ? "array must be 4-byte aligned (elem_bytes 4)" : "array must be 8-byte aligned (elem_bytes 8)");
-    if (n > (~0ull - 64) / static_cast<uint64_t>(elem_bytes)) return fail_text("n * elem_bytes is not a size");
-    if (sel_offset > ~0ull - 64 - n) return fail_text("sel_offset + n is not an index");
-    return 0;
-}
-
-// the bytes of d_sel a call over the whole array needs, from d_sel itself on (n > 0)
-uint64_t sel_bytes(uint64_t n, uint64_t sel_offset, int sel_bits)
-{
-    uint64_t first = 0, bytes = 0;
-    where_extent(n, sel_offset, sel_bits, &first, &bytes);
-    return first + bytes;
-}
-
-// rows, counts, then masks, of a synchronous call into the caller's host words: rows and counts stored or added, masks stored or
-// ORed
-void apply_all(uint64_t* out, uint64_t* selected, uint64_t* high, const fsseg::HostRows& got, uint64_t nseg, int flags)
-{
-    fsseg::apply_both(out, selected, got, nseg, flags);
-    fsseg::apply_masks(high, got.p.get() + nseg * 33, nseg, flags);
+    return refused(fsseg::check_segments(offsets, out, nseg, null_text, fsseg::kMaxSegments / 2) || check_array_given(array, n) ||
+                   check_mapq_given(mapq, n, min_mapq) || check_sel_given(sel, n) || check_array_layout(array, n, elem_bytes) ||
+                   check_sel_range(sel_offset, n));
 }
 
 }  // namespace
@@ -534,18 +507,15 @@ int FLAGSTATS_hip_device_wide_segments_filter_where(const void* d_array, uint64_
 {
     FS_ENTRY();
     int rc = segwfw_args(d_array, n, elem_bytes, d_offsets, nseg, require, exclude, d_mapq, min_mapq, d_sel, sel_offset, sel_bits, d_out, flags,
-                         "NULL d_offsets or d_out with nseg > 0");
+                         fsseg::kNullDevice);
     if (rc || nseg == 0) return rc;
     const uint64_t W = static_cast<uint64_t>(elem_bytes);
     const fsdrv::DeviceWord words[] = {{d_selected, "d_selected", "the counts are added with device atomics"},
                                        {d_high, "d_high", "the masks are ORed with device atomics"}};
-    // the MAPQ column last: it is an input only when min_mapq > 0
-    const fsdrv::Input in[] = {{d_offsets, "d_offsets", (nseg + 1) * sizeof(uint64_t)},
-                               {d_array, "d_array", n * W},
-                               {d_sel, "d_sel", n ? sel_bytes(n, sel_offset, sel_bits) : 0},
-                               {d_mapq, "d_mapq", n}};
+    fsdrv::Inputs in = fsseg::offsets_input(d_offsets, nseg);
+    in.add_columns(d_array, n, W, d_sel, sel_offset, sel_bits, d_mapq, min_mapq);
     return fsseg::device_call(
-        d_out, words, 2, in, n ? (min_mapq ? 4 : 3) : 1, nseg, stream,
+        d_out, words, 2, in.in, in.count, nseg, stream,
         [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWideUnitBytes / W, grid); },
         [&](uint32_t grid, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_segments_wide_masked_filter(d_array, elem_bytes, d_mapq, d_sel, sel_offset, sel_bits, 0, n, d_offsets, nseg,
@@ -561,12 +531,13 @@ int FLAGSTATS_hip_device_wide_segments_filter_where_sync(const void* d_array, ui
 {
     FS_ENTRY();
     int rc = segwfw_args(d_array, n, elem_bytes, offsets, nseg, require, exclude, d_mapq, min_mapq, d_sel, sel_offset, sel_bits, out, flags,
-                         "NULL offsets or out with nseg > 0");
+                         fsseg::kNullHost);
     if (rc || nseg == 0) return rc;
     const uint64_t W = static_cast<uint64_t>(elem_bytes);
-    const fsdrv::Input in[] = {{d_array, "d_array", n * W}, {d_sel, "d_sel", n ? sel_bytes(n, sel_offset, sel_bits) : 0}, {d_mapq, "d_mapq", n}};
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, W, d_sel, sel_offset, sel_bits, d_mapq, min_mapq);
     return fsseg::sync_call(
-        in, n ? (min_mapq ? 3 : 2) : 0, n, offsets, nseg, 34,
+        in.in, in.count, n, offsets, nseg, 34,
         [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWideUnitBytes / W, grid); },
         [&](fsseg::SegBuffers& buf, uint32_t grid, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_segments_wide_masked_filter(d_array, elem_bytes, d_mapq, d_sel, sel_offset, sel_bits, 0, n, buf.off, nseg,
@@ -574,7 +545,7 @@ int FLAGSTATS_hip_device_wide_segments_filter_where_sync(const void* d_array, ui
                                                               1 | (flags & 2), grid, s));
             return 0;
         },
-        [&](const fsseg::HostRows& got) { apply_all(out, selected, high, got, nseg, flags); });
+        [&](const fsseg::HostRows& got) { fsseg::apply_all(out, selected, high, got, nseg, flags); });
 }
 
 int FLAGSTATS_hip_wide_x64_segments_filter_where(const void* array, uint64_t n, int elem_bytes, const uint64_t* offsets, uint64_t nseg,
@@ -584,7 +555,7 @@ int FLAGSTATS_hip_wide_x64_segments_filter_where(const void* array, uint64_t n, 
 {
     FS_ENTRY();
     int rc = segwfw_args(array, n, elem_bytes, offsets, nseg, require, exclude, mapq, min_mapq, sel, sel_offset, sel_bits, out, flags,
-                         "NULL offsets or out with nseg > 0");
+                         fsseg::kNullHost);
     if (rc || nseg == 0) return rc;
     // the elements cross the bus as they are, in chunks of "chunk_flags" * 2 bytes (the wide host entries'); a chunk's slices of the
     // MAPQ column and of the selection ride in the same staging buffer, behind its elements: the column's first, then the
@@ -612,7 +583,7 @@ int FLAGSTATS_hip_wide_x64_segments_filter_where(const void* array, uint64_t n, 
                                                               buf.cnt + nseg * 32, buf.cnt + nseg * 33, mode, grid, e.stream[sl]));
             return 0;
         },
-        [&](const fsseg::HostRows& got) { apply_all(out, selected, high, got, nseg, flags); });
+        [&](const fsseg::HostRows& got) { fsseg::apply_all(out, selected, high, got, nseg, flags); });
 }
 
 }  // extern "C"

@@ -408,38 +408,14 @@ namespace {
 int segww_args(const void* array, uint64_t n, int elem_bytes, const uint64_t* offsets, uint64_t nseg, const void* sel, uint64_t sel_offset,
                int sel_bits, const void* out, int flags, const char* null_text)
 {
-    if (elem_bytes == 2)
-        return fail_text("elem_bytes 2: 16-bit arrays go to the u16 segments_where entries (FLAGSTATS_hip_u16_x64_segments_where, "
-                         "FLAGSTATS_hip_device_u16_segments_where)");
-    if (elem_bytes != 4 && elem_bytes != 8) return fail_text("elem_bytes must be 4 or 8");
-    if (sel_bits != 1 && sel_bits != 8) return fail_text("sel_bits must be 1 (an LSB-first bitmap) or 8 (one byte per element)");
-    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
+    using namespace fsdrv;
+    if (check_elem_bytes(elem_bytes, "elem_bytes 2: 16-bit arrays go to the u16 segments_where entries "
+                                     "(FLAGSTATS_hip_u16_x64_segments_where, FLAGSTATS_hip_device_u16_segments_where)") ||
+        check_sel_bits(sel_bits) || check_flags(flags))
+        return -1;
     if (nseg == 0) return 0;
-    if (!offsets || !out) return fail_text(null_text);
-    if (nseg > fsseg::kMaxSegments / 2) return fail_text("nseg is too large: its counters cannot be allocated");   // 34 words each
-    if (n && !array) return fail_text("NULL array with n > 0");
-    if (n && !sel) return fail_text("NULL selection with n > 0");
-    if (reinterpret_cast<uintptr_t>(array) & static_cast<uintptr_t>(elem_bytes - 1))
-        return fail_text(elem_bytes == 4 ? "array must be 4-byte aligned (elem_bytes 4)" : "array must be 8-byte aligned (elem_bytes 8)");
-    if (n > (~0ull - 64) / static_cast<uint64_t>(elem_bytes)) return fail_text("n * elem_bytes is not a size");
-    if (sel_offset > ~0ull - 64 - n) return fail_text("sel_offset + n is not an index");
-    return 0;
-}
-
-// the bytes of d_sel a call over the whole array needs, from d_sel itself on (n > 0)
-uint64_t sel_bytes(uint64_t n, uint64_t sel_offset, int sel_bits)
-{
-    uint64_t first = 0, bytes = 0;
-    where_extent(n, sel_offset, sel_bits, &first, &bytes);
-    return first + bytes;
-}
-
-// rows, selected counts, then masks, of a synchronous call into the caller's host words: rows and counts stored or added, masks
-// stored or ORed
-void apply_all(uint64_t* out, uint64_t* selected, uint64_t* high, const fsseg::HostRows& got, uint64_t nseg, int flags)
-{
-    fsseg::apply_both(out, selected, got, nseg, flags);
-    fsseg::apply_masks(high, got.p.get() + nseg * 33, nseg, flags);
+    return refused(fsseg::check_segments(offsets, out, nseg, null_text, fsseg::kMaxSegments / 2) || check_array_given(array, n) ||
+                   check_sel_given(sel, n) || check_array_layout(array, n, elem_bytes) || check_sel_range(sel_offset, n));
 }
 
 }  // namespace
@@ -452,16 +428,15 @@ int FLAGSTATS_hip_device_wide_segments_where(const void* d_array, uint64_t n, in
 {
     FS_ENTRY();
     int rc = segww_args(d_array, n, elem_bytes, d_offsets, nseg, d_sel, sel_offset, sel_bits, d_out, flags,
-                        "NULL d_offsets or d_out with nseg > 0");
+                        fsseg::kNullDevice);
     if (rc || nseg == 0) return rc;
     const uint64_t W = static_cast<uint64_t>(elem_bytes);
     const fsdrv::DeviceWord words[] = {{d_selected, "d_selected", "the counts are added with device atomics"},
                                        {d_high, "d_high", "the masks are ORed with device atomics"}};
-    const fsdrv::Input in[] = {{d_offsets, "d_offsets", (nseg + 1) * sizeof(uint64_t)},
-                               {d_array, "d_array", n * W},
-                               {d_sel, "d_sel", n ? sel_bytes(n, sel_offset, sel_bits) : 0}};
+    fsdrv::Inputs in = fsseg::offsets_input(d_offsets, nseg);
+    in.add_columns(d_array, n, W, d_sel, sel_offset, sel_bits, nullptr, 0);
     return fsseg::device_call(
-        d_out, words, 2, in, n ? 3 : 1, nseg, stream,
+        d_out, words, 2, in.in, in.count, nseg, stream,
         [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWideUnitBytes / W, grid); },
         [&](uint32_t grid, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_segments_wide_where(d_array, elem_bytes, d_sel, sel_offset, sel_bits, 0, n, d_offsets, nseg, d_out,
@@ -475,18 +450,19 @@ int FLAGSTATS_hip_device_wide_segments_where_sync(const void* d_array, uint64_t 
                                                   uint64_t* high, int flags)
 {
     FS_ENTRY();
-    int rc = segww_args(d_array, n, elem_bytes, offsets, nseg, d_sel, sel_offset, sel_bits, out, flags, "NULL offsets or out with nseg > 0");
+    int rc = segww_args(d_array, n, elem_bytes, offsets, nseg, d_sel, sel_offset, sel_bits, out, flags, fsseg::kNullHost);
     if (rc || nseg == 0) return rc;
     const uint64_t W = static_cast<uint64_t>(elem_bytes);
-    const fsdrv::Input in[] = {{d_array, "d_array", n * W}, {d_sel, "d_sel", n ? sel_bytes(n, sel_offset, sel_bits) : 0}};
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, W, d_sel, sel_offset, sel_bits, nullptr, 0);
     return fsseg::sync_call(
-        in, n ? 2 : 0, n, offsets, nseg, 34, [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWideUnitBytes / W, grid); },
+        in.in, in.count, n, offsets, nseg, 34, [&](uint32_t grid) { return fsseg::fits(d_array, n, fsk::kSegWideUnitBytes / W, grid); },
         [&](fsseg::SegBuffers& buf, uint32_t grid, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_segments_wide_where(d_array, elem_bytes, d_sel, sel_offset, sel_bits, 0, n, buf.off, nseg, buf.cnt,
                                                       buf.cnt + nseg * 32, buf.cnt + nseg * 33, 1 | (flags & 2), grid, s));
             return 0;
         },
-        [&](const fsseg::HostRows& got) { apply_all(out, selected, high, got, nseg, flags); });
+        [&](const fsseg::HostRows& got) { fsseg::apply_all(out, selected, high, got, nseg, flags); });
 }
 
 int FLAGSTATS_hip_wide_x64_segments_where(const void* array, uint64_t n, int elem_bytes, const uint64_t* offsets, uint64_t nseg,
@@ -494,7 +470,7 @@ int FLAGSTATS_hip_wide_x64_segments_where(const void* array, uint64_t n, int ele
                                           uint64_t* high, int flags)
 {
     FS_ENTRY();
-    int rc = segww_args(array, n, elem_bytes, offsets, nseg, sel, sel_offset, sel_bits, out, flags, "NULL offsets or out with nseg > 0");
+    int rc = segww_args(array, n, elem_bytes, offsets, nseg, sel, sel_offset, sel_bits, out, flags, fsseg::kNullHost);
     if (rc || nseg == 0) return rc;
     // the elements cross the bus as they are, in chunks of "chunk_flags" * 2 bytes (the wide host entries'); a chunk's slice of the
     // selection rides in the same staging buffer, behind its elements -- a bitmap slice from the byte that holds the chunk's first
@@ -518,7 +494,7 @@ int FLAGSTATS_hip_wide_x64_segments_where(const void* array, uint64_t n, int ele
                                                       e.stream[sl]));
             return 0;
         },
-        [&](const fsseg::HostRows& got) { apply_all(out, selected, high, got, nseg, flags); });
+        [&](const fsseg::HostRows& got) { fsseg::apply_all(out, selected, high, got, nseg, flags); });
 }
 
 }  // extern "C"

@@ -265,30 +265,12 @@ namespace {
 // what every form refuses before it touches the GPU
 int where_args(const uint16_t* array, uint64_t n, const void* sel, uint64_t sel_offset, int sel_bits, const void* out, int flags)
 {
-    if (sel_bits != 1 && sel_bits != 8) return fail_text("sel_bits must be 1 (an LSB-first bitmap) or 8 (one byte per element)");
-    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
-    if (n && !array) return fail_text("NULL array with n > 0");
-    if (n && !sel) return fail_text("NULL selection with n > 0");
-    if (reinterpret_cast<uintptr_t>(array) & 1u) return fail_text("array must be 2-byte aligned");
-    if (n > (~0ull - 64) / 2) return fail_text("n * 2 is not a size");
-    if (sel_offset > ~0ull - 64 - n) return fail_text("sel_offset + n is not an index");
-    if (!out && (n || (flags & 1))) return fail_text("NULL counters");
-    return 0;
+    using namespace fsdrv;
+    return refused(check_sel_bits(sel_bits) || check_flags(flags) || check_array_given(array, n) || check_sel_given(sel, n) ||
+                   check_array_layout(array, n, 2) || check_sel_range(sel_offset, n) || check_counters(out, n, flags));
 }
 
 constexpr const char* kWhereAlloc = "hipMalloc(where counters)";
-
-// the array and the selection as a call's inputs (n > 0)
-struct WhereInputs {
-    fsdrv::Input in[2];
-    WhereInputs(const uint16_t* d_array, uint64_t n, const void* d_sel, uint64_t sel_offset, int sel_bits)
-    {
-        uint64_t first = 0, bytes = 0;
-        if (n) where_extent(n, sel_offset, sel_bits, &first, &bytes);
-        in[0] = fsdrv::Input{d_array, "d_array", n * 2};
-        in[1] = fsdrv::Input{d_sel, "d_sel", first + bytes};
-    }
-};
 
 }  // namespace
 
@@ -302,11 +284,11 @@ int FLAGSTATS_hip_device_u16_where(const uint16_t* d_array, uint64_t n, const vo
     if (rc) return rc;
     if (n == 0 && !(flags & 1)) return 0;
     const fsdrv::DeviceWord word{d_selected, "d_selected", "the count is added with a device atomic"};
-    const WhereInputs w(d_array, n, d_sel, sel_offset, sel_bits);
-    const int inputs = n ? 2 : 0;
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, 2, d_sel, sel_offset, sel_bits, nullptr, 0);
     fsdrv::DeviceCall call;
-    if ((rc = call.open(d_out, word, w.in, inputs, stream))) return rc;
-    if ((rc = fsdrv::check_extents(d_out, word, w.in, inputs))) return rc;
+    if ((rc = call.open(d_out, word, in.in, in.count, stream))) return rc;
+    if ((rc = fsdrv::check_extents(d_out, word, in.in, in.count))) return rc;
     Engine* e = call.e;
     hipStream_t s = call.s;
     FS_HIP_TRY(fsk_launch_where(d_array, n, d_sel, sel_offset, sel_bits, d_out, d_selected, flags & 3, fsint::grid_for(*e), s));
@@ -323,8 +305,9 @@ int FLAGSTATS_hip_device_u16_where_sync(const uint16_t* d_array, uint64_t n, con
         fsdrv::store_nothing(out, selected, flags);
         return 0;
     }
-    const WhereInputs w(d_array, n, d_sel, sel_offset, sel_bits);
-    return fsdrv::sync_call(w.in, 2, kWhereAlloc, out, selected, flags, fsdrv::kWordAdd, fsdrv::fits_always,
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, 2, d_sel, sel_offset, sel_bits, nullptr, 0);
+    return fsdrv::sync_call(in.in, in.count, kWhereAlloc, out, selected, flags, fsdrv::kWordAdd, fsdrv::fits_always,
                             [&](Engine& e, fsdrv::Row& row, hipStream_t s) {
                                 FS_HIP_TRY(fsk_launch_where(d_array, n, d_sel, sel_offset, sel_bits, row.d, row.d + 32, 1 | (flags & 2), fsint::grid_for(e), s));
                                 return 0;

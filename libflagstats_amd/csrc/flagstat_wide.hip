@@ -187,15 +187,10 @@ namespace {
 // what every form refuses before it touches the GPU
 int wide_args(const void* array, uint64_t n, int elem_bytes, const void* out, int flags)
 {
-    if (elem_bytes == 2) return fail_text("elem_bytes 2: 16-bit arrays go to the u16 entries (FLAGSTATS_u16_x64, FLAGSTATS_hip_device_u16)");
-    if (elem_bytes != 4 && elem_bytes != 8) return fail_text("elem_bytes must be 4 or 8");
-    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
-    if (n && !array) return fail_text("NULL array with n > 0");
-    if (reinterpret_cast<uintptr_t>(array) & static_cast<uintptr_t>(elem_bytes - 1))
-        return fail_text(elem_bytes == 4 ? "array must be 4-byte aligned (elem_bytes 4)" : "array must be 8-byte aligned (elem_bytes 8)");
-    if (n > (~0ull - 64) / static_cast<uint64_t>(elem_bytes)) return fail_text("n * elem_bytes is not a size");
-    if (!out && (n || (flags & 1))) return fail_text("NULL counters");
-    return 0;
+    using namespace fsdrv;
+    return refused(check_elem_bytes(elem_bytes, "elem_bytes 2: 16-bit arrays go to the u16 entries (FLAGSTATS_u16_x64, FLAGSTATS_hip_device_u16)") ||
+                   check_flags(flags) || check_array_given(array, n) || check_array_layout(array, n, elem_bytes) ||
+                   check_counters(out, n, flags));
 }
 
 constexpr const char* kWideAlloc = "hipMalloc(wide counters)";
@@ -211,11 +206,11 @@ int FLAGSTATS_hip_device_wide(const void* d_array, uint64_t n, int elem_bytes, u
     if (rc) return rc;
     if (n == 0 && !(flags & 1)) return 0;
     const fsdrv::DeviceWord word{d_high, "d_high", "the mask is ORed with a device atomic"};
-    const fsdrv::Input in[] = {{d_array, "d_array", n * static_cast<uint64_t>(elem_bytes)}};
-    const int inputs = n ? 1 : 0;
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, elem_bytes, nullptr, 0, 0, nullptr, 0);
     fsdrv::DeviceCall call;
-    if ((rc = call.open(d_out, word, in, inputs, stream))) return rc;
-    if ((rc = fsdrv::check_extents(d_out, word, in, inputs))) return rc;
+    if ((rc = call.open(d_out, word, in.in, in.count, stream))) return rc;
+    if ((rc = fsdrv::check_extents(d_out, word, in.in, in.count))) return rc;
     Engine* e = call.e;
     hipStream_t s = call.s;
     FS_HIP_TRY(fsk_launch_wide(d_array, n, elem_bytes, d_out, d_high, flags & 3, fsint::grid_for(*e), s));
@@ -231,8 +226,9 @@ int FLAGSTATS_hip_device_wide_sync(const void* d_array, uint64_t n, int elem_byt
         fsdrv::store_nothing(out, high, flags);
         return 0;
     }
-    const fsdrv::Input in[] = {{d_array, "d_array", n * static_cast<uint64_t>(elem_bytes)}};
-    return fsdrv::sync_call(in, 1, kWideAlloc, out, high, flags, fsdrv::kWordOr, fsdrv::fits_always, [&](Engine& e, fsdrv::Row& row, hipStream_t s) {
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, elem_bytes, nullptr, 0, 0, nullptr, 0);
+    return fsdrv::sync_call(in.in, in.count, kWideAlloc, out, high, flags, fsdrv::kWordOr, fsdrv::fits_always, [&](Engine& e, fsdrv::Row& row, hipStream_t s) {
         FS_HIP_TRY(fsk_launch_wide(d_array, n, elem_bytes, row.d, row.d + 32, 1 | (flags & 2), fsint::grid_for(e), s));
         return 0;
     });

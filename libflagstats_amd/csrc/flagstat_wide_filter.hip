@@ -237,32 +237,14 @@ namespace {
 int wide_filter_args(const void* array, uint64_t n, int elem_bytes, uint32_t require, uint32_t exclude, const uint8_t* mapq,
                      uint32_t min_mapq, const void* out, int flags)
 {
-    if (elem_bytes == 2)
-        return fail_text("elem_bytes 2: 16-bit arrays go to the u16 filter entries (FLAGSTATS_hip_u16_x64_filter, FLAGSTATS_hip_device_u16_filter)");
-    if (elem_bytes != 4 && elem_bytes != 8) return fail_text("elem_bytes must be 4 or 8");
-    if (require > 0xFFFFu) return fail_text("require must be a 16-bit FLAG mask (at most 0xFFFF)");
-    if (exclude > 0xFFFFu) return fail_text("exclude must be a 16-bit FLAG mask (at most 0xFFFF)");
-    if (min_mapq > 255u) return fail_text("min_mapq must be at most 255 (MAPQ is one byte)");
-    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
-    if (n && !array) return fail_text("NULL array with n > 0");
-    if (n && min_mapq && !mapq) return fail_text("NULL mapq with min_mapq > 0 and n > 0");
-    if (reinterpret_cast<uintptr_t>(array) & static_cast<uintptr_t>(elem_bytes - 1))
-        return fail_text(elem_bytes == 4 ? "array must be 4-byte aligned (elem_bytes 4)" : "array must be 8-byte aligned (elem_bytes 8)");
-    if (n > (~0ull - 64) / static_cast<uint64_t>(elem_bytes)) return fail_text("n * elem_bytes is not a size");
-    if (!out && (n || (flags & 1))) return fail_text("NULL counters");
-    return 0;
+    using namespace fsdrv;
+    return refused(check_elem_bytes(elem_bytes, "elem_bytes 2: 16-bit arrays go to the u16 filter entries (FLAGSTATS_hip_u16_x64_filter, "
+                                                "FLAGSTATS_hip_device_u16_filter)") ||
+                   check_predicate(require, exclude, min_mapq) || check_flags(flags) || check_array_given(array, n) ||
+                   check_mapq_given(mapq, n, min_mapq) || check_array_layout(array, n, elem_bytes) || check_counters(out, n, flags));
 }
 
 constexpr const char* kWideFilterAlloc = "hipMalloc(wide filter counters)";
-
-// a wave's totals are uint32: the one thing the step split still refuses once wide_filter_args has passed
-int wide_filter_fits(const void* array, uint64_t n, int elem_bytes, uint32_t grid)
-{
-    uint64_t geo[6];
-    if (fsdrv::step_split(reinterpret_cast<uintptr_t>(array), n, elem_bytes, grid, geo) != hipSuccess)
-        return fail_text("n is too large for this grid: a wave's uint32 totals could overflow (split the array)");
-    return 0;
-}
 
 }  // namespace
 
@@ -278,14 +260,14 @@ int FLAGSTATS_hip_device_wide_filter(const void* d_array, uint64_t n, int elem_b
     if (n == 0 && !(flags & 1)) return 0;
     const fsdrv::DeviceWord words[] = {{d_selected, "d_selected", "the count is added with a device atomic"},
                                        {d_high, "d_high", "the mask is ORed with a device atomic"}};
-    const fsdrv::Input in[] = {{d_array, "d_array", n * static_cast<uint64_t>(elem_bytes)}, {d_mapq, "d_mapq", n}};
-    const int inputs = n ? (min_mapq ? 2 : 1) : 0;
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, elem_bytes, nullptr, 0, 0, d_mapq, min_mapq);
     fsdrv::DeviceCall call;
-    if ((rc = call.open(d_out, words, 2, in, inputs, stream))) return rc;
+    if ((rc = call.open(d_out, words, 2, in.in, in.count, stream))) return rc;
     Engine* e = call.e;
     hipStream_t s = call.s;
-    if ((rc = wide_filter_fits(d_array, n, elem_bytes, fsint::grid_for(*e)))) return rc;
-    if ((rc = fsdrv::check_extents(d_out, words, 2, in, inputs))) return rc;
+    if ((rc = fsdrv::step_fits(d_array, n, elem_bytes, fsint::grid_for(*e)))) return rc;
+    if ((rc = fsdrv::check_extents(d_out, words, 2, in.in, in.count))) return rc;
     FS_HIP_TRY(fsk_launch_wide_filter(d_array, n, elem_bytes, require, exclude, d_mapq, min_mapq, d_out, d_selected, d_high, flags & 3,
                                       fsint::grid_for(*e), s));
     return 0;
@@ -302,10 +284,11 @@ int FLAGSTATS_hip_device_wide_filter_sync(const void* d_array, uint64_t n, int e
         fsdrv::store_nothing(out, selected, high, flags);
         return 0;
     }
-    const fsdrv::Input in[] = {{d_array, "d_array", n * static_cast<uint64_t>(elem_bytes)}, {d_mapq, "d_mapq", n}};
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, elem_bytes, nullptr, 0, 0, d_mapq, min_mapq);
     return fsdrv::sync_call2(
-        in, min_mapq ? 2 : 1, kWideFilterAlloc, out, selected, high, flags,
-        [&](Engine& e) { return wide_filter_fits(d_array, n, elem_bytes, fsint::grid_for(e)); },
+        in.in, in.count, kWideFilterAlloc, out, selected, high, flags,
+        [&](Engine& e) { return fsdrv::step_fits(d_array, n, elem_bytes, fsint::grid_for(e)); },
         [&](Engine& e, fsdrv::Row& row, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_wide_filter(d_array, n, elem_bytes, require, exclude, d_mapq, min_mapq, row.d, row.d + 32, row.d + 33,
                                               1 | (flags & 2), fsint::grid_for(e), s));
@@ -334,7 +317,7 @@ int FLAGSTATS_hip_wide_x64_filter(const void* array, uint64_t n, int elem_bytes,
     const uint8_t* src = static_cast<const uint8_t*>(array);
     return fsdrv::host_call2(
         n, chunk, cap * W / 2 + (mapq_cap + 1) / 2, kWideFilterAlloc, out, selected, high, flags,
-        [&](Engine& e) { return wide_filter_fits(nullptr, cap, elem_bytes, fsint::grid_for(e)); },
+        [&](Engine& e) { return fsdrv::step_fits(nullptr, cap, elem_bytes, fsint::grid_for(e)); },
         [&](Engine& e, fsdrv::Row& row, int sl, uint64_t pos, uint64_t c) {
             const uint32_t grid = fsint::grid_for(e);
             uint8_t* d_mapq = reinterpret_cast<uint8_t*>(e.stage[sl]) + cap * W;

@@ -349,52 +349,17 @@ namespace {
 int wide_filter_where_args(const void* array, uint64_t n, int elem_bytes, uint32_t require, uint32_t exclude, const uint8_t* mapq,
                            uint32_t min_mapq, const void* sel, uint64_t sel_offset, int sel_bits, const void* out, int flags)
 {
-    if (elem_bytes == 2)
-        return fail_text("elem_bytes 2: 16-bit arrays go to the u16 filter_where entries (FLAGSTATS_hip_u16_x64_filter_where, "
-                         "FLAGSTATS_hip_device_u16_filter_where)");
-    if (elem_bytes != 4 && elem_bytes != 8) return fail_text("elem_bytes must be 4 or 8");
-    if (require > 0xFFFFu) return fail_text("require must be a 16-bit FLAG mask (at most 0xFFFF)");
-    if (exclude > 0xFFFFu) return fail_text("exclude must be a 16-bit FLAG mask (at most 0xFFFF)");
-    if (min_mapq > 255u) return fail_text("min_mapq must be at most 255 (MAPQ is one byte)");
-    if (sel_bits != 1 && sel_bits != 8) return fail_text("sel_bits must be 1 (an LSB-first bitmap) or 8 (one byte per element)");
-    if (flags & ~3) return fail_text("flags: bit 0 store, bit 1 superset; no other bits");
-    if (n && !array) return fail_text("NULL array with n > 0");
-    if (n && min_mapq && !mapq) return fail_text("NULL mapq with min_mapq > 0 and n > 0");
-    if (n && !sel)
-        return fail_text("NULL selection with n > 0 (no selection: the filtered wide entries FLAGSTATS_hip_wide_x64_filter, "
-                         "FLAGSTATS_hip_device_wide_filter)");
-    if (reinterpret_cast<uintptr_t>(array) & static_cast<uintptr_t>(elem_bytes - 1))
-        return fail_text(elem_bytes == 4 ? "array must be 4-byte aligned (elem_bytes 4)" : "array must be 8-byte aligned (elem_bytes 8)");
-    if (n > (~0ull - 64) / static_cast<uint64_t>(elem_bytes)) return fail_text("n * elem_bytes is not a size");
-    if (sel_offset > ~0ull - 64 - n) return fail_text("sel_offset + n is not an index");
-    if (!out && (n || (flags & 1))) return fail_text("NULL counters");
-    return 0;
+    using namespace fsdrv;
+    return refused(check_elem_bytes(elem_bytes, "elem_bytes 2: 16-bit arrays go to the u16 filter_where entries "
+                                                "(FLAGSTATS_hip_u16_x64_filter_where, FLAGSTATS_hip_device_u16_filter_where)") ||
+                   check_predicate(require, exclude, min_mapq) || check_sel_bits(sel_bits) || check_flags(flags) ||
+                   check_array_given(array, n) || check_mapq_given(mapq, n, min_mapq) ||
+                   check_sel_given(sel, n, "NULL selection with n > 0 (no selection: the filtered wide entries FLAGSTATS_hip_wide_x64_filter, "
+                                           "FLAGSTATS_hip_device_wide_filter)") ||
+                   check_array_layout(array, n, elem_bytes) || check_sel_range(sel_offset, n) || check_counters(out, n, flags));
 }
 
 constexpr const char* kWideFilterWhereAlloc = "hipMalloc(wide filter_where counters)";
-
-// a wave's totals are uint32: the one thing the step split still refuses once wide_filter_where_args has passed
-int wide_filter_where_fits(const void* array, uint64_t n, int elem_bytes, uint32_t grid)
-{
-    uint64_t geo[6];
-    if (fsdrv::step_split(reinterpret_cast<uintptr_t>(array), n, elem_bytes, grid, geo) != hipSuccess)
-        return fail_text("n is too large for this grid: a wave's uint32 totals could overflow (split the array)");
-    return 0;
-}
-
-// the array, the selection and the MAPQ column (last: it is an input only when min_mapq > 0) as a call's inputs (n > 0)
-struct WideFilterWhereInputs {
-    fsdrv::Input in[3];
-    WideFilterWhereInputs(const void* d_array, uint64_t n, int elem_bytes, const uint8_t* d_mapq, const void* d_sel, uint64_t sel_offset,
-                          int sel_bits)
-    {
-        uint64_t first = 0, bytes = 0;
-        if (n) where_extent(n, sel_offset, sel_bits, &first, &bytes);
-        in[0] = fsdrv::Input{d_array, "d_array", n * static_cast<uint64_t>(elem_bytes)};
-        in[1] = fsdrv::Input{d_sel, "d_sel", first + bytes};
-        in[2] = fsdrv::Input{d_mapq, "d_mapq", n};
-    }
-};
 
 }  // namespace
 
@@ -410,14 +375,14 @@ int FLAGSTATS_hip_device_wide_filter_where(const void* d_array, uint64_t n, int 
     if (n == 0 && !(flags & 1)) return 0;
     const fsdrv::DeviceWord words[] = {{d_selected, "d_selected", "the count is added with a device atomic"},
                                        {d_high, "d_high", "the mask is ORed with a device atomic"}};
-    const WideFilterWhereInputs w(d_array, n, elem_bytes, d_mapq, d_sel, sel_offset, sel_bits);
-    const int inputs = n ? (min_mapq ? 3 : 2) : 0;
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, elem_bytes, d_sel, sel_offset, sel_bits, d_mapq, min_mapq);
     fsdrv::DeviceCall call;
-    if ((rc = call.open(d_out, words, 2, w.in, inputs, stream))) return rc;
+    if ((rc = call.open(d_out, words, 2, in.in, in.count, stream))) return rc;
     Engine* e = call.e;
     hipStream_t s = call.s;
-    if ((rc = wide_filter_where_fits(d_array, n, elem_bytes, fsint::grid_for(*e)))) return rc;
-    if ((rc = fsdrv::check_extents(d_out, words, 2, w.in, inputs))) return rc;
+    if ((rc = fsdrv::step_fits(d_array, n, elem_bytes, fsint::grid_for(*e)))) return rc;
+    if ((rc = fsdrv::check_extents(d_out, words, 2, in.in, in.count))) return rc;
     FS_HIP_TRY(fsk_launch_wide_filter_where(d_array, n, elem_bytes, require, exclude, d_mapq, min_mapq, d_sel, sel_offset, sel_bits, d_out,
                                             d_selected, d_high, flags & 3, fsint::grid_for(*e), s));
     return 0;
@@ -434,10 +399,11 @@ int FLAGSTATS_hip_device_wide_filter_where_sync(const void* d_array, uint64_t n,
         fsdrv::store_nothing(out, selected, high, flags);
         return 0;
     }
-    const WideFilterWhereInputs w(d_array, n, elem_bytes, d_mapq, d_sel, sel_offset, sel_bits);
+    fsdrv::Inputs in;
+    in.add_columns(d_array, n, elem_bytes, d_sel, sel_offset, sel_bits, d_mapq, min_mapq);
     return fsdrv::sync_call2(
-        w.in, min_mapq ? 3 : 2, kWideFilterWhereAlloc, out, selected, high, flags,
-        [&](Engine& e) { return wide_filter_where_fits(d_array, n, elem_bytes, fsint::grid_for(e)); },
+        in.in, in.count, kWideFilterWhereAlloc, out, selected, high, flags,
+        [&](Engine& e) { return fsdrv::step_fits(d_array, n, elem_bytes, fsint::grid_for(e)); },
         [&](Engine& e, fsdrv::Row& row, hipStream_t s) {
             FS_HIP_TRY(fsk_launch_wide_filter_where(d_array, n, elem_bytes, require, exclude, d_mapq, min_mapq, d_sel, sel_offset, sel_bits,
                                                     row.d, row.d + 32, row.d + 33, 1 | (flags & 2), fsint::grid_for(e), s));
@@ -471,7 +437,7 @@ int FLAGSTATS_hip_wide_x64_filter_where(const void* array, uint64_t n, int elem_
     const uint8_t* sel_src = static_cast<const uint8_t*>(sel);
     return fsdrv::host_call2(
         n, chunk, cap * W / 2 + mapq_slot + (sel_cap + 1) / 2, kWideFilterWhereAlloc, out, selected, high, flags,
-        [&](Engine& e) { return wide_filter_where_fits(nullptr, cap, elem_bytes, fsint::grid_for(e)); },
+        [&](Engine& e) { return fsdrv::step_fits(nullptr, cap, elem_bytes, fsint::grid_for(e)); },
         [&](Engine& e, fsdrv::Row& row, int sl, uint64_t pos, uint64_t c) {
             const uint32_t grid = fsint::grid_for(e);
             uint64_t first, bytes;

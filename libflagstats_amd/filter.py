@@ -13,9 +13,8 @@ import ctypes
 import numpy as np
 
 from . import _checks, _lib
+from ._checks import STORE, SUPERSET  # noqa: F401  (kept as this module's names)
 from .pyflagstats import _as_dict
-
-STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
 
 
 def _check_predicate(require, exclude, min_mapq, has_mapq: bool):
@@ -83,7 +82,7 @@ def counters_filter(values, require: int = 0, exclude: int = 0, mapq=None, min_m
     _lib.check(_lib.lib().FLAGSTATS_hip_u16_x64_filter(v.ctypes.data if v.size else None, v.size, require, exclude,
                                                        q.ctypes.data if q is not None and q.size else None, min_mapq,
                                                        out.ctypes.data, ctypes.byref(selected),
-                                                       STORE | (SUPERSET if superset else 0)), "FLAGSTATS_hip_u16_x64_filter")
+                                                       _checks.c_flags(True, superset)), "FLAGSTATS_hip_u16_x64_filter")
     return out, int(selected.value)
 
 
@@ -105,7 +104,7 @@ def count_device_ptr_filter(ptr: int, n: int, require: int = 0, exclude: int = 0
     selected = ctypes.c_uint64(0)
     _lib.check(_lib.lib().FLAGSTATS_hip_device_u16_filter_sync(ptr if n else None, n, require, exclude, mapq_ptr if n and mapq_ptr else None,
                                                                min_mapq, out.ctypes.data, ctypes.byref(selected),
-                                                               STORE | (SUPERSET if superset else 0)), "FLAGSTATS_hip_device_u16_filter_sync")
+                                                               _checks.c_flags(True, superset)), "FLAGSTATS_hip_device_u16_filter_sync")
     return out, int(selected.value)
 
 
@@ -119,12 +118,7 @@ def count_torch_filter(t, require: int = 0, exclude: int = 0, mapq=None, min_map
     ``store=False`` adds into both; ``store=True`` overwrites both."""
     import torch
 
-    if not isinstance(t, torch.Tensor):
-        raise ValueError("t must be a torch.Tensor, not %s" % type(t).__name__)
-    if t.dtype not in (torch.int16, torch.uint16):
-        raise ValueError("t must have dtype int16 or uint16, not %s" % t.dtype)
-    if t.dim() != 1 or not t.is_contiguous():
-        raise ValueError("t must be 1-D and contiguous")
+    _checks.check_u16_tensor(t)
     _check_mapq_torch(mapq, t.numel())
     require, exclude, min_mapq = _check_predicate(require, exclude, min_mapq, mapq is not None)
     _checks.check_result_pair(out, "selected", selected)
@@ -133,7 +127,7 @@ def count_torch_filter(t, require: int = 0, exclude: int = 0, mapq=None, min_map
     with torch.cuda.device(t.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
         n = t.numel()
-        flags = (STORE if store else 0) | (SUPERSET if superset else 0)
+        flags = _checks.c_flags(store, superset)
         _lib.check(lib.FLAGSTATS_hip_device_u16_filter(t.data_ptr() if n else None, n, require, exclude,
                                                        mapq.data_ptr() if mapq is not None and n else None, min_mapq, out.data_ptr(),
                                                        selected.data_ptr(), flags, stream),

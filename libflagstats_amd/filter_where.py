@@ -15,12 +15,11 @@ import ctypes
 import numpy as np
 
 from . import _checks, _lib
+from ._checks import STORE, SUPERSET  # noqa: F401  (kept as this module's names)
 from .filter import _check_mapq_numpy, _check_mapq_torch, _check_predicate
 from .pyflagstats import _as_dict
 from .where import _check_numpy as _check_values_and_selection
 from .where import _check_sel_bits, _check_torch
-
-STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
 
 
 def counters_filter_where(values, where, require: int = 0, exclude: int = 0, mapq=None, min_mapq: int = 0, packed: bool = False,
@@ -39,7 +38,7 @@ def counters_filter_where(values, where, require: int = 0, exclude: int = 0, map
                                                              q.ctypes.data if q is not None and q.size else None, min_mapq,
                                                              w.ctypes.data if v.size else None, bit_offset, 1 if packed else 8,
                                                              out.ctypes.data, ctypes.byref(selected),
-                                                             STORE | (SUPERSET if superset else 0)),
+                                                             _checks.c_flags(True, superset)),
                "FLAGSTATS_hip_u16_x64_filter_where")
     return out, int(selected.value)
 
@@ -68,7 +67,7 @@ def count_device_ptr_filter_where(ptr: int, n: int, sel_ptr: int, sel_bits: int,
     _lib.check(_lib.lib().FLAGSTATS_hip_device_u16_filter_where_sync(ptr if n else None, n, require, exclude,
                                                                      mapq_ptr if n and mapq_ptr else None, min_mapq,
                                                                      sel_ptr if n else None, sel_offset, sel_bits, out.ctypes.data,
-                                                                     ctypes.byref(selected), STORE | (SUPERSET if superset else 0)),
+                                                                     ctypes.byref(selected), _checks.c_flags(True, superset)),
                "FLAGSTATS_hip_device_u16_filter_where_sync")
     return out, int(selected.value)
 
@@ -93,7 +92,7 @@ def count_torch_filter_where(t, where, require: int = 0, exclude: int = 0, mapq=
     with torch.cuda.device(t.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
         n = t.numel()
-        flags = (STORE if store else 0) | (SUPERSET if superset else 0)
+        flags = _checks.c_flags(store, superset)
         _lib.check(lib.FLAGSTATS_hip_device_u16_filter_where(t.data_ptr() if n else None, n, require, exclude,
                                                              mapq.data_ptr() if mapq is not None and n else None, min_mapq,
                                                              where.data_ptr() if n else None, bit_offset, 1 if packed else 8,

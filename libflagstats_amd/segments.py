@@ -14,10 +14,9 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _checks, _lib
+from ._checks import STORE, SUPERSET  # noqa: F401  (kept as this module's names)
 from .pyflagstats import _as_dict
-
-STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
 
 
 def offsets_from_lengths(lengths) -> np.ndarray:
@@ -64,7 +63,7 @@ def flagstats_segments(values, offsets, superset: bool = False) -> np.ndarray:
     out = np.zeros((nseg, 32), dtype=np.uint64)
     if nseg:
         _lib.check(_lib.lib().FLAGSTATS_hip_u16_x64_segments(v.ctypes.data if v.size else None, v.size, o.ctypes.data, nseg,
-                                                             out.ctypes.data, STORE | (SUPERSET if superset else 0)),
+                                                             out.ctypes.data, _checks.c_flags(True, superset)),
                    "FLAGSTATS_hip_u16_x64_segments")
     return out
 
@@ -77,7 +76,7 @@ def count_segments_device_ptr(ptr: int, n: int, offsets, superset: bool = False)
     out = np.zeros((nseg, 32), dtype=np.uint64)
     if nseg:
         _lib.check(_lib.lib().FLAGSTATS_hip_device_u16_segments_sync(ptr, n, o.ctypes.data, nseg, out.ctypes.data,
-                                                                     STORE | (SUPERSET if superset else 0)),
+                                                                     _checks.c_flags(True, superset)),
                    "FLAGSTATS_hip_device_u16_segments_sync")
     return out
 
@@ -102,7 +101,7 @@ def count_segments_torch(t, offsets, out=None, store: bool = True, superset: boo
             and out.device == t.device):
         raise ValueError("out must be a contiguous int64 CUDA tensor of shape (nseg, 32) on the array's device")
     stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-    flags = (STORE if store else 0) | (SUPERSET if superset else 0)
+    flags = _checks.c_flags(store, superset)
     _lib.check(_lib.lib().FLAGSTATS_hip_device_u16_segments(t.data_ptr() if t.numel() else None, t.numel(), offsets.data_ptr(),
                                                             nseg, out.data_ptr(), flags, stream),
                "FLAGSTATS_hip_device_u16_segments")

@@ -15,11 +15,10 @@ import ctypes
 import numpy as np
 
 from . import _checks, _lib
-from .filter import _check_numpy, _check_predicate
+from ._checks import STORE, SUPERSET  # noqa: F401  (kept as this module's names)
+from .filter import _check_mapq_torch, _check_numpy, _check_predicate
 from .pyflagstats import _as_dict
 from .segments import check_offsets
-
-STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
 
 
 def flagstats_segments_filter(values, offsets, require: int = 0, exclude: int = 0, mapq=None, min_mapq: int = 0,
@@ -31,14 +30,13 @@ def flagstats_segments_filter(values, offsets, require: int = 0, exclude: int = 
     require, exclude, min_mapq = _check_predicate(require, exclude, min_mapq, q is not None)
     o = check_offsets(offsets, v.size)
     nseg = o.size - 1
-    out = np.zeros((nseg, 32), dtype=np.uint64)
-    selected = np.zeros(nseg, dtype=np.uint64)
+    out, selected = _checks.segment_results(nseg, 1)
     if nseg:
         _lib.check(_lib.lib().FLAGSTATS_hip_u16_x64_segments_filter(v.ctypes.data if v.size else None, v.size, o.ctypes.data, nseg,
                                                                     require, exclude,
                                                                     q.ctypes.data if q is not None and q.size else None, min_mapq,
                                                                     out.ctypes.data, selected.ctypes.data,
-                                                                    STORE | (SUPERSET if superset else 0)),
+                                                                    _checks.c_flags(True, superset)),
                    "FLAGSTATS_hip_u16_x64_segments_filter")
     return out, selected
 
@@ -53,13 +51,12 @@ def count_segments_device_ptr_filter(ptr: int, n: int, offsets, require: int = 0
     ptr, n, mapq_ptr = int(ptr), int(n), int(mapq_ptr)
     o = check_offsets(offsets, n)
     nseg = o.size - 1
-    out = np.zeros((nseg, 32), dtype=np.uint64)
-    selected = np.zeros(nseg, dtype=np.uint64)
+    out, selected = _checks.segment_results(nseg, 1)
     if nseg:
         _lib.check(_lib.lib().FLAGSTATS_hip_device_u16_segments_filter_sync(ptr if n else None, n, o.ctypes.data, nseg, require, exclude,
                                                                             mapq_ptr if n and mapq_ptr else None, min_mapq,
                                                                             out.ctypes.data, selected.ctypes.data,
-                                                                            STORE | (SUPERSET if superset else 0)),
+                                                                            _checks.c_flags(True, superset)),
                    "FLAGSTATS_hip_device_u16_segments_filter_sync")
     return out, selected
 
@@ -76,44 +73,17 @@ def count_segments_torch_filter(t, offsets, require: int = 0, exclude: int = 0, 
     both (made zeroed when not given) instead of overwriting them."""
     import torch
 
-    if not isinstance(t, torch.Tensor):
-        raise ValueError("t must be a torch.Tensor, not %s" % type(t).__name__)
-    if t.dtype not in (torch.int16, torch.uint16):
-        raise ValueError("t must have dtype int16 or uint16, not %s" % t.dtype)
-    if t.dim() != 1 or not t.is_contiguous():
-        raise ValueError("t must be 1-D and contiguous")
-    if not (isinstance(offsets, torch.Tensor) and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous()
-            and offsets.numel() >= 1):
-        raise ValueError("offsets must be a 1-D contiguous int64 tensor (nseg + 1 values)")
-    if mapq is not None:
-        if not isinstance(mapq, torch.Tensor):
-            raise ValueError("mapq must be a torch.Tensor, not %s" % type(mapq).__name__)
-        if mapq.dtype != torch.uint8:
-            raise ValueError("mapq must have dtype torch.uint8, not %s" % mapq.dtype)
-        if mapq.dim() != 1 or not mapq.is_contiguous():
-            raise ValueError("mapq must be 1-D and contiguous")
-        if mapq.numel() != t.numel():
-            raise ValueError("mapq must have one element per value (%d), not %d" % (t.numel(), mapq.numel()))
+    _checks.check_u16_tensor(t)
+    nseg = _checks.check_offsets_tensor(offsets)
+    _check_mapq_torch(mapq, t.numel())
     require, exclude, min_mapq = _check_predicate(require, exclude, min_mapq, mapq is not None)
-    nseg = offsets.numel() - 1
-    for name, x, shape in (("out", out, (nseg, 32)), ("selected", selected, (nseg,))):
-        if x is not None and not (isinstance(x, torch.Tensor) and x.dtype == torch.int64 and tuple(x.shape) == shape and x.is_contiguous()):
-            raise ValueError("%s must be a contiguous int64 tensor of shape %s" % (name, shape))
-    if not t.is_cuda:
-        raise ValueError("t must be a CUDA tensor")
-    for name, x in (("offsets", offsets), ("mapq", mapq), ("out", out), ("selected", selected)):
-        if x is not None and x.device != t.device:
-            raise ValueError("%s must live on t's device (%s), not on %s" % (name, t.device, x.device))
-    make = torch.empty if store else torch.zeros
-    if out is None:
-        out = make((nseg, 32), dtype=torch.int64, device=t.device)
-    if selected is None:
-        selected = make((nseg,), dtype=torch.int64, device=t.device)
+    out, selected = _checks.place_result_rows(t, nseg, store, (("out", out), ("selected", selected)),
+                                            others=(("offsets", offsets), ("mapq", mapq)))
     lib = _lib.lib()
     with torch.cuda.device(t.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
         n = t.numel()
-        flags = (STORE if store else 0) | (SUPERSET if superset else 0)
+        flags = _checks.c_flags(store, superset)
         _lib.check(lib.FLAGSTATS_hip_device_u16_segments_filter(t.data_ptr() if n else None, n, offsets.data_ptr(), nseg, require, exclude,
                                                                 mapq.data_ptr() if mapq is not None and n else None, min_mapq,
                                                                 out.data_ptr(), selected.data_ptr(), flags, stream),

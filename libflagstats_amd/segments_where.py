@@ -14,14 +14,11 @@ from __future__ import annotations
 
 import ctypes
 
-import numpy as np
-
 from . import _checks, _lib
+from ._checks import STORE, SUPERSET  # noqa: F401  (kept as this module's names)
 from .segments import check_offsets
 from .segments_filter import segment_filter_dicts
 from .where import _check_numpy, _check_torch
-
-STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
 
 
 def counters_segments_where(values, offsets, where, packed: bool = False, bit_offset: int = 0, superset: bool = False):
@@ -31,13 +28,12 @@ def counters_segments_where(values, offsets, where, packed: bool = False, bit_of
     v, w, bit_offset = _check_numpy(values, where, packed, bit_offset)
     o = check_offsets(offsets, v.size)
     nseg = o.size - 1
-    out = np.zeros((nseg, 32), dtype=np.uint64)
-    selected = np.zeros(nseg, dtype=np.uint64)
+    out, selected = _checks.segment_results(nseg, 1)
     if nseg:
         _lib.check(_lib.lib().FLAGSTATS_hip_u16_x64_segments_where(v.ctypes.data if v.size else None, v.size, o.ctypes.data, nseg,
                                                                    w.ctypes.data if v.size else None, bit_offset, 1 if packed else 8,
                                                                    out.ctypes.data, selected.ctypes.data,
-                                                                   STORE | (SUPERSET if superset else 0)),
+                                                                   _checks.c_flags(True, superset)),
                    "FLAGSTATS_hip_u16_x64_segments_where")
     return out, selected
 
@@ -58,13 +54,12 @@ def count_segments_device_ptr_where(ptr: int, n: int, offsets, sel_ptr: int, sel
     ptr, n, sel_ptr, sel_offset = int(ptr), int(n), int(sel_ptr), int(sel_offset)
     o = check_offsets(offsets, n)
     nseg = o.size - 1
-    out = np.zeros((nseg, 32), dtype=np.uint64)
-    selected = np.zeros(nseg, dtype=np.uint64)
+    out, selected = _checks.segment_results(nseg, 1)
     if nseg:
         _lib.check(_lib.lib().FLAGSTATS_hip_device_u16_segments_where_sync(ptr if n else None, n, o.ctypes.data, nseg,
                                                                            sel_ptr if n else None, sel_offset, sel_bits,
                                                                            out.ctypes.data, selected.ctypes.data,
-                                                                           STORE | (SUPERSET if superset else 0)),
+                                                                           _checks.c_flags(True, superset)),
                    "FLAGSTATS_hip_device_u16_segments_where_sync")
     return out, selected
 
@@ -82,28 +77,14 @@ def count_segments_torch_where(t, offsets, where, packed: bool = False, bit_offs
     import torch
 
     bit_offset = _check_torch(t, where, packed, bit_offset)
-    if not (isinstance(offsets, torch.Tensor) and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous()
-            and offsets.numel() >= 1):
-        raise ValueError("offsets must be a 1-D contiguous int64 tensor (nseg + 1 values)")
-    nseg = offsets.numel() - 1
-    for name, x, shape in (("out", out, (nseg, 32)), ("selected", selected, (nseg,))):
-        if x is not None and not (isinstance(x, torch.Tensor) and x.dtype == torch.int64 and tuple(x.shape) == shape and x.is_contiguous()):
-            raise ValueError("%s must be a contiguous int64 tensor of shape %s" % (name, shape))
-    if not t.is_cuda:
-        raise ValueError("t must be a CUDA tensor")
-    for name, x in (("offsets", offsets), ("where", where), ("out", out), ("selected", selected)):
-        if x is not None and x.device != t.device:
-            raise ValueError("%s must live on t's device (%s), not on %s" % (name, t.device, x.device))
-    make = torch.empty if store else torch.zeros
-    if out is None:
-        out = make((nseg, 32), dtype=torch.int64, device=t.device)
-    if selected is None:
-        selected = make((nseg,), dtype=torch.int64, device=t.device)
+    nseg = _checks.check_offsets_tensor(offsets)
+    out, selected = _checks.place_result_rows(t, nseg, store, (("out", out), ("selected", selected)),
+                                            others=(("offsets", offsets), ("where", where)))
     lib = _lib.lib()
     with torch.cuda.device(t.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
         n = t.numel()
-        flags = (STORE if store else 0) | (SUPERSET if superset else 0)
+        flags = _checks.c_flags(store, superset)
         _lib.check(lib.FLAGSTATS_hip_device_u16_segments_where(t.data_ptr() if n else None, n, offsets.data_ptr(), nseg,
                                                                where.data_ptr() if n else None, bit_offset, 1 if packed else 8,
                                                                out.data_ptr(), selected.data_ptr(), flags, stream),

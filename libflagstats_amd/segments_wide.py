@@ -14,10 +14,9 @@ import ctypes
 import numpy as np
 
 from . import _checks, _lib
+from ._checks import STORE, SUPERSET  # noqa: F401  (kept as this module's names)
 from .segments import check_offsets, count_segments_torch
 from .wide import _check_tensor, _check_values, high_bits_message
-
-STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
 
 
 def counters_segments_ints(values, offsets, superset: bool = False):
@@ -27,11 +26,10 @@ def counters_segments_ints(values, offsets, superset: bool = False):
     v = _check_values(values)
     o = check_offsets(offsets, v.size)
     nseg = o.size - 1
-    out = np.zeros((nseg, 32), dtype=np.uint64)
-    high = np.zeros(nseg, dtype=np.uint64)
+    out, high = _checks.segment_results(nseg, 1)
     if not nseg:
         return out, high
-    flags = STORE | (SUPERSET if superset else 0)
+    flags = _checks.c_flags(True, superset)
     lib = _lib.lib()
     ptr = v.ctypes.data if v.size else None
     if v.dtype.itemsize == 2:
@@ -64,18 +62,16 @@ def flagstats_segments_ints(values, offsets, superset: bool = False, strict: boo
 def count_segments_device_ptr_ints(ptr: int, n: int, elem_bytes: int, offsets, superset: bool = False):
     """``(uint64[nseg, 32], uint64[nseg] high)`` of the segments of a device array of ``n`` 4-byte or 8-byte integers given as a
     raw pointer; host offsets; synchronous (``FLAGSTATS_hip_device_wide_segments_sync``)."""
-    if elem_bytes not in (4, 8):
-        raise ValueError("elem_bytes must be 4 or 8 (16-bit arrays: segments.count_segments_device_ptr), not %r" % (elem_bytes,))
+    _checks.check_elem_bytes(elem_bytes, "segments.count_segments_device_ptr")
     _checks.check_raw_ints((("ptr", ptr), ("n", n)))
     ptr, n = int(ptr), int(n)
     o = check_offsets(offsets, n)
     nseg = o.size - 1
-    out = np.zeros((nseg, 32), dtype=np.uint64)
-    high = np.zeros(nseg, dtype=np.uint64)
+    out, high = _checks.segment_results(nseg, 1)
     if nseg:
         _lib.check(_lib.lib().FLAGSTATS_hip_device_wide_segments_sync(ptr if n else None, n, elem_bytes, o.ctypes.data, nseg,
                                                                       out.ctypes.data, high.ctypes.data,
-                                                                      STORE | (SUPERSET if superset else 0)),
+                                                                      _checks.c_flags(True, superset)),
                    "FLAGSTATS_hip_device_wide_segments_sync")
     return out, high
 
@@ -93,23 +89,9 @@ def count_segments_torch_ints(t, offsets, out=None, high=None, store: bool = Tru
     import torch
 
     _check_tensor(t)
-    if not (isinstance(offsets, torch.Tensor) and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous()
-            and offsets.numel() >= 1):
-        raise ValueError("offsets must be a 1-D contiguous int64 tensor (nseg + 1 values)")
-    nseg = offsets.numel() - 1
-    for name, x, shape in (("out", out, (nseg, 32)), ("high", high, (nseg,))):
-        if x is not None and not (isinstance(x, torch.Tensor) and x.dtype == torch.int64 and tuple(x.shape) == shape and x.is_contiguous()):
-            raise ValueError("%s must be a contiguous int64 tensor of shape %s" % (name, shape))
-    if not t.is_cuda:
-        raise ValueError("t must be a CUDA tensor")
-    for name, x in (("offsets", offsets), ("out", out), ("high", high)):
-        if x is not None and x.device != t.device:
-            raise ValueError("%s must live on t's device (%s), not on %s" % (name, t.device, x.device))
-    make = torch.empty if store else torch.zeros
-    if out is None:
-        out = make((nseg, 32), dtype=torch.int64, device=t.device)
-    if high is None:
-        high = make((nseg,), dtype=torch.int64, device=t.device)
+    nseg = _checks.check_offsets_tensor(offsets)
+    out, high = _checks.place_result_rows(t, nseg, store, (("out", out), ("high", high)),
+                                        others=(("offsets", offsets),))
     with torch.cuda.device(t.device):
         if t.element_size() == 2:
             if store:
@@ -118,7 +100,7 @@ def count_segments_torch_ints(t, offsets, out=None, high=None, store: bool = Tru
             return out, high
         stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
         n = t.numel()
-        flags = (STORE if store else 0) | (SUPERSET if superset else 0)
+        flags = _checks.c_flags(store, superset)
         _lib.check(_lib.lib().FLAGSTATS_hip_device_wide_segments(t.data_ptr() if n else None, n, t.element_size(), offsets.data_ptr(),
                                                                  nseg, out.data_ptr(), high.data_ptr(), flags, stream),
                    "FLAGSTATS_hip_device_wide_segments")

@@ -16,13 +16,12 @@ import ctypes
 import numpy as np
 
 from . import _checks, _lib
+from ._checks import STORE, SUPERSET  # noqa: F401  (kept as this module's names)
 from .filter import _check_mapq_numpy, _check_mapq_torch, _check_predicate
 from .segments import check_offsets
 from .segments_filter import count_segments_torch_filter
 from .segments_wide import strict_message
 from .wide import _check_tensor, _check_values
-
-STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
 
 
 def counters_segments_ints_filter(values, offsets, require: int = 0, exclude: int = 0, mapq=None, min_mapq: int = 0,
@@ -36,12 +35,10 @@ def counters_segments_ints_filter(values, offsets, require: int = 0, exclude: in
     require, exclude, min_mapq = _check_predicate(require, exclude, min_mapq, q is not None)
     o = check_offsets(offsets, v.size)
     nseg = o.size - 1
-    out = np.zeros((nseg, 32), dtype=np.uint64)
-    selected = np.zeros(nseg, dtype=np.uint64)
-    high = np.zeros(nseg, dtype=np.uint64)
+    out, selected, high = _checks.segment_results(nseg, 2)
     if not nseg:
         return out, selected, high
-    flags = STORE | (SUPERSET if superset else 0)
+    flags = _checks.c_flags(True, superset)
     lib = _lib.lib()
     ptr = v.ctypes.data if v.size else None
     qptr = q.ctypes.data if q is not None and q.size else None
@@ -74,22 +71,18 @@ def count_segments_device_ptr_ints_filter(ptr: int, n: int, elem_bytes: int, off
     """``(uint64[nseg, 32], uint64[nseg] selected, uint64[nseg] high)`` of the segments of a device array of ``n`` 4-byte or
     8-byte integers under the filter, array and MAPQ column (``n`` bytes; ``mapq_ptr`` 0: none) given as raw pointers; host
     offsets; synchronous (``FLAGSTATS_hip_device_wide_segments_filter_sync``)."""
-    if elem_bytes not in (4, 8):
-        raise ValueError("elem_bytes must be 4 or 8 (16-bit arrays: segments_filter.count_segments_device_ptr_filter), not %r"
-                         % (elem_bytes,))
+    _checks.check_elem_bytes(elem_bytes, "segments_filter.count_segments_device_ptr_filter")
     _checks.check_raw_ints((("ptr", ptr), ("n", n), ("mapq_ptr", mapq_ptr)))
     require, exclude, min_mapq = _check_predicate(require, exclude, min_mapq, mapq_ptr != 0)
     ptr, n, mapq_ptr = int(ptr), int(n), int(mapq_ptr)
     o = check_offsets(offsets, n)
     nseg = o.size - 1
-    out = np.zeros((nseg, 32), dtype=np.uint64)
-    selected = np.zeros(nseg, dtype=np.uint64)
-    high = np.zeros(nseg, dtype=np.uint64)
+    out, selected, high = _checks.segment_results(nseg, 2)
     if nseg:
         _lib.check(_lib.lib().FLAGSTATS_hip_device_wide_segments_filter_sync(ptr if n else None, n, elem_bytes, o.ctypes.data, nseg,
                                                                              require, exclude, mapq_ptr if n and mapq_ptr else None,
                                                                              min_mapq, out.ctypes.data, selected.ctypes.data,
-                                                                             high.ctypes.data, STORE | (SUPERSET if superset else 0)),
+                                                                             high.ctypes.data, _checks.c_flags(True, superset)),
                    "FLAGSTATS_hip_device_wide_segments_filter_sync")
     return out, selected, high
 
@@ -110,27 +103,11 @@ def count_segments_torch_ints_filter(t, offsets, require: int = 0, exclude: int 
     import torch
 
     _check_tensor(t)
-    if not (isinstance(offsets, torch.Tensor) and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous()
-            and offsets.numel() >= 1):
-        raise ValueError("offsets must be a 1-D contiguous int64 tensor (nseg + 1 values)")
+    nseg = _checks.check_offsets_tensor(offsets)
     _check_mapq_torch(mapq, t.numel())
     require, exclude, min_mapq = _check_predicate(require, exclude, min_mapq, mapq is not None)
-    nseg = offsets.numel() - 1
-    for name, x, shape in (("out", out, (nseg, 32)), ("selected", selected, (nseg,)), ("high", high, (nseg,))):
-        if x is not None and not (isinstance(x, torch.Tensor) and x.dtype == torch.int64 and tuple(x.shape) == shape and x.is_contiguous()):
-            raise ValueError("%s must be a contiguous int64 tensor of shape %s" % (name, shape))
-    if not t.is_cuda:
-        raise ValueError("t must be a CUDA tensor")
-    for name, x in (("offsets", offsets), ("mapq", mapq), ("out", out), ("selected", selected), ("high", high)):
-        if x is not None and x.device != t.device:
-            raise ValueError("%s must live on t's device (%s), not on %s" % (name, t.device, x.device))
-    make = torch.empty if store else torch.zeros
-    if out is None:
-        out = make((nseg, 32), dtype=torch.int64, device=t.device)
-    if selected is None:
-        selected = make((nseg,), dtype=torch.int64, device=t.device)
-    if high is None:
-        high = make((nseg,), dtype=torch.int64, device=t.device)
+    out, selected, high = _checks.place_result_rows(t, nseg, store, (("out", out), ("selected", selected), ("high", high)),
+                                                  others=(("offsets", offsets), ("mapq", mapq)))
     with torch.cuda.device(t.device):
         if t.element_size() == 2:
             if store:
@@ -140,7 +117,7 @@ def count_segments_torch_ints_filter(t, offsets, require: int = 0, exclude: int 
             return out, selected, high
         stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
         n = t.numel()
-        flags = (STORE if store else 0) | (SUPERSET if superset else 0)
+        flags = _checks.c_flags(store, superset)
         _lib.check(_lib.lib().FLAGSTATS_hip_device_wide_segments_filter(t.data_ptr() if n else None, n, t.element_size(),
                                                                         offsets.data_ptr(), nseg, require, exclude,
                                                                         mapq.data_ptr() if mapq is not None and n else None,

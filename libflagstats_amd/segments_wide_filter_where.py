@@ -20,6 +20,7 @@ import ctypes
 import numpy as np
 
 from . import _checks, _lib
+from ._checks import STORE, SUPERSET  # noqa: F401  (kept as this module's names)
 from .filter import _check_mapq_numpy, _check_mapq_torch, _check_predicate
 from .segments import check_offsets
 from .segments_filter import segment_filter_dicts
@@ -27,8 +28,6 @@ from .segments_filter_where import count_segments_torch_filter_where, counters_s
 from .segments_wide import strict_message
 from .where import _check_sel_bits, _check_selection_numpy, _check_selection_torch
 from .wide import _check_tensor, _check_values
-
-STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
 
 
 def counters_segments_ints_filter_where(values, offsets, where, require: int = 0, exclude: int = 0, mapq=None, min_mapq: int = 0,
@@ -49,16 +48,14 @@ def counters_segments_ints_filter_where(values, offsets, where, require: int = 0
         out, selected = counters_segments_filter_where(v.view(np.uint16), o, w, require=require, exclude=exclude, mapq=q,
                                                        min_mapq=min_mapq, packed=packed, bit_offset=bit_offset, superset=superset)
         return out, selected, np.zeros(nseg, dtype=np.uint64)
-    out = np.zeros((nseg, 32), dtype=np.uint64)
-    selected = np.zeros(nseg, dtype=np.uint64)
-    high = np.zeros(nseg, dtype=np.uint64)
+    out, selected, high = _checks.segment_results(nseg, 2)
     if nseg:
         _lib.check(_lib.lib().FLAGSTATS_hip_wide_x64_segments_filter_where(v.ctypes.data if v.size else None, v.size, v.dtype.itemsize,
                                                                            o.ctypes.data, nseg, require, exclude,
                                                                            q.ctypes.data if q is not None and q.size else None,
                                                                            min_mapq, w.ctypes.data if v.size else None, bit_offset,
                                                                            1 if packed else 8, out.ctypes.data, selected.ctypes.data,
-                                                                           high.ctypes.data, STORE | (SUPERSET if superset else 0)),
+                                                                           high.ctypes.data, _checks.c_flags(True, superset)),
                    "FLAGSTATS_hip_wide_x64_segments_filter_where")
     return out, selected, high
 
@@ -72,13 +69,8 @@ def flagstats_segments_ints_filter_where(values, offsets, where, require: int = 
     extra key ``"high_bits"``."""
     out, selected, high = counters_segments_ints_filter_where(values, offsets, where, require=require, exclude=exclude, mapq=mapq,
                                                               min_mapq=min_mapq, packed=packed, bit_offset=bit_offset)
-    if strict and high.any():
-        raise ValueError(strict_message(high, np.asarray(offsets)))
-    dicts = segment_filter_dicts(out, selected)
-    if not strict:
-        for d, h in zip(dicts, high.tolist()):
-            d["high_bits"] = int(h)
-    return dicts
+    return _checks.with_high_bits(strict, high, lambda: strict_message(high, np.asarray(offsets)),
+                                  lambda: segment_filter_dicts(out, selected))
 
 
 def count_segments_device_ptr_ints_filter_where(ptr: int, n: int, elem_bytes: int, offsets, sel_ptr: int, sel_bits: int,
@@ -89,9 +81,7 @@ def count_segments_device_ptr_ints_filter_where(ptr: int, n: int, elem_bytes: in
     (``mapq_ptr`` 0: none); ``sel_bits`` 1 = LSB-first bitmap, 8 = one byte per element, element ``j`` being bit / byte
     ``sel_offset + j``.  Host offsets.  ``high`` covers the selected elements only.  Synchronous
     (``FLAGSTATS_hip_device_wide_segments_filter_where_sync``)."""
-    if elem_bytes not in (4, 8):
-        raise ValueError("elem_bytes must be 4 or 8 (16-bit arrays: segments_filter_where.count_segments_device_ptr_filter_where), "
-                         "not %r" % (elem_bytes,))
+    _checks.check_elem_bytes(elem_bytes, "segments_filter_where.count_segments_device_ptr_filter_where")
     _check_sel_bits(sel_bits)
     _checks.check_raw_ints((("ptr", ptr), ("n", n), ("sel_ptr", sel_ptr), ("sel_offset", sel_offset), ("mapq_ptr", mapq_ptr)),
                            non_negative=("n", "sel_offset"))
@@ -99,16 +89,14 @@ def count_segments_device_ptr_ints_filter_where(ptr: int, n: int, elem_bytes: in
     ptr, n, sel_ptr, sel_offset, mapq_ptr = int(ptr), int(n), int(sel_ptr), int(sel_offset), int(mapq_ptr)
     o = check_offsets(offsets, n)
     nseg = o.size - 1
-    out = np.zeros((nseg, 32), dtype=np.uint64)
-    selected = np.zeros(nseg, dtype=np.uint64)
-    high = np.zeros(nseg, dtype=np.uint64)
+    out, selected, high = _checks.segment_results(nseg, 2)
     if nseg:
         _lib.check(_lib.lib().FLAGSTATS_hip_device_wide_segments_filter_where_sync(ptr if n else None, n, elem_bytes, o.ctypes.data, nseg,
                                                                                    require, exclude,
                                                                                    mapq_ptr if n and mapq_ptr else None, min_mapq,
                                                                                    sel_ptr if n else None, sel_offset, sel_bits,
                                                                                    out.ctypes.data, selected.ctypes.data, high.ctypes.data,
-                                                                                   STORE | (SUPERSET if superset else 0)),
+                                                                                   _checks.c_flags(True, superset)),
                    "FLAGSTATS_hip_device_wide_segments_filter_where_sync")
     return out, selected, high
 
@@ -136,25 +124,9 @@ def count_segments_torch_ints_filter_where(t, offsets, where, require: int = 0, 
     bit_offset = _check_selection_torch(where, t.numel(), packed, bit_offset)
     _check_mapq_torch(mapq, t.numel())
     require, exclude, min_mapq = _check_predicate(require, exclude, min_mapq, mapq is not None)
-    if not (isinstance(offsets, torch.Tensor) and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous()
-            and offsets.numel() >= 1):
-        raise ValueError("offsets must be a 1-D contiguous int64 tensor (nseg + 1 values)")
-    nseg = offsets.numel() - 1
-    for name, x, shape in (("out", out, (nseg, 32)), ("selected", selected, (nseg,)), ("high", high, (nseg,))):
-        if x is not None and not (isinstance(x, torch.Tensor) and x.dtype == torch.int64 and tuple(x.shape) == shape and x.is_contiguous()):
-            raise ValueError("%s must be a contiguous int64 tensor of shape %s" % (name, shape))
-    if not t.is_cuda:
-        raise ValueError("t must be a CUDA tensor")
-    for name, x in (("offsets", offsets), ("where", where), ("mapq", mapq), ("out", out), ("selected", selected), ("high", high)):
-        if x is not None and x.device != t.device:
-            raise ValueError("%s must live on t's device (%s), not on %s" % (name, t.device, x.device))
-    make = torch.empty if store else torch.zeros
-    if out is None:
-        out = make((nseg, 32), dtype=torch.int64, device=t.device)
-    if selected is None:
-        selected = make((nseg,), dtype=torch.int64, device=t.device)
-    if high is None:
-        high = make((nseg,), dtype=torch.int64, device=t.device)
+    nseg = _checks.check_offsets_tensor(offsets)
+    out, selected, high = _checks.place_result_rows(t, nseg, store, (("out", out), ("selected", selected), ("high", high)),
+                                                  others=(("offsets", offsets), ("where", where), ("mapq", mapq)))
     with torch.cuda.device(t.device):
         if t.element_size() == 2:
             if store:
@@ -165,7 +137,7 @@ def count_segments_torch_ints_filter_where(t, offsets, where, require: int = 0, 
             return out, selected, high
         stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
         n = t.numel()
-        flags = (STORE if store else 0) | (SUPERSET if superset else 0)
+        flags = _checks.c_flags(store, superset)
         _lib.check(_lib.lib().FLAGSTATS_hip_device_wide_segments_filter_where(t.data_ptr() if n else None, n, t.element_size(),
                                                                               offsets.data_ptr(), nseg, require, exclude,
                                                                               mapq.data_ptr() if mapq is not None and n else None,

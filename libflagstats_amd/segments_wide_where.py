@@ -18,14 +18,13 @@ import ctypes
 import numpy as np
 
 from . import _checks, _lib
+from ._checks import STORE, SUPERSET  # noqa: F401  (kept as this module's names)
 from .segments import check_offsets
 from .segments_filter import segment_filter_dicts
 from .segments_where import count_segments_torch_where, counters_segments_where
 from .segments_wide import strict_message
 from .where import _check_sel_bits, _check_selection_numpy, _check_selection_torch
 from .wide import _check_tensor, _check_values
-
-STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
 
 
 def counters_segments_ints_where(values, offsets, where, packed: bool = False, bit_offset: int = 0, superset: bool = False):
@@ -41,15 +40,13 @@ def counters_segments_ints_where(values, offsets, where, packed: bool = False, b
     if v.dtype.itemsize == 2:
         out, selected = counters_segments_where(v.view(np.uint16), o, w, packed=packed, bit_offset=bit_offset, superset=superset)
         return out, selected, np.zeros(nseg, dtype=np.uint64)
-    out = np.zeros((nseg, 32), dtype=np.uint64)
-    selected = np.zeros(nseg, dtype=np.uint64)
-    high = np.zeros(nseg, dtype=np.uint64)
+    out, selected, high = _checks.segment_results(nseg, 2)
     if nseg:
         _lib.check(_lib.lib().FLAGSTATS_hip_wide_x64_segments_where(v.ctypes.data if v.size else None, v.size, v.dtype.itemsize,
                                                                     o.ctypes.data, nseg, w.ctypes.data if v.size else None,
                                                                     bit_offset, 1 if packed else 8, out.ctypes.data,
                                                                     selected.ctypes.data, high.ctypes.data,
-                                                                    STORE | (SUPERSET if superset else 0)),
+                                                                    _checks.c_flags(True, superset)),
                    "FLAGSTATS_hip_wide_x64_segments_where")
     return out, selected, high
 
@@ -61,13 +58,8 @@ def flagstats_segments_ints_where(values, offsets, where, packed: bool = False, 
     not selected never does); ``strict=False``: the dicts of the truncated values, each with its mask as an extra key
     ``"high_bits"``."""
     out, selected, high = counters_segments_ints_where(values, offsets, where, packed=packed, bit_offset=bit_offset)
-    if strict and high.any():
-        raise ValueError(strict_message(high, np.asarray(offsets)))
-    dicts = segment_filter_dicts(out, selected)
-    if not strict:
-        for d, h in zip(dicts, high.tolist()):
-            d["high_bits"] = int(h)
-    return dicts
+    return _checks.with_high_bits(strict, high, lambda: strict_message(high, np.asarray(offsets)),
+                                  lambda: segment_filter_dicts(out, selected))
 
 
 def count_segments_device_ptr_ints_where(ptr: int, n: int, elem_bytes: int, offsets, sel_ptr: int, sel_bits: int, sel_offset: int = 0,
@@ -76,22 +68,18 @@ def count_segments_device_ptr_ints_where(ptr: int, n: int, elem_bytes: int, offs
     8-byte integers under a device selection, both given as raw pointers: ``sel_bits`` 1 = LSB-first bitmap, 8 = one byte per
     element; element ``j`` is bit / byte ``sel_offset + j``.  Host offsets.  ``high`` covers the selected elements only.
     Synchronous (``FLAGSTATS_hip_device_wide_segments_where_sync``)."""
-    if elem_bytes not in (4, 8):
-        raise ValueError("elem_bytes must be 4 or 8 (16-bit arrays: segments_where.count_segments_device_ptr_where), not %r"
-                         % (elem_bytes,))
+    _checks.check_elem_bytes(elem_bytes, "segments_where.count_segments_device_ptr_where")
     _check_sel_bits(sel_bits)
     _checks.check_raw_ints((("ptr", ptr), ("n", n), ("sel_ptr", sel_ptr), ("sel_offset", sel_offset)), non_negative=("n", "sel_offset"))
     ptr, n, sel_ptr, sel_offset = int(ptr), int(n), int(sel_ptr), int(sel_offset)
     o = check_offsets(offsets, n)
     nseg = o.size - 1
-    out = np.zeros((nseg, 32), dtype=np.uint64)
-    selected = np.zeros(nseg, dtype=np.uint64)
-    high = np.zeros(nseg, dtype=np.uint64)
+    out, selected, high = _checks.segment_results(nseg, 2)
     if nseg:
         _lib.check(_lib.lib().FLAGSTATS_hip_device_wide_segments_where_sync(ptr if n else None, n, elem_bytes, o.ctypes.data, nseg,
                                                                             sel_ptr if n else None, sel_offset, sel_bits,
                                                                             out.ctypes.data, selected.ctypes.data, high.ctypes.data,
-                                                                            STORE | (SUPERSET if superset else 0)),
+                                                                            _checks.c_flags(True, superset)),
                    "FLAGSTATS_hip_device_wide_segments_where_sync")
     return out, selected, high
 
@@ -113,25 +101,9 @@ def count_segments_torch_ints_where(t, offsets, where, packed: bool = False, bit
 
     _check_tensor(t)
     bit_offset = _check_selection_torch(where, t.numel(), packed, bit_offset)
-    if not (isinstance(offsets, torch.Tensor) and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous()
-            and offsets.numel() >= 1):
-        raise ValueError("offsets must be a 1-D contiguous int64 tensor (nseg + 1 values)")
-    nseg = offsets.numel() - 1
-    for name, x, shape in (("out", out, (nseg, 32)), ("selected", selected, (nseg,)), ("high", high, (nseg,))):
-        if x is not None and not (isinstance(x, torch.Tensor) and x.dtype == torch.int64 and tuple(x.shape) == shape and x.is_contiguous()):
-            raise ValueError("%s must be a contiguous int64 tensor of shape %s" % (name, shape))
-    if not t.is_cuda:
-        raise ValueError("t must be a CUDA tensor")
-    for name, x in (("offsets", offsets), ("where", where), ("out", out), ("selected", selected), ("high", high)):
-        if x is not None and x.device != t.device:
-            raise ValueError("%s must live on t's device (%s), not on %s" % (name, t.device, x.device))
-    make = torch.empty if store else torch.zeros
-    if out is None:
-        out = make((nseg, 32), dtype=torch.int64, device=t.device)
-    if selected is None:
-        selected = make((nseg,), dtype=torch.int64, device=t.device)
-    if high is None:
-        high = make((nseg,), dtype=torch.int64, device=t.device)
+    nseg = _checks.check_offsets_tensor(offsets)
+    out, selected, high = _checks.place_result_rows(t, nseg, store, (("out", out), ("selected", selected), ("high", high)),
+                                                  others=(("offsets", offsets), ("where", where)))
     with torch.cuda.device(t.device):
         if t.element_size() == 2:
             if store:
@@ -141,7 +113,7 @@ def count_segments_torch_ints_where(t, offsets, where, packed: bool = False, bit
             return out, selected, high
         stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
         n = t.numel()
-        flags = (STORE if store else 0) | (SUPERSET if superset else 0)
+        flags = _checks.c_flags(store, superset)
         _lib.check(_lib.lib().FLAGSTATS_hip_device_wide_segments_where(t.data_ptr() if n else None, n, t.element_size(),
                                                                        offsets.data_ptr(), nseg, where.data_ptr() if n else None,
                                                                        bit_offset, 1 if packed else 8, out.data_ptr(),

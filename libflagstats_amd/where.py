@@ -13,9 +13,8 @@ import ctypes
 import numpy as np
 
 from . import _checks, _lib
+from ._checks import STORE, SUPERSET  # noqa: F401  (kept as this module's names)
 from .pyflagstats import _as_dict
-
-STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
 
 
 def _check_bit_offset(packed, bit_offset) -> int:
@@ -88,14 +87,7 @@ def _check_selection_torch(where, n: int, packed, bit_offset) -> int:
 
 def _check_torch(t, where, packed, bit_offset) -> int:
     """the tensor and its selection as the torch entries take them (devices are checked by the caller); the bit offset"""
-    import torch
-
-    if not isinstance(t, torch.Tensor):
-        raise ValueError("t must be a torch.Tensor, not %s" % type(t).__name__)
-    if t.dtype not in (torch.int16, torch.uint16):
-        raise ValueError("t must have dtype int16 or uint16, not %s" % t.dtype)
-    if t.dim() != 1 or not t.is_contiguous():
-        raise ValueError("t must be 1-D and contiguous")
+    _checks.check_u16_tensor(t)
     return _check_selection_torch(where, t.numel(), packed, bit_offset)
 
 
@@ -114,7 +106,7 @@ def counters_where(values, where, packed: bool = False, bit_offset: int = 0, sup
     selected = ctypes.c_uint64(0)
     _lib.check(_lib.lib().FLAGSTATS_hip_u16_x64_where(v.ctypes.data if v.size else None, v.size, w.ctypes.data if v.size else None,
                                                       bit_offset, 1 if packed else 8, out.ctypes.data, ctypes.byref(selected),
-                                                      STORE | (SUPERSET if superset else 0)), "FLAGSTATS_hip_u16_x64_where")
+                                                      _checks.c_flags(True, superset)), "FLAGSTATS_hip_u16_x64_where")
     return out, int(selected.value)
 
 
@@ -136,7 +128,7 @@ def count_device_ptr_where(ptr: int, n: int, sel_ptr: int, sel_bits: int, sel_of
     selected = ctypes.c_uint64(0)
     _lib.check(_lib.lib().FLAGSTATS_hip_device_u16_where_sync(ptr if n else None, n, sel_ptr if n else None, sel_offset, sel_bits,
                                                               out.ctypes.data, ctypes.byref(selected),
-                                                              STORE | (SUPERSET if superset else 0)), "FLAGSTATS_hip_device_u16_where_sync")
+                                                              _checks.c_flags(True, superset)), "FLAGSTATS_hip_device_u16_where_sync")
     return out, int(selected.value)
 
 
@@ -157,7 +149,7 @@ def count_torch_where(t, where, out=None, selected=None, store: bool = False, su
     with torch.cuda.device(t.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
         n = t.numel()
-        flags = (STORE if store else 0) | (SUPERSET if superset else 0)
+        flags = _checks.c_flags(store, superset)
         _lib.check(lib.FLAGSTATS_hip_device_u16_where(t.data_ptr() if n else None, n, where.data_ptr() if n else None, bit_offset,
                                                       1 if packed else 8, out.data_ptr(), selected.data_ptr(), flags, stream),
                    "FLAGSTATS_hip_device_u16_where")

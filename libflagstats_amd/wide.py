@@ -14,9 +14,9 @@ import ctypes
 import numpy as np
 
 from . import _checks, _lib
+from ._checks import STORE, SUPERSET  # noqa: F401  (kept as this module's names)
 from .pyflagstats import _as_dict
 
-STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
 INT_DTYPES = ("int16", "uint16", "int32", "uint32", "int64", "uint64")
 
 
@@ -60,7 +60,7 @@ def counters_ints(values, superset: bool = False):
         return out, 0
     high = ctypes.c_uint64(0)
     _lib.check(lib.FLAGSTATS_hip_wide_x64(v.ctypes.data if v.size else None, v.size, v.dtype.itemsize, out.ctypes.data,
-                                          ctypes.byref(high), STORE | (SUPERSET if superset else 0)), "FLAGSTATS_hip_wide_x64")
+                                          ctypes.byref(high), _checks.c_flags(True, superset)), "FLAGSTATS_hip_wide_x64")
     return out, int(high.value)
 
 
@@ -69,25 +69,19 @@ def flagstats_ints(values, strict: bool = True) -> dict:
     outside 0..65535 raises ``ValueError`` naming the bits seen above bit 15; ``strict=False``: the dict of the truncated values
     with the mask as an extra key ``"high_bits"``."""
     counters, high = counters_ints(values)
-    if strict and high:
-        raise ValueError(high_bits_message(high))
-    ret = _as_dict(counters, len(values))
-    if not strict:
-        ret["high_bits"] = high
-    return ret
+    return _checks.with_high_bits(strict, high, lambda: high_bits_message(high), lambda: _as_dict(counters, len(values)))
 
 
 def count_device_ptr_ints(ptr: int, n: int, elem_bytes: int, superset: bool = False):
     """``(uint64[32], int high)`` of a device array of ``n`` 4-byte or 8-byte integers given as a raw pointer; synchronous
     (``FLAGSTATS_hip_device_wide_sync``)."""
-    if elem_bytes not in (4, 8):
-        raise ValueError("elem_bytes must be 4 or 8 (16-bit arrays: device.count_device_ptr), not %r" % (elem_bytes,))
+    _checks.check_elem_bytes(elem_bytes, "device.count_device_ptr")
     if n < 0:
         raise ValueError("n must not be negative")
     out = np.zeros(32, dtype=np.uint64)
     high = ctypes.c_uint64(0)
     _lib.check(_lib.lib().FLAGSTATS_hip_device_wide_sync(ptr if n else None, n, elem_bytes, out.ctypes.data, ctypes.byref(high),
-                                                         STORE | (SUPERSET if superset else 0)), "FLAGSTATS_hip_device_wide_sync")
+                                                         _checks.c_flags(True, superset)), "FLAGSTATS_hip_device_wide_sync")
     return out, int(high.value)
 
 
@@ -119,7 +113,7 @@ def count_torch_ints(t, out=None, high=None, store: bool = False, superset: bool
                     "FLAGSTATS_hip_device_u16_store" if store else "FLAGSTATS_hip_device_u16")
             _lib.check(getattr(lib, name)(ptr, t.numel(), out.data_ptr(), stream), name)
         else:
-            flags = (STORE if store else 0) | (SUPERSET if superset else 0)
+            flags = _checks.c_flags(store, superset)
             _lib.check(lib.FLAGSTATS_hip_device_wide(ptr, t.numel(), t.element_size(), out.data_ptr(), high.data_ptr(), flags, stream),
                        "FLAGSTATS_hip_device_wide")
     return out, high

@@ -14,11 +14,10 @@ import ctypes
 import numpy as np
 
 from . import _checks, _lib
+from ._checks import STORE, SUPERSET  # noqa: F401  (kept as this module's names)
 from . import filter as _filter
 from . import wide as _wide
 from .pyflagstats import _as_dict
-
-STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
 
 
 def counters_ints_filter(values, require: int = 0, exclude: int = 0, mapq=None, min_mapq: int = 0, superset: bool = False):
@@ -37,7 +36,7 @@ def counters_ints_filter(values, require: int = 0, exclude: int = 0, mapq=None, 
     _lib.check(_lib.lib().FLAGSTATS_hip_wide_x64_filter(v.ctypes.data if v.size else None, v.size, v.dtype.itemsize, require, exclude,
                                                         q.ctypes.data if q is not None and q.size else None, min_mapq,
                                                         out.ctypes.data, ctypes.byref(selected), ctypes.byref(high),
-                                                        STORE | (SUPERSET if superset else 0)), "FLAGSTATS_hip_wide_x64_filter")
+                                                        _checks.c_flags(True, superset)), "FLAGSTATS_hip_wide_x64_filter")
     return out, int(selected.value), int(high.value)
 
 
@@ -47,12 +46,7 @@ def flagstats_ints_filter(values, require: int = 0, exclude: int = 0, mapq=None,
     ``ValueError`` naming the bits seen above bit 15; ``strict=False``: the dict of the truncated values with the mask as an
     extra key ``"high_bits"``."""
     counters, selected, high = counters_ints_filter(values, require=require, exclude=exclude, mapq=mapq, min_mapq=min_mapq)
-    if strict and high:
-        raise ValueError(_wide.high_bits_message(high))
-    ret = _as_dict(counters, selected)
-    if not strict:
-        ret["high_bits"] = high
-    return ret
+    return _checks.with_high_bits(strict, high, lambda: _wide.high_bits_message(high), lambda: _as_dict(counters, selected))
 
 
 def count_device_ptr_ints_filter(ptr: int, n: int, elem_bytes: int, require: int = 0, exclude: int = 0, mapq_ptr: int = 0,
@@ -60,8 +54,7 @@ def count_device_ptr_ints_filter(ptr: int, n: int, elem_bytes: int, require: int
     """``(uint64[32], int selected, int high)`` of a device array of ``n`` 4-byte or 8-byte integers under the filter, array and
     MAPQ column (``n`` bytes; ``mapq_ptr`` 0: none) given as raw pointers.  Synchronous
     (``FLAGSTATS_hip_device_wide_filter_sync``)."""
-    if elem_bytes not in (4, 8):
-        raise ValueError("elem_bytes must be 4 or 8 (16-bit arrays: filter.count_device_ptr_filter), not %r" % (elem_bytes,))
+    _checks.check_elem_bytes(elem_bytes, "filter.count_device_ptr_filter")
     _checks.check_raw_ints((("ptr", ptr), ("n", n), ("mapq_ptr", mapq_ptr)))
     require, exclude, min_mapq = _filter._check_predicate(require, exclude, min_mapq, mapq_ptr != 0)
     ptr, n, mapq_ptr = int(ptr), int(n), int(mapq_ptr)
@@ -70,7 +63,7 @@ def count_device_ptr_ints_filter(ptr: int, n: int, elem_bytes: int, require: int
     _lib.check(_lib.lib().FLAGSTATS_hip_device_wide_filter_sync(ptr if n else None, n, elem_bytes, require, exclude,
                                                                 mapq_ptr if n and mapq_ptr else None, min_mapq, out.ctypes.data,
                                                                 ctypes.byref(selected), ctypes.byref(high),
-                                                                STORE | (SUPERSET if superset else 0)),
+                                                                _checks.c_flags(True, superset)),
                "FLAGSTATS_hip_device_wide_filter_sync")
     return out, int(selected.value), int(high.value)
 
@@ -90,11 +83,7 @@ def count_torch_ints_filter(t, require: int = 0, exclude: int = 0, mapq=None, mi
     _wide._check_tensor(t)
     _filter._check_mapq_torch(mapq, t.numel())
     require, exclude, min_mapq = _filter._check_predicate(require, exclude, min_mapq, mapq is not None)
-    _checks.check_result_pair(out, "selected", selected)
-    _checks.check_result_pair(None, "high", high)
-    out, selected = _checks.place_result_pair(t, out, "selected", selected, others=(("mapq", mapq), ("high", high)))
-    if high is None:
-        high = torch.zeros(1, dtype=torch.int64, device=t.device)
+    out, selected, high = _checks.place_result_triple(t, out, selected, high, others=(("mapq", mapq),))
     if t.element_size() == 2:
         if store:
             with torch.cuda.device(t.device):
@@ -106,7 +95,7 @@ def count_torch_ints_filter(t, require: int = 0, exclude: int = 0, mapq=None, mi
     with torch.cuda.device(t.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
         n = t.numel()
-        flags = (STORE if store else 0) | (SUPERSET if superset else 0)
+        flags = _checks.c_flags(store, superset)
         _lib.check(lib.FLAGSTATS_hip_device_wide_filter(t.data_ptr() if n else None, n, t.element_size(), require, exclude,
                                                         mapq.data_ptr() if mapq is not None and n else None, min_mapq, out.data_ptr(),
                                                         selected.data_ptr(), high.data_ptr(), flags, stream),

@@ -18,13 +18,12 @@ import ctypes
 import numpy as np
 
 from . import _checks, _lib
+from ._checks import STORE, SUPERSET  # noqa: F401  (kept as this module's names)
 from . import filter as _filter
 from . import filter_where as _filter_where
 from . import where as _where
 from . import wide as _wide
 from .pyflagstats import _as_dict
-
-STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
 
 
 def counters_ints_filter_where(values, where, require: int = 0, exclude: int = 0, mapq=None, min_mapq: int = 0, packed: bool = False,
@@ -49,7 +48,7 @@ def counters_ints_filter_where(values, where, require: int = 0, exclude: int = 0
                                                               exclude, q.ctypes.data if q is not None and q.size else None, min_mapq,
                                                               w.ctypes.data if v.size else None, bit_offset, 1 if packed else 8,
                                                               out.ctypes.data, ctypes.byref(selected), ctypes.byref(high),
-                                                              STORE | (SUPERSET if superset else 0)),
+                                                              _checks.c_flags(True, superset)),
                "FLAGSTATS_hip_wide_x64_filter_where")
     return out, int(selected.value), int(high.value)
 
@@ -62,12 +61,7 @@ def flagstats_ints_filter_where(values, where, require: int = 0, exclude: int = 
     mask as an extra key ``"high_bits"``."""
     counters, selected, high = counters_ints_filter_where(values, where, require=require, exclude=exclude, mapq=mapq, min_mapq=min_mapq,
                                                           packed=packed, bit_offset=bit_offset)
-    if strict and high:
-        raise ValueError(_wide.high_bits_message(high))
-    ret = _as_dict(counters, selected)
-    if not strict:
-        ret["high_bits"] = high
-    return ret
+    return _checks.with_high_bits(strict, high, lambda: _wide.high_bits_message(high), lambda: _as_dict(counters, selected))
 
 
 def count_device_ptr_ints_filter_where(ptr: int, n: int, elem_bytes: int, sel_ptr: int, sel_bits: int, require: int = 0, exclude: int = 0,
@@ -76,8 +70,7 @@ def count_device_ptr_ints_filter_where(ptr: int, n: int, elem_bytes: int, sel_pt
     device selection, all given as raw pointers: the MAPQ column has ``n`` bytes (``mapq_ptr`` 0: none); ``sel_bits`` 1 =
     LSB-first bitmap, 8 = one byte per element, element ``i`` being bit / byte ``sel_offset + i``.  ``high`` covers the selected
     elements, passing or not.  Synchronous (``FLAGSTATS_hip_device_wide_filter_where_sync``)."""
-    if elem_bytes not in (4, 8):
-        raise ValueError("elem_bytes must be 4 or 8 (16-bit arrays: filter_where.count_device_ptr_filter_where), not %r" % (elem_bytes,))
+    _checks.check_elem_bytes(elem_bytes, "filter_where.count_device_ptr_filter_where")
     _where._check_sel_bits(sel_bits)
     _checks.check_raw_ints((("ptr", ptr), ("n", n), ("sel_ptr", sel_ptr), ("sel_offset", sel_offset), ("mapq_ptr", mapq_ptr)),
                            non_negative=("n", "sel_offset"))
@@ -89,7 +82,7 @@ def count_device_ptr_ints_filter_where(ptr: int, n: int, elem_bytes: int, sel_pt
                                                                       mapq_ptr if n and mapq_ptr else None, min_mapq,
                                                                       sel_ptr if n else None, sel_offset, sel_bits, out.ctypes.data,
                                                                       ctypes.byref(selected), ctypes.byref(high),
-                                                                      STORE | (SUPERSET if superset else 0)),
+                                                                      _checks.c_flags(True, superset)),
                "FLAGSTATS_hip_device_wide_filter_where_sync")
     return out, int(selected.value), int(high.value)
 
@@ -113,11 +106,7 @@ def count_torch_ints_filter_where(t, where, require: int = 0, exclude: int = 0, 
     bit_offset = _where._check_selection_torch(where, t.numel(), packed, bit_offset)
     _filter._check_mapq_torch(mapq, t.numel())
     require, exclude, min_mapq = _filter._check_predicate(require, exclude, min_mapq, mapq is not None)
-    _checks.check_result_pair(out, "selected", selected)
-    _checks.check_result_pair(None, "high", high)
-    out, selected = _checks.place_result_pair(t, out, "selected", selected, others=(("where", where), ("mapq", mapq), ("high", high)))
-    if high is None:
-        high = torch.zeros(1, dtype=torch.int64, device=t.device)
+    out, selected, high = _checks.place_result_triple(t, out, selected, high, others=(("where", where), ("mapq", mapq)))
     if t.element_size() == 2:
         if store:
             with torch.cuda.device(t.device):
@@ -129,7 +118,7 @@ def count_torch_ints_filter_where(t, where, require: int = 0, exclude: int = 0, 
     with torch.cuda.device(t.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
         n = t.numel()
-        flags = (STORE if store else 0) | (SUPERSET if superset else 0)
+        flags = _checks.c_flags(store, superset)
         _lib.check(lib.FLAGSTATS_hip_device_wide_filter_where(t.data_ptr() if n else None, n, t.element_size(), require, exclude,
                                                               mapq.data_ptr() if mapq is not None and n else None, min_mapq,
                                                               where.data_ptr() if n else None, bit_offset, 1 if packed else 8,

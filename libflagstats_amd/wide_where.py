@@ -16,11 +16,10 @@ import ctypes
 import numpy as np
 
 from . import _checks, _lib
+from ._checks import STORE, SUPERSET  # noqa: F401  (kept as this module's names)
 from . import where as _where
 from . import wide as _wide
 from .pyflagstats import _as_dict
-
-STORE, SUPERSET = 1, 2   # the C entry points' `flags` bits
 
 
 def counters_ints_where(values, where, packed: bool = False, bit_offset: int = 0, superset: bool = False):
@@ -39,7 +38,7 @@ def counters_ints_where(values, where, packed: bool = False, bit_offset: int = 0
     _lib.check(_lib.lib().FLAGSTATS_hip_wide_x64_where(v.ctypes.data if v.size else None, v.size, v.dtype.itemsize,
                                                        w.ctypes.data if v.size else None, bit_offset, 1 if packed else 8,
                                                        out.ctypes.data, ctypes.byref(selected), ctypes.byref(high),
-                                                       STORE | (SUPERSET if superset else 0)), "FLAGSTATS_hip_wide_x64_where")
+                                                       _checks.c_flags(True, superset)), "FLAGSTATS_hip_wide_x64_where")
     return out, int(selected.value), int(high.value)
 
 
@@ -49,12 +48,7 @@ def flagstats_ints_where(values, where, packed: bool = False, bit_offset: int = 
     bit 15 (a value that is not selected never does); ``strict=False``: the dict of the truncated values with the mask as an
     extra key ``"high_bits"``."""
     counters, selected, high = counters_ints_where(values, where, packed=packed, bit_offset=bit_offset)
-    if strict and high:
-        raise ValueError(_wide.high_bits_message(high))
-    ret = _as_dict(counters, selected)
-    if not strict:
-        ret["high_bits"] = high
-    return ret
+    return _checks.with_high_bits(strict, high, lambda: _wide.high_bits_message(high), lambda: _as_dict(counters, selected))
 
 
 def count_device_ptr_ints_where(ptr: int, n: int, elem_bytes: int, sel_ptr: int, sel_bits: int, sel_offset: int = 0,
@@ -62,8 +56,7 @@ def count_device_ptr_ints_where(ptr: int, n: int, elem_bytes: int, sel_ptr: int,
     """``(uint64[32], int selected, int high)`` of a device array of ``n`` 4-byte or 8-byte integers under a device selection,
     both given as raw pointers: ``sel_bits`` 1 = LSB-first bitmap, 8 = one byte per element; element ``i`` is bit / byte
     ``sel_offset + i``.  ``high`` covers the selected elements only.  Synchronous (``FLAGSTATS_hip_device_wide_where_sync``)."""
-    if elem_bytes not in (4, 8):
-        raise ValueError("elem_bytes must be 4 or 8 (16-bit arrays: where.count_device_ptr_where), not %r" % (elem_bytes,))
+    _checks.check_elem_bytes(elem_bytes, "where.count_device_ptr_where")
     _where._check_sel_bits(sel_bits)
     _checks.check_raw_ints((("ptr", ptr), ("n", n), ("sel_ptr", sel_ptr), ("sel_offset", sel_offset)), non_negative=("n", "sel_offset"))
     ptr, n, sel_ptr, sel_offset = int(ptr), int(n), int(sel_ptr), int(sel_offset)
@@ -71,7 +64,7 @@ def count_device_ptr_ints_where(ptr: int, n: int, elem_bytes: int, sel_ptr: int,
     selected, high = ctypes.c_uint64(0), ctypes.c_uint64(0)
     _lib.check(_lib.lib().FLAGSTATS_hip_device_wide_where_sync(ptr if n else None, n, elem_bytes, sel_ptr if n else None, sel_offset,
                                                                sel_bits, out.ctypes.data, ctypes.byref(selected), ctypes.byref(high),
-                                                               STORE | (SUPERSET if superset else 0)),
+                                                               _checks.c_flags(True, superset)),
                "FLAGSTATS_hip_device_wide_where_sync")
     return out, int(selected.value), int(high.value)
 
@@ -91,11 +84,7 @@ def count_torch_ints_where(t, where, out=None, selected=None, high=None, store: 
 
     _wide._check_tensor(t)
     bit_offset = _where._check_selection_torch(where, t.numel(), packed, bit_offset)
-    _checks.check_result_pair(out, "selected", selected)
-    _checks.check_result_pair(None, "high", high)
-    out, selected = _checks.place_result_pair(t, out, "selected", selected, others=(("where", where), ("high", high)))
-    if high is None:
-        high = torch.zeros(1, dtype=torch.int64, device=t.device)
+    out, selected, high = _checks.place_result_triple(t, out, selected, high, others=(("where", where),))
     if t.element_size() == 2:
         if store:
             with torch.cuda.device(t.device):
@@ -107,7 +96,7 @@ def count_torch_ints_where(t, where, out=None, selected=None, high=None, store: 
     with torch.cuda.device(t.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
         n = t.numel()
-        flags = (STORE if store else 0) | (SUPERSET if superset else 0)
+        flags = _checks.c_flags(store, superset)
         _lib.check(lib.FLAGSTATS_hip_device_wide_where(t.data_ptr() if n else None, n, t.element_size(),
                                                        where.data_ptr() if n else None, bit_offset, 1 if packed else 8,
                                                        out.data_ptr(), selected.data_ptr(), high.data_ptr(), flags, stream),
