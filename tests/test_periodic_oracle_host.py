@@ -1,0 +1,189 @@
+"""CPU: tests/periodic_oracle.py, the exact reference of the GPU tests past 2^32 (tests/test_gpu_derived_limits.py).
+(a) The oracle against every brute-force oracle of the family, on columns of a few million elements with random phases,
+    selection offsets, segment offsets and needles.
+(b) For every call of the GPU module, the wrapped models: a kernel that held the array's byte offset, the selection index, the
+    MAPQ index or a segment offset in 32 bits (modulo 2^31, modulo 2^32, or sign-extended) would report something else than the
+    truth in the very quantities the GPU test compares -- so a subtly wrong kernel fails there, and no GPU run of broken code is
+    needed to know it."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import filter_oracle  # noqa: E402
+import filter_where_oracle  # noqa: E402
+import periodic_oracle as po  # noqa: E402
+import segments_filter_oracle  # noqa: E402
+import segments_filter_where_oracle  # noqa: E402
+import segments_oracle  # noqa: E402
+import segments_where_oracle  # noqa: E402
+import segments_wide_filter_oracle  # noqa: E402
+import segments_wide_filter_where_oracle  # noqa: E402
+import segments_wide_oracle  # noqa: E402
+import segments_wide_where_oracle  # noqa: E402
+import where_oracle  # noqa: E402
+import wide_filter_oracle  # noqa: E402
+import wide_filter_where_oracle  # noqa: E402
+import wide_where_oracle  # noqa: E402
+
+
+def random_column(W, rng, n):
+    F, H, S, Q = po.patterns(W)
+    needles = {}
+    for i, k in enumerate([0, n - 1] + [int(x) for x in rng.randint(1, n - 1, 4)]):
+        needles[k] = (po.NEEDLE_FLAGS[i], 0 if W == 2 else 1 << po.NEEDLE_BITS[W][i], bool(rng.randint(0, 2)), int(rng.randint(0, 256)))
+    return po.Column(W, n, rng.permutation(F), rng.permutation(H), rng.permutation(S), rng.permutation(Q), phase=int(rng.randint(0, 5000)),
+                     needles=needles)
+
+
+def random_offsets(col, rng):
+    n = col.n
+    cuts = np.sort(rng.randint(0, n + 1, 40))
+    near = [k + d for k in col.needles for d in (0, 1) if 0 <= k + d <= n]      # segments that begin and end at a needle
+    return np.unique(np.concatenate([cuts, near])).astype(np.int64)
+
+
+@pytest.mark.parametrize("W", [2, 4, 8])
+def test_oracle_matches_every_brute_force_oracle(W, oracle_mod):
+    rng = np.random.RandomState(100 + W)
+    n = 2_000_003 + W
+    col = random_column(W, rng, n)
+    assert col.n > 2 * po.JOINT
+    for trial, (require, exclude, min_mapq) in enumerate(po.PREDICATES + ((2, 2, 0), (0, 0x100, 60))):
+        sel_offset = int((0, 5, po.BIG_OFFSET, rng.randint(0, 1 << 40), rng.randint(0, 100))[trial])
+        superset = bool(trial % 2)
+        o = random_offsets(col, rng)
+        flat = np.array([o[1], o[-2]], dtype=np.int64)
+        v, m, q = col.materialize(0, n, sel_offset)
+        low = wide_where_oracle.low16(v) if W > 2 else v
+        mq = q if min_mapq else None
+        pred = dict(require=require, exclude=exclude, min_mapq=min_mapq)
+        same = lambda got, want: all(np.array_equal(np.asarray(g, dtype=np.uint64).ravel(), np.asarray(w, dtype=np.uint64).ravel())  # noqa: E731
+                                     for g, w in zip(got, want))
+        # segmented, the four kinds on the low 16 bits and the four wide ones
+        r = col.expect(o, superset=superset)
+        assert np.array_equal(r.rows, segments_oracle.segmented_counters(low, o, superset))
+        rf = col.expect(o, superset=superset, **pred)
+        assert same((rf.rows, rf.selected), segments_filter_oracle.want(low, o, require, exclude, mq, min_mapq, superset))
+        rw = col.expect(o, superset=superset, masked=True, sel_offset=sel_offset)
+        assert same((rw.rows, rw.selected), segments_where_oracle.want(low, o, m, superset))
+        rfw = col.expect(o, superset=superset, masked=True, sel_offset=sel_offset, **pred)
+        assert same((rfw.rows, rfw.selected), segments_filter_where_oracle.want(low, o, m, require, exclude, mq, min_mapq, superset))
+        if W > 2:
+            assert same((r.rows, r.high_read), segments_wide_oracle.want(v, o, superset))
+            assert same((rf.rows, rf.selected, rf.high_read), segments_wide_filter_oracle.want(v, o, require, exclude, mq, min_mapq, superset))
+            assert same((rw.rows, rw.selected, rw.high_selected), segments_wide_where_oracle.want(v, o, m, superset))
+            assert same((rfw.rows, rfw.selected, rfw.high_selected),
+                        segments_wide_filter_where_oracle.want(v, o, m, require, exclude, mq, min_mapq, superset))
+        # flat: one segment, compacted and handed to the C reference
+        a, b = int(flat[0]), int(flat[1])
+        va, ma, qa, la = v[a:b], m[a:b], (None if mq is None else mq[a:b]), low[a:b]
+        f = col.expect(flat, superset=superset, **pred)
+        assert same((f.rows, f.selected), filter_oracle.want_counters(oracle_mod, la, require, exclude, qa, min_mapq, superset))
+        w = col.expect(flat, superset=superset, masked=True, sel_offset=sel_offset)
+        assert same((w.rows,), (where_oracle.want_counters(oracle_mod, la, ma, superset),)) and int(w.selected[0]) == int(ma.sum())
+        fw = col.expect(flat, superset=superset, masked=True, sel_offset=sel_offset, **pred)
+        assert same((fw.rows, fw.selected), filter_where_oracle.want_counters(oracle_mod, la, ma, require, exclude, qa, min_mapq, superset))
+        if W > 2:
+            c, k, h = wide_filter_oracle.want(oracle_mod, va, require, exclude, qa, min_mapq, superset)
+            h = 0 if require & exclude else h         # (that oracle leaves the pair that reads nothing to its caller)
+            assert same((f.rows, f.selected, f.high_read), (c, k, h))
+            assert same((w.rows, w.selected, w.high_selected), wide_where_oracle.want(oracle_mod, va, ma, superset))
+            assert same((fw.rows, fw.selected, fw.high_selected),
+                        wide_filter_where_oracle.want(oracle_mod, va, ma, require, exclude, qa, min_mapq, superset))
+
+
+def test_index_maps_against_a_gather():
+    """the maps themselves: ``expect`` under a map equals the brute-force count of the gathered column (small marks stand in for
+    2^31 and 2^32, so that the column can be materialized)"""
+    rng = np.random.RandomState(7)
+    n = 1_700_000
+    col = random_column(4, rng, n)
+    o = random_offsets(col, rng)
+    maps = (((0, 900_000, 0), (900_000, po.INF, -900_000)), ((0, 500_000, 0), (500_000, 1_000_000, -1_000_000), (1_000_000, po.INF, 0)))
+    j = np.arange(n, dtype=np.int64)
+    for pieces in maps:
+        for what in ("array_map", "sel_map", "mapq_map"):
+            sel_offset = 11
+            ja = po.map_indices(pieces, j) if what == "array_map" else j
+            je = po.map_indices(pieces, j + sel_offset) - sel_offset if what == "sel_map" else j
+            jq = po.map_indices(pieces, j) if what == "mapq_map" else j
+            flag, hb, sel, q = col.read(ja, je, jq, sel_offset)
+            v = (flag.astype(np.uint64) | hb).astype(np.uint32)
+            got = col.expect(o, 0, 0x904, 30, masked=True, sel_offset=sel_offset, superset=True, **{what: pieces})
+            rows, selected, high = segments_wide_filter_where_oracle.want(v, o, sel, 0, 0x904, q, 30, True)
+            assert np.array_equal(got.rows, rows) and np.array_equal(got.selected, selected) and np.array_equal(got.high_selected, high), what
+
+
+def assert_detected(found: dict, whats, label):
+    """every model that moves an index of the call is told, and each of ``whats`` that the call reads by one model at least"""
+    missed = [k for k, hit in found.items() if k[0] in whats and hit is False]
+    assert not missed, "%s: a kernel with these wrapped indices would pass: %r" % (label, missed)
+    for what in {k[0] for k in found if k[0] in whats}:
+        assert any(hit for k, hit in found.items() if k[0] == what), (label, what)
+    assert any(k[0] in whats for k in found), label
+
+
+@pytest.mark.parametrize("W", [2, 4, 8])
+def test_wrapped_models_fail_every_slab_call(W):
+    col = po.column(W)
+    found = {}                                    # calls that differ only in what a kernel does not take are one call to it
+    for call in po.slab_calls(W):
+        segmented = len(call["offsets"]) > 2
+        for filt in (False, True):
+            for mask in (False, True):
+                if call["local"] and not mask:
+                    continue                      # a window without a selection holds no index past the mark
+                whats = ("selection",) if call["local"] else ("array", "offsets", "selection", "mapq") if segmented else ("array", "selection", "mapq")
+                key = po.call_key(call, filt, mask)
+                if key not in found:
+                    found[key] = col.detects(call["offsets"], superset=True, **po.reduced(call, filt, mask))
+                assert_detected(found[key], whats, (W, call["case"], filt, mask))
+
+
+@pytest.mark.parametrize("W", [2, 4, 8])
+def test_wrapped_models_fail_the_one_needle_calls(W):
+    """every model is told by the call of at least one needle (a needle below 2^31 bytes cannot tell any)"""
+    col = po.column(W)
+    for filt in (False, True):
+        pred = dict(min_mapq=60) if filt else {}
+        found = {}
+        for k in col.needles:
+            truth = po.union_expect(col, po.one_needle_ranges(k), **pred)
+            if filt:                                  # counters and selected are those of exactly that element
+                alone = col.expect([k, k + 1])
+                assert int(truth.selected[0]) == 1 and np.array_equal(truth.rows, alone.rows) and alone.rows[0, [10, 25]].any()
+            for model in po.MODELS:
+                tries = {"array": po.union_expect(col, po.one_needle_ranges(k), array_map=po.wrapped(model, W), **pred),
+                         "selection": po.union_expect(col, po.one_needle_ranges(k, po.wrapped(model)), **pred)}
+                if filt:
+                    tries["mapq"] = po.union_expect(col, po.one_needle_ranges(k), mapq_map=po.wrapped(model), **pred)
+                for what, got in tries.items():
+                    moved = po.delta_at(po.wrapped(model, W if what == "array" else 1), k) != 0
+                    hit = (not truth.same(got, True, W > 2)) if moved else None
+                    found[(what, model)] = found.get((what, model)) or hit
+        assert_detected(found, ("array", "selection", "mapq"), (W, filt))
+
+
+def test_wrapped_models_fail_the_one_workgroup_calls():
+    for W, kinds in ((2, ((False, True), (True, False), (True, True))), (4, ((True, True),))):
+        col = po.column(W, dense=True)
+        whole = np.array([0, col.n], dtype=np.int64)
+        for filt, mask in kinds:
+            kw = po.reduced(po.DENSE_CALL, filt, mask)
+            truth = col.expect(whole, superset=True, **kw)
+            assert int(truth.selected[0]) > 1 << 32 and int(truth.rows[0, 9]) > 1 << 32       # one workgroup's total passes 2^32
+            assert_detected(col.detects(whole, superset=True, **kw), ("array", "selection", "mapq"), (W, filt, mask))
+
+
+def test_wrapped_models_fail_the_host_calls():
+    col = po.column(2, n=po.HOST_N)
+    kw = po.reduced(po.HOST_CALL, True, True)
+    assert_detected(col.detects(np.array([0, col.n]), **kw), ("array", "selection", "mapq"), "flat")
+    assert_detected(col.detects(np.array(po.HOST_OFFSETS[2]), **kw), ("array", "selection", "mapq", "offsets"), "segments")
+    wide = po.column(8, n=po.HOST_WIDE_N)
+    found = wide.detects(np.array(po.HOST_OFFSETS[8]), **po.reduced(po.HOST_CALL, False, True))
+    # 2^29 + 65541 elements: only the byte offset pos * W passes 2^32 -- no selection index does
+    assert_detected(found, ("array",), "wide")
