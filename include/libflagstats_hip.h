@@ -209,6 +209,42 @@ int FLAGSTATS_hip_device_u16_filter_sync(const uint16_t* d_array, uint64_t n, ui
 int FLAGSTATS_hip_u16_x64_filter(const uint16_t* array, uint64_t n, uint32_t require, uint32_t exclude, const uint8_t* mapq,
                                  uint32_t min_mapq, uint64_t* out, uint64_t* selected, int flags);
 
+/* ================= filtered, the whole predicate: samtools' view filter -f / -F / --rf / -G / -q =================
+ * The filtered entries with the two options of `samtools view` that no require / exclude pair can express once they name two
+ * bits: --rf (--incl-flags) include_any keeps a read only if it has AT LEAST ONE of these bits (--rf 0x50: first or reverse), -G
+ * exclude_all drops a read only if it has ALL of these bits (-G 0xC: read and mate both unmapped).  uint16 arrays as a whole only.
+ *   pass(i) = (array[i] & require) == require && (array[i] & exclude) == 0
+ *             && (include_any == 0 || (array[i] & include_any) != 0)
+ *             && (exclude_all == 0 || (array[i] & exclude_all) != exclude_all)
+ *             && (min_mapq == 0 || mapq[i] >= min_mapq)
+ * include_any == 0 and exclude_all == 0 switch those tests off; with both 0 the entries are the filtered entries.  Everything
+ * else is the filtered entries' contract: the 32 counters over {array[i] : pass(i), 0 <= i < n} and the optional superset (slot 9
+ * from the passing count), `selected`, `flags` (bit 0 store, bit 1 superset), min_mapq == 0 reads no byte of `mapq`, which may
+ * then be NULL, otherwise exactly mapq[0 .. n) is read; n == 0 succeeds and touches nothing (the store form writes zeros).
+ * The four masks are first reduced exactly on the host (a single --rf bit is a required bit, a single -G bit an excluded one, a
+ * bit that -f / -F already decide leaves --rf / -G), and by what is left a call is one of three things:
+ *   nothing can pass (require & exclude != 0, every --rf bit excluded, every -G bit required): nothing is launched or read; the
+ *       store form still zeroes
+ *   a plain require / exclude pair is left: the launch is the filtered entries' kernel, at its speed
+ *   a residue of two or more free bits in --rf or -G is left: one kernel of its own (fsk::flagstat_count_filter_rf)
+ * Refused (non-zero, message in FLAGSTATS_hip_last_error, out and selected untouched, nothing launched): what the filtered
+ * entries refuse, and include_any or exclude_all above 0xFFFF. */
+/* DEVICE array and MAPQ column, DEVICE d_out[32] and d_selected[1] (uint64); asynchronous on `stream`: ONE kernel (the store form
+ * puts one memset per pointer in front of it; one in all when d_selected == d_out + 32), no workspace, nothing synchronised; may
+ * be captured into a graph.  Adds are atomic: launches on several streams may share d_out and d_selected in the += form. */
+int FLAGSTATS_hip_device_u16_filter_rf(const uint16_t* d_array, uint64_t n, uint32_t require, uint32_t exclude, uint32_t include_any,
+                                       uint32_t exclude_all, const uint8_t* d_mapq, uint32_t min_mapq, uint64_t* d_out,
+                                       uint64_t* d_selected, int flags, void* stream);
+/* DEVICE array and MAPQ column, HOST out[32] and selected[1]; synchronous */
+int FLAGSTATS_hip_device_u16_filter_rf_sync(const uint16_t* d_array, uint64_t n, uint32_t require, uint32_t exclude,
+                                            uint32_t include_any, uint32_t exclude_all, const uint8_t* d_mapq, uint32_t min_mapq,
+                                            uint64_t* out, uint64_t* selected, int flags);
+/* HOST array and MAPQ column, HOST out[32] and selected[1]; synchronous.  Array and column cross the bus in the engine's chunks
+ * (knob "chunk_flags"), each chunk's slice of the column behind its flags; the counters are summed on the device. */
+int FLAGSTATS_hip_u16_x64_filter_rf(const uint16_t* array, uint64_t n, uint32_t require, uint32_t exclude, uint32_t include_any,
+                                    uint32_t exclude_all, const uint8_t* mapq, uint32_t min_mapq, uint64_t* out, uint64_t* selected,
+                                    int flags);
+
 /* ================= filtered and selected: samtools' view filter -f / -F / -q under a bitmap or a byte mask =================
  * The table for `-F 0x904 -q 30` of a FLAG column that has a validity bitmap (Arrow leaves the value of a null slot unspecified,
  * so a null FLAG must not be tested or counted), or of the reads that pass the filter AND lie in a region / read-group / dedup

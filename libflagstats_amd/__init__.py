@@ -15,6 +15,8 @@ Only what the path needs:
                      bitmap selects, with the number selected, in one pass
 * ``filter``         the same counters for the reads that pass samtools' ``-f`` / ``-F`` / ``-q``
                      (FLAG bits required and excluded, a MAPQ threshold), with no mask array
+* ``filter_rf``      the filter with the rest of samtools' FLAG predicate, ``--rf`` (at least one of these bits) and ``-G``
+                     (not all of these bits), on ``uint16`` arrays as a whole
 * ``filter_where``   the filter and a boolean mask or bitmap together: the counters of the reads that pass ``-f`` / ``-F`` /
                      ``-q`` AND are selected (the non-null rows of an Arrow FLAG column), with their number, in one pass
 * ``segments_filter`` the filter per segment: rows of counters and the number of reads that pass, for
@@ -53,6 +55,12 @@ from .segments import (  # noqa: F401
     segment_dicts,
 )
 from .filter import count_device_ptr_filter, count_torch_filter, counters_filter, flagstats_filter  # noqa: F401
+from .filter_rf import (  # noqa: F401
+    count_device_ptr_filter_rf,
+    count_torch_filter_rf,
+    counters_filter_rf,
+    flagstats_filter_rf,
+)
 from .filter_where import (  # noqa: F401
     count_device_ptr_filter_where,
     count_torch_filter_where,
@@ -139,4 +147,5 @@ __all__ = ["flagstats", "flagstats_x64", "SAM_FLAG_NAMES", "flagstats_segments",
            "count_segments_torch_filter_where", "counters_ints_filter_where", "flagstats_ints_filter_where",
            "count_device_ptr_ints_filter_where", "count_torch_ints_filter_where", "counters_segments_ints_filter_where",
            "flagstats_segments_ints_filter_where", "count_segments_device_ptr_ints_filter_where",
-           "count_segments_torch_ints_filter_where"]
+           "count_segments_torch_ints_filter_where", "counters_filter_rf", "flagstats_filter_rf", "count_device_ptr_filter_rf",
+           "count_torch_filter_rf"]

@@ -1,6 +1,7 @@
 // flagstat_derived_host.h -- internal: the host code that the kernels derived from K1 share.  All fifteen derived units use it:
 // the seven flat ones (flagstat_{wide,where,filter,filter_where,wide_filter,wide_where,wide_filter_where}.hip) directly, the
-// eight segmented ones (flagstat_segments*.hip) through flagstat_segments_shared.h.  It holds the launcher's step split and
+// eight segmented ones (flagstat_segments*.hip) through flagstat_segments_shared.h; flagstat_filter_rf.hip, the filtered unit's
+// --rf / -G form, uses it as that unit does.  It holds the launcher's step split and
 // store-form memset, the rules of an entry's arguments with the text of their refusals (one function per rule; a unit's *_args
 // composes them in its own order), a call's inputs table, the device row of a synchronous call (32 counters and one trailing
 // word, or two: kRowWords / kRowWords2), and the bodies of the three entry forms of the flat units -- on the caller's stream,
@@ -173,6 +174,16 @@ inline int check_predicate(uint32_t require, uint32_t exclude, uint32_t min_mapq
     if (exclude > 0xFFFFu) return fail_text("exclude must be a 16-bit FLAG mask (at most 0xFFFF)");
     if (min_mapq > 255u) return fail_text("min_mapq must be at most 255 (MAPQ is one byte)");
     return 0;
+}
+
+// the two further masks of samtools' view predicate (--rf, -G: flagstat_filter_rf.hip), in check_predicate's words
+inline int check_predicate_rf(uint32_t include_any, uint32_t exclude_all)
+{
+    const bool any = include_any > 0xFFFFu;
+    if (!any && exclude_all <= 0xFFFFu) return 0;
+    char buf[96];
+    std::snprintf(buf, sizeof buf, "%s must be a 16-bit FLAG mask (at most 0x%X)", any ? "include_any" : "exclude_all", 0xFFFFu);
+    return fail_text(buf);
 }
 
 inline int check_sel_bits(int sel_bits)

@@ -17,11 +17,17 @@ from ._checks import STORE, SUPERSET  # noqa: F401  (kept as this module's names
 from .pyflagstats import _as_dict
 
 
+def _check_flag_mask(name: str, x) -> int:
+    """``x`` is an int in 0..65535: one of the predicate's masks over the 16 FLAG bits"""
+    _checks.check_int(name, x)
+    if not 0 <= x <= 0xFFFF:
+        raise ValueError("%s must be a 16-bit FLAG mask (0..65535), not %d" % (name, x))
+    return int(x)
+
+
 def _check_predicate(require, exclude, min_mapq, has_mapq: bool):
     for name, x in (("require", require), ("exclude", exclude)):
-        _checks.check_int(name, x)
-        if not 0 <= x <= 0xFFFF:
-            raise ValueError("%s must be a 16-bit FLAG mask (0..65535), not %d" % (name, x))
+        _check_flag_mask(name, x)
     _checks.check_int("min_mapq", min_mapq)
     if not 0 <= min_mapq <= 255:
         raise ValueError("min_mapq must be in 0..255 (MAPQ is one byte), not %d" % min_mapq)
