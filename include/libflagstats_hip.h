@@ -453,6 +453,46 @@ int FLAGSTATS_hip_wide_x64_filter(const void* array, uint64_t n, int elem_bytes,
                                   const uint8_t* mapq, uint32_t min_mapq, uint64_t* out, uint64_t* selected, uint64_t* high,
                                   int flags);
 
+/* ================= filtered wide input, the whole predicate: -f / -F / --rf / -G / -q on a 4-byte or 8-byte FLAG column =========
+ * The filtered wide entries with the two options of `samtools view` that no require / exclude pair can express once they name two
+ * bits (--rf include_any: AT LEAST ONE of these bits; -G exclude_all: not ALL of these bits), on the column as it arrives: int32
+ * or int64, read once and in place.  Whole columns only.  With f(i) = the low 16 bits of element i:
+ *   pass(i) = (f(i) & require) == require && (f(i) & exclude) == 0
+ *             && (include_any == 0 || (f(i) & include_any) != 0)
+ *             && (exclude_all == 0 || (f(i) & exclude_all) != exclude_all)
+ *             && (min_mapq == 0 || mapq[i] >= min_mapq)
+ * include_any == 0 and exclude_all == 0 switch those tests off; with both 0 the entries are the filtered wide entries.  Everything
+ * else is the filtered wide entries' contract: out, selected and high, `flags`, NULL selected / high, the MAPQ column, n == 0.
+ * The whole predicate sees the low 16 bits only: a bit above bit 15 satisfies no --rf and completes no -G, and is reported in
+ * `high` whether its element passes or not.
+ * The four masks are first reduced exactly on the host, as for the uint16 entries of the whole predicate, and by what is left a
+ * call is one of three things:
+ *   nothing can pass (require & exclude != 0, every --rf bit excluded, every -G bit required): nothing is launched and NO ELEMENT
+ *       IS READ, so `high` is then 0 in the store form and untouched in the += form, like out and selected -- it says nothing
+ *       about the column
+ *   a plain require / exclude pair is left: the launch is the filtered wide entries' kernel, at its speed
+ *   a residue of two or more free bits in --rf or -G is left: one kernel of its own (fsk::flagstat_count_wide_filter_rf)
+ * In the last two `high` is the OR over all n elements, whatever min_mapq is.
+ * Refused (non-zero, message in FLAGSTATS_hip_last_error, outputs untouched, nothing launched): what the filtered wide entries
+ * refuse (elem_bytes 2: use the u16 entries of the whole predicate), and include_any or exclude_all above 0xFFFF. */
+/* DEVICE array and MAPQ column, DEVICE d_out[32], d_selected[1] and d_high[1] (uint64); asynchronous on `stream`: ONE kernel
+ * (the store form puts one memset per pointer in front of it; one in all when d_selected == d_out + 32 and d_high == d_out + 33),
+ * no workspace, nothing synchronised; may be captured into a graph.  Adds and ORs are atomic: launches on several streams may
+ * share the three in the += form. */
+int FLAGSTATS_hip_device_wide_filter_rf(const void* d_array, uint64_t n, int elem_bytes, uint32_t require, uint32_t exclude,
+                                        uint32_t include_any, uint32_t exclude_all, const uint8_t* d_mapq, uint32_t min_mapq,
+                                        uint64_t* d_out, uint64_t* d_selected, uint64_t* d_high, int flags, void* stream);
+/* DEVICE array and MAPQ column, HOST out[32], selected[1] and high[1]; synchronous */
+int FLAGSTATS_hip_device_wide_filter_rf_sync(const void* d_array, uint64_t n, int elem_bytes, uint32_t require, uint32_t exclude,
+                                             uint32_t include_any, uint32_t exclude_all, const uint8_t* d_mapq, uint32_t min_mapq,
+                                             uint64_t* out, uint64_t* selected, uint64_t* high, int flags);
+/* HOST array and MAPQ column, HOST out[32], selected[1] and high[1]; synchronous.  The array crosses the bus as it is in the
+ * engine's chunks (knob "chunk_flags": chunk_flags * 2 bytes of elements each), each chunk's slice of the column behind its
+ * elements; counters, count and mask are summed / ORed on the device. */
+int FLAGSTATS_hip_wide_x64_filter_rf(const void* array, uint64_t n, int elem_bytes, uint32_t require, uint32_t exclude,
+                                     uint32_t include_any, uint32_t exclude_all, const uint8_t* mapq, uint32_t min_mapq,
+                                     uint64_t* out, uint64_t* selected, uint64_t* high, int flags);
+
 /* ================= selected elements of wide input: a bitmap or byte mask on a FLAG column of 4-byte or 8-byte integers =========
  * An Arrow FLAG column is both at once: int32 values and an LSB-first validity bitmap at some bit offset.  One pass over the
  * array as it is and its selection: no uint16 copy in front (which would turn a negative element or one >= 65,536 into a

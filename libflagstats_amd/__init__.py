@@ -27,6 +27,8 @@ Only what the path needs:
                      that pass AND are selected, for every CSR segment in one launch
 * ``wide_filter``    the filter on int32 / int64 (and 16-bit) arrays and tensors in place: counters, the number of
                      reads that pass and the mask of bits seen above bit 15, in one pass
+* ``wide_filter_rf`` ``wide_filter`` under samtools' whole FLAG predicate: ``--rf`` (at least one of these bits) and ``-G``
+                     (not all of these bits) on int32 / int64 (and 16-bit) arrays and tensors in place, as a whole
 * ``wide_where``     the mask or bitmap on int32 / int64 (and 16-bit) arrays and tensors in place: counters, the number
                      selected and the mask of bits seen above bit 15 of the selected elements, in one pass
 * ``wide_filter_where`` the filter and the mask or bitmap together on int32 / int64 (and 16-bit) arrays and tensors in place:
@@ -117,6 +119,12 @@ from .wide_filter import (  # noqa: F401
     counters_ints_filter,
     flagstats_ints_filter,
 )
+from .wide_filter_rf import (  # noqa: F401
+    count_device_ptr_ints_filter_rf,
+    count_torch_ints_filter_rf,
+    counters_ints_filter_rf,
+    flagstats_ints_filter_rf,
+)
 from .wide_filter_where import (  # noqa: F401
     count_device_ptr_ints_filter_where,
     count_torch_ints_filter_where,
@@ -148,4 +156,5 @@ __all__ = ["flagstats", "flagstats_x64", "SAM_FLAG_NAMES", "flagstats_segments",
            "count_device_ptr_ints_filter_where", "count_torch_ints_filter_where", "counters_segments_ints_filter_where",
            "flagstats_segments_ints_filter_where", "count_segments_device_ptr_ints_filter_where",
            "count_segments_torch_ints_filter_where", "counters_filter_rf", "flagstats_filter_rf", "count_device_ptr_filter_rf",
-           "count_torch_filter_rf"]
+           "count_torch_filter_rf", "counters_ints_filter_rf", "flagstats_ints_filter_rf", "count_device_ptr_ints_filter_rf",
+           "count_torch_ints_filter_rf"]

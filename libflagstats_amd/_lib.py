@@ -104,6 +104,16 @@ SIGNATURES = {
     "FLAGSTATS_hip_wide_x64_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
                                                      ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                      ctypes.c_int]),
+    "FLAGSTATS_hip_device_wide_filter_rf": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
+                                                           ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "FLAGSTATS_hip_device_wide_filter_rf_sync": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32,
+                                                                ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                                                ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                                ctypes.c_int]),
+    "FLAGSTATS_hip_wide_x64_filter_rf": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
+                                                        ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
     "FLAGSTATS_hip_device_wide_where": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
                                                        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                        ctypes.c_void_p]),
@@ -281,7 +291,7 @@ SIGNATURES = {
 }
 
 # internal launchers the tests and tests/perf drive directly (csrc/flagstat_wide.h, csrc/flagstat_where.h, csrc/flagstat_filter.h,
-# csrc/flagstat_segments_filter.h, csrc/flagstat_wide_filter.h, csrc/flagstat_segments_wide.h, csrc/flagstat_segments_wide_filter.h, csrc/flagstat_segments_where.h, csrc/flagstat_wide_where.h, csrc/flagstat_segments_wide_where.h, csrc/flagstat_filter_where.h, csrc/flagstat_segments_filter_where.h, csrc/flagstat_wide_filter_where.h, csrc/flagstat_segments_wide_filter_where.h, csrc/flagstat_filter_rf.h); not part of the public headers, so kept apart from SIGNATURES, which mirrors those
+# csrc/flagstat_segments_filter.h, csrc/flagstat_wide_filter.h, csrc/flagstat_segments_wide.h, csrc/flagstat_segments_wide_filter.h, csrc/flagstat_segments_where.h, csrc/flagstat_wide_where.h, csrc/flagstat_segments_wide_where.h, csrc/flagstat_filter_where.h, csrc/flagstat_segments_filter_where.h, csrc/flagstat_wide_filter_where.h, csrc/flagstat_segments_wide_filter_where.h, csrc/flagstat_filter_rf.h, csrc/flagstat_wide_filter_rf.h); not part of the public headers, so kept apart from SIGNATURES, which mirrors those
 INTERNAL_SIGNATURES = {
     "fsk_launch_wide": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                        ctypes.c_uint32, ctypes.c_void_p]),
@@ -301,6 +311,9 @@ INTERNAL_SIGNATURES = {
     "fsk_launch_wide_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                               ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32,
                                               ctypes.c_void_p]),
+    "fsk_launch_wide_filter_rf": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
+                                                 ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p]),
     "fsk_launch_segments_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
                                                   ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p]),

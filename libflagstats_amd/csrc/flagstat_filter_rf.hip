@@ -15,9 +15,9 @@
 //
 // Kernel.  fsk::flagstat_count_filter_rf is flagstat_count_filter (flagstat_filter.hip: geometry, fsdrv::step_split, guarded edge
 // steps, rolling schedule 71 on fast steps, chain depth 8 with epochs of 255 steps, the direct epilogue) with up to two more tests
-// ANDed into the pass word of 4 flags, in front of the popcount and of the v_perm_b32 masks.  On the byte planes L (FLAG bits 0-7)
-// and H (bits 8-15), with a = include_any, g = exclude_all byte-replicated in wave-uniform registers and p the parent's pass word
-// (0x80 per passing flag):
+// ANDed into the pass word of 4 flags (pass4_rf of flagstat_filter_rf_device.h), in front of the popcount and of the v_perm_b32
+// masks.  On the byte planes L (FLAG bits 0-7) and H (bits 8-15), with a = include_any, g = exclude_all byte-replicated in
+// wave-uniform registers and p the parent's pass word (0x80 per passing flag):
 //   any-of   t = L & aL                          v_and_b32
 //            y = (H & aH) | t                    v_bitop3_b32    a byte of y is 0 iff the flag has no bit of a
 //            s = (y & 0x7F..) + 0x7F..           v_and_b32, v_add_u32     bit 7 of a byte: one of bits 0-6 of y is set (no carry
@@ -41,47 +41,11 @@
 #include "flagstat_filter.h"
 #include "flagstat_filter_device.h"
 #include "flagstat_filter_rf.h"
+#include "flagstat_filter_rf_device.h"
 
 namespace fsk {
 
 constexpr int kFilterRfDepth = 8;     // chain depth as K1: epochs of 255 steps
-
-// the residue of a launch, byte-replicated: wave-uniform
-struct FilterRfArgs {
-    uint32_t aL, aH;           // include_any, low and high byte plane
-    uint32_t gL, gH;           // exclude_all
-};
-
-__device__ __forceinline__ FilterRfArgs filter_rf_args_of(uint32_t include_any, uint32_t exclude_all)
-{
-    FilterRfArgs r;
-    r.aL = (include_any & 0xFFu) * 0x01010101u;
-    r.aH = ((include_any >> 8) & 0xFFu) * 0x01010101u;
-    r.gL = (exclude_all & 0xFFu) * 0x01010101u;
-    r.gH = ((exclude_all >> 8) & 0xFFu) * 0x01010101u;
-    return r;
-}
-
-// v_bitop3_b32 truth tables of this unit (a = 0xF0, b = 0xCC, c = 0xAA, as in flagstat_filter_device.h)
-constexpr uint32_t kTtAndOr = (0xF0 & 0xCC) | 0xAA;                           // (a & b) | c
-constexpr uint32_t kTtNotAndOr = ((~0xF0 & 0xCC) | 0xAA) & 0xFF;              // (~a & b) | c
-
-// p with the bytes cleared whose byte of x is 0; p holds nothing but bit 7 of its bytes
-__device__ __forceinline__ uint32_t and_nonzero_bytes(uint32_t p, uint32_t x)
-{
-    const uint32_t s = (x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;
-    return __builtin_amdgcn_bitop3_b32(s, x, p, kTtOrAnd);
-}
-
-// pass4 (flagstat_filter_device.h) under the residue: 0x80 per flag of the planes L, H that passes all of it
-template <bool MAPQ, bool ANY, bool ALL>
-__device__ __forceinline__ uint32_t pass4_rf(const FilterArgs& f, const FilterRfArgs& r, uint32_t L, uint32_t H, uint32_t w)
-{
-    uint32_t p = pass4<MAPQ>(f, L, H, w);
-    if constexpr (ANY) p = and_nonzero_bytes(p, __builtin_amdgcn_bitop3_b32(H, r.aH, L & r.aL, kTtAndOr));
-    if constexpr (ALL) p = and_nonzero_bytes(p, __builtin_amdgcn_bitop3_b32(H, r.gH, ~L & r.gL, kTtNotAndOr));
-    return p;
-}
 
 // One step, as flagstat_filter.hip's filter_step_and_count: 8 vectors of 16 B per lane through K1's tree, the predicate applied in
 // the per-vector front.  ROLL 0 (edge steps): the vectors are in v[], their MAPQ bytes in m[], the bits of their positions that
