@@ -19,7 +19,20 @@ Two deliberate limits, both recorded in the case itself:
   * a bitmap ``sel_offset`` of 2^33 + k needs the selection pointer moved 2^30 bytes back, which names no allocation: the public
     device and _sync entries check the allocation from the pointer itself on and refuse it as documented, so such an offset is
     applied in the direct-launcher and host forms only (``big_offset`` says whether it was); the others get the drawn small one.
-No case is skipped: ``case["skip"]`` is None throughout, and test_derived_plan_host.py asserts so."""
+No case is skipped: ``case["skip"]`` is None throughout, and test_derived_plan_host.py asserts so.
+
+``plan_later(seed, iters)`` is the same for the nine units derived afterwards (LATER_KINDS: the masked kinds, which take a
+selection and, where they filter, a predicate as well, and the two kinds of the whole predicate, --rf / -G).  It is a sequence of
+its own, drawn with the pieces that ``_draw`` is made of, so ``plan`` is byte for byte what it was (test_derived_plan_host.py pins
+its digest).  Beyond an existing case a later one carries ``sel_bits`` (dealt: it alternates with block and form), the --rf / -G
+masks with the outcome of the host reduction that they were built for (``rf_outcome``, dealt from RF_OUTCOMES), and, in the
+masked wide kinds, decoys: an unselected element with every bit above bit 15 set, and in the ``one`` style the column's single
+high bit in an unselected slot about half the time.  The big bitmap offset is dealt to half of the launcher- and host-form
+bitmap cases.
+
+``Definition`` states what the headers define, one method each: counted(j) = pass(j) && sel(j), ``selected`` the number counted,
+``high`` over the selected elements, passing or not (every element where the kind takes no selection), nothing read where no FLAG
+value can pass.  ``reference`` evaluates it; the wrong models of test_derived_plan_host.py override one method each."""
 import numpy as np
 
 KINDS = ("where_bitmap", "where_bytes", "filter", "segments", "segments_filter", "wide", "wide_filter", "wide_segments",
@@ -46,6 +59,18 @@ FILTERED = ("filter", "segments_filter", "wide_filter", "wide_segments_filter")
 WIDE = ("wide", "wide_filter", "wide_segments", "wide_segments_filter")
 SELECTING = ("where_bitmap", "where_bytes") + FILTERED            # kinds that report `selected`
 PLACEMENTS = ("together", "apart", "null")
+
+# the nine units derived afterwards: plan_later deals them as plan deals KINDS.  A masked kind takes a selection (sel_bits 1 or 8
+# is part of the case, not of the kind) and, where it also filters, a predicate; an rf kind takes samtools' --rf / -G masks.
+LATER_KINDS = ("segments_where", "wide_where", "wide_segments_where", "filter_where", "segments_filter_where", "wide_filter_where",
+               "wide_segments_filter_where", "filter_rf", "wide_filter_rf")
+RF = ("filter_rf", "wide_filter_rf")
+MASKED = tuple(k for k in LATER_KINDS if k.endswith("where"))
+LATER_SEGMENTED = tuple(k for k in LATER_KINDS if "segments" in k)
+LATER_FILTERED = tuple(k for k in LATER_KINDS if "filter" in k)
+LATER_WIDE = tuple(k for k in LATER_KINDS if k.startswith("wide"))
+RF_OUTCOMES = ("empty", "pair", "any", "all", "both")       # what the host reduction can leave of the four FLAG masks
+assert len(LATER_KINDS) * len(FORMS) == PAIRS
 
 
 def family(kind):
@@ -108,17 +133,17 @@ def _layout(rs, n, W, nseg):
     return np.concatenate([[lo], cuts, [hi]]).astype(np.int64), ("random", "random", "units", "runs")[style]
 
 
-def _draw(rs, index, kind, form, block):
-    case = {"index": index, "kind": kind, "family": family(kind), "form": form, "skip": None}
-    wide = kind in WIDE
+def _geometry(rs, case, rot, wide, segmented):
+    """element width and type, grid / chunk_flags (rotating with `rot`), segment policy, n in its four clusters, the three
+    alignments; returns the drawn small selection offset, whether a big one was drawn, and its k"""
+    form = case["form"]
     W = (4, 8)[int(rs.randint(0, 2))] if wide else 2
     signed = bool(rs.randint(0, 2))
     case["W"], case["dtype"] = W, np.dtype(SIGNED[W] if signed else UNSIGNED[W]).name
-    rot = KINDS.index(kind) + block
     case["grid"] = GRIDS[rot % len(GRIDS)] if form == "launcher" else None
     case["chunk_flags"] = CHUNKS[rot % len(CHUNKS)] if form == "host" else None
     mu, bpc = int(rs.randint(0, len(MIN_UNITS))), int(rs.randint(1, 3))
-    case["policy"] = (MIN_UNITS[mu], bpc) if kind in SEGMENTED else None
+    case["policy"] = (MIN_UNITS[mu], bpc) if segmented else None
     # n: four clusters under the cap
     pick, step = int(rs.randint(0, 4)), STEP_BYTES // W
     draws = (int(rs.randint(0, 64)), int(step * rs.randint(0, 13) + rs.randint(-9, 10)),
@@ -131,11 +156,14 @@ def _draw(rs, index, kind, form, block):
     case["n"], case["n_cluster"] = n, pick
     case["phase"] = int(rs.randint(0, 16 // W)) * W           # bytes past a 16-byte boundary
     case["mapq_align"], case["sel_align"] = int(rs.randint(0, 16)), int(rs.randint(0, 16))
-    small_off, big, k = int(rs.randint(0, 64)), int(rs.randint(0, 8)) == 0, int(rs.randint(0, 8))
-    case["big_offset"] = bool(big and kind == "where_bitmap" and form in ("launcher", "host"))
-    case["sel_offset"] = ((1 << 33) + k if case["big_offset"] else small_off) if kind == "where_bitmap" else 0
+    return int(rs.randint(0, 64)), int(rs.randint(0, 8)) == 0, int(rs.randint(0, 8))
+
+
+def _column(rs, case, wide):
+    """the array: its low 16 bits by _values; wide extras: bits above bit 15 on one element in 37, on exactly one element, nowhere.
+    Returns (the low 16 bits, the high style drawn, the draw that places the single high bit)"""
+    n, W = case["n"], case["W"]
     case["values"], low = _values(rs, n)
-    # wide extras: bits above bit 15 on one element in 37, on exactly one element, nowhere
     style, pos = int(rs.randint(0, 3)), int(rs.randint(0, 1 << 30))
     hot = rs.randint(0, 37, n) == 0
     hi = rs.randint(0, 1 << 16, n).astype(np.uint64) << np.uint64(16)
@@ -148,7 +176,13 @@ def _draw(rs, index, kind, form, block):
         elif style == 1:
             x[pos % n] |= np.uint64(1) << np.uint64(16 + pos % (8 * W - 16))
     case["array"] = x.astype(UNSIGNED[W]).view(case["dtype"])
-    # predicate and MAPQ bytes
+    return low, style, pos
+
+
+def _predicate(rs, low):
+    """require / exclude / min_mapq and the MAPQ bytes: {"witness": an element that the drawn bits let pass, "require", "exclude",
+    "overlap": the pair was made to share bits, "min_mapq", "mapq", "mapq_null"}"""
+    n = low.size
     witness = int(rs.randint(0, 1 << 30)) % max(n, 1)         # one element that the drawn bits let pass
     v = int(low[witness]) if n else 0
     require, exclude = _mask_side(rs, v), _mask_side(rs, ~v)
@@ -165,29 +199,51 @@ def _draw(rs, index, kind, form, block):
     if n:
         q[witness] = max(int(q[witness]), mq)
     mapq_null = bool(rs.randint(0, 2))
-    if kind in FILTERED:
-        case.update(require=require, exclude=exclude, min_mapq=mq, mapq=q, mapq_null=mapq_null and mq == 0)
-    else:
-        case.update(require=0, exclude=0, min_mapq=0, mapq=None, mapq_null=True)
-    # selection of the `where` kinds: half, sparse, dense, everything (1 in 40), nothing (1 in 40)
+    return {"witness": witness, "value": v, "require": require, "exclude": exclude, "overlap": overlap, "min_mapq": mq, "mapq": q,
+            "mapq_null": mapq_null and mq == 0}
+
+
+def _selection(rs, n):
+    """(bool[n], its density): half, sparse, dense, everything (1 in 40), nothing (1 in 40)"""
     density = (0.5,) * 24 + (0.1,) * 7 + (0.9,) * 7 + (1.0, 0.0)
     d = density[int(rs.randint(0, 40))]
-    m = rs.random_sample(n) < d
-    case["mask"] = m if kind in ("where_bitmap", "where_bytes") else None
-    # segments
+    return rs.random_sample(n) < d, d
+
+
+def _segments(rs, case, segmented):
     nseg = NSEGS[int(rs.randint(0, len(NSEGS)))]
-    offsets, style = _layout(rs, n, W, nseg)
-    case["offsets"], case["layout"] = (offsets, style) if kind in SEGMENTED else (None, None)
-    case["nseg"] = nseg if kind in SEGMENTED else 1
+    offsets, style = _layout(rs, case["n"], case["W"], nseg)
+    case["offsets"], case["layout"] = (offsets, style) if segmented else (None, None)
+    case["nseg"] = nseg if segmented else 1
+
+
+def _outputs(rs, case, selecting, wide):
     case["mode"] = int(rs.randint(0, 4))
     sel_place, high_place = PLACEMENTS[int(rs.randint(0, 3))], PLACEMENTS[int(rs.randint(0, 3))]
-    case["selected_at"] = sel_place if kind in SELECTING else None
+    case["selected_at"] = sel_place if selecting else None
     case["high_at"] = high_place if wide else None
+
+
+def _draw(rs, index, kind, form, block):
+    case = {"index": index, "kind": kind, "family": family(kind), "form": form, "skip": None}
+    wide = kind in WIDE
+    small_off, big, k = _geometry(rs, case, KINDS.index(kind) + block, wide, kind in SEGMENTED)
+    case["big_offset"] = bool(big and kind == "where_bitmap" and form in ("launcher", "host"))
+    case["sel_offset"] = ((1 << 33) + k if case["big_offset"] else small_off) if kind == "where_bitmap" else 0
+    low, _, _ = _column(rs, case, wide)
+    p = _predicate(rs, low)
+    if kind in FILTERED:
+        case.update(require=p["require"], exclude=p["exclude"], min_mapq=p["min_mapq"], mapq=p["mapq"], mapq_null=p["mapq_null"])
+    else:
+        case.update(require=0, exclude=0, min_mapq=0, mapq=None, mapq_null=True)
+    m, _ = _selection(rs, case["n"])
+    case["mask"] = m if kind in ("where_bitmap", "where_bytes") else None
+    _segments(rs, case, kind in SEGMENTED)
+    _outputs(rs, case, kind in SELECTING, wide)
     return case
 
 
-def plan(seed, iters):
-    """the first `iters` cases of the sequence that `seed` names"""
+def _deal(seed, iters, kinds, draw):
     rs = np.random.RandomState(seed)
     cases = []
     perm = None
@@ -195,9 +251,116 @@ def plan(seed, iters):
         block, j = divmod(it, PAIRS)
         if j == 0:
             perm = rs.permutation(PAIRS)
-        kind, form = KINDS[perm[j] // len(FORMS)], FORMS[perm[j] % len(FORMS)]
-        cases.append(_draw(rs, it, kind, form, block))
+        kind, form = kinds[perm[j] // len(FORMS)], FORMS[perm[j] % len(FORMS)]
+        cases.append(draw(rs, it, kind, form, block))
     return cases
+
+
+def plan(seed, iters):
+    """the first `iters` cases of the sequence that `seed` names"""
+    return _deal(seed, iters, KINDS, _draw)
+
+
+def _positions(mask):
+    return [b for b in range(16) if mask >> b & 1]
+
+
+def _several(rs, pool, prefer):
+    """two to four distinct bits of `pool` (which has two or more): the first from `prefer` where the pool has any of it"""
+    draws, k = rs.randint(0, 1 << 30, 4), 2 + int(rs.randint(0, 3))
+    firsts = _positions(pool & prefer) or _positions(pool)
+    first = firsts[int(draws[0]) % len(firsts)]
+    rest = [b for b in _positions(pool) if b != first]
+    out = 1 << first
+    for d in draws[1:k]:
+        out |= 1 << rest[int(d) % len(rest)]
+    return out
+
+
+def _rf_masks(rs, outcome, require, exclude, v):
+    """(require, exclude, include_any, exclude_all) that the host reduction must turn into `outcome` (RF_OUTCOMES), dealt by the
+    caller: bits are drawn over all of 0xFFFF, the any-of test around a bit the witness value `v` has, the all-of test around one
+    it lacks.  The pair loses bits 12-15 and its overlap, so that eight bits or more are free and `empty` occurs only as dealt."""
+    r = require & 0x0FFF
+    e = exclude & 0x0FFF & ~r
+    free = 0xFFFF & ~(r | e)
+    any2, all2 = _several(rs, free, v), _several(rs, free, ~v)
+    s, variant = rs.randint(0, 1 << 30, 2), int(rs.randint(0, 3))
+    spots = _positions(free & v) or _positions(free)
+    bit_a = 1 << spots[int(s[0]) % len(spots)]                # alone in --rf it is a required bit
+    spots = _positions(free & ~v & ~bit_a) or _positions(free & ~bit_a)
+    bit_g = 1 << spots[int(s[1]) % len(spots)]                # alone in -G it is an excluded bit
+    low_r, low_e = r & -r, e & -e
+    if outcome == "empty":     # every --rf bit excluded; every -G bit required; an overlapping pair
+        return ((r, e | any2, any2, 0), (r | all2, e, 0, all2), (r | bit_a, e | bit_a, any2, all2))[variant]
+    if outcome == "pair":      # single bits; tests that -f / -F already decide; a single --rf bit alone
+        return ((r, e, bit_a, bit_g), (r, e, any2 | low_r if r else 0, all2 | low_e if e else 0), (r, e, bit_a, 0))[variant]
+    if outcome == "any":
+        return r, e, any2, (0, 0 if bit_g & any2 else bit_g, all2 | low_e if e else 0)[variant]
+    if outcome == "all":
+        return r, e, (0, 0 if bit_a & all2 else bit_a, any2 | low_r if r else 0)[variant], all2
+    assert outcome == "both"
+    return r, e, any2 | (low_e if variant == 1 else 0), all2 | (low_r if variant == 2 else 0)
+
+
+def _draw_later(rs, index, kind, form, block):
+    """_draw for LATER_KINDS: the same pieces in the same order, then what only these kinds have"""
+    case = {"index": index, "kind": kind, "family": kind, "form": form, "skip": None}
+    wide, segmented, masked, rf = kind in LATER_WIDE, kind in LATER_SEGMENTED, kind in MASKED, kind in RF
+    ki, fi = LATER_KINDS.index(kind), FORMS.index(form)
+    small_off, big, k = _geometry(rs, case, ki + block, wide, segmented)
+    # dealt: sel_bits alternates with block and form; half the bitmap cases of the launcher and host forms take the big offset
+    case["sel_bits"] = (1, 8)[(block + fi) % 2] if masked else None
+    dealt = (block // 2 + ki) % 2 == 0
+    case["big_offset"] = bool((big or dealt) and case["sel_bits"] == 1 and form in ("launcher", "host"))
+    case["sel_offset"] = ((1 << 33) + k if case["big_offset"] else small_off) if masked else 0
+    low, style, pos = _column(rs, case, wide)
+    p = _predicate(rs, low)
+    if kind in LATER_FILTERED:
+        case.update(require=p["require"], exclude=p["exclude"], min_mapq=p["min_mapq"], mapq=p["mapq"], mapq_null=p["mapq_null"])
+    else:
+        case.update(require=0, exclude=0, min_mapq=0, mapq=None, mapq_null=True)
+    m, density = _selection(rs, case["n"])
+    _segments(rs, case, segmented)
+    _outputs(rs, case, True, wide)
+    # --rf / -G
+    case["rf_outcome"] = RF_OUTCOMES[(block * len(FORMS) + fi + ki) % len(RF_OUTCOMES)] if rf else None
+    masks = _rf_masks(rs, case["rf_outcome"] or "both", p["require"], p["exclude"], p["value"])
+    case["include_any"], case["exclude_all"] = masks[2:] if rf else (0, 0)
+    if rf:
+        case["require"], case["exclude"] = masks[:2]
+    # the selection: the witness is selected as well as passing; decoys in the masked wide kinds
+    n, W = case["n"], case["W"]
+    e = rs.randint(0, 1 << 30, 2)
+    case["mask"] = m if masked else None
+    if masked and n and density > 0:
+        m[p["witness"]] = True
+    if masked and wide and n >= 3 and style in (0, 1):
+        u = case["array"].view(UNSIGNED[W]).copy()
+        single = pos % n
+        if style == 1 and e[1] & 1 and single != p["witness"]:
+            m[single] = False                                 # the one high bit of the column lies in a slot that is not selected
+        else:
+            if style == 1 and density > 0:
+                m[single] = True
+            decoy = int(e[0]) % n
+            while decoy == p["witness"] or (style == 1 and decoy == single):
+                decoy = (decoy + 1) % n
+            m[decoy] = False
+            u[decoy] |= UNSIGNED[W](np.iinfo(UNSIGNED[W]).max - 0xFFFF)     # every bit above bit 15, the low 16 as drawn
+        case["array"] = u.view(case["dtype"])
+    if wide and n and case["rf_outcome"] == "empty":
+        # a call that reads nothing says nothing about the column: let the column have something to say, and the call a place for it
+        u = case["array"].view(UNSIGNED[W]).copy()
+        u[int(e[0]) % n] |= UNSIGNED[W](np.iinfo(UNSIGNED[W]).max - 0xFFFF)
+        case["array"] = u.view(case["dtype"])
+        case["high_at"] = "together" if case["high_at"] == "null" else case["high_at"]
+    return case
+
+
+def plan_later(seed, iters):
+    """plan() for LATER_KINDS: the first `iters` cases of the sequence that `seed` names, under plan()'s contract"""
+    return _deal(seed, iters, LATER_KINDS, _draw_later)
 
 
 def describe(case):
@@ -205,6 +368,7 @@ def describe(case):
     keep = ("index", "kind", "form", "W", "dtype", "n", "phase", "grid", "chunk_flags", "policy", "mode", "sel_offset", "sel_align",
             "mapq_align", "require", "exclude", "min_mapq", "mapq_null", "values", "high_style", "nseg", "layout", "selected_at", "high_at")
     d = {k: case[k] for k in keep}
+    d.update({k: case[k] for k in ("sel_bits", "include_any", "exclude_all", "rf_outcome") if k in case})   # later kinds
     if case["offsets"] is not None:
         d["offsets"] = (int(case["offsets"][0]), int(case["offsets"][-1]))
     return d
@@ -221,34 +385,91 @@ def segments_of(case):
     return case["offsets"] if case["offsets"] is not None else np.array([0, case["n"]], dtype=np.int64)
 
 
-def passing(case):
-    """bool[n]: which elements the call selects"""
-    n, W = case["n"], case["W"]
-    if case["mask"] is not None:
-        return case["mask"].astype(bool)
-    low = case["array"].view(UNSIGNED[W]).astype(np.uint64) & np.uint64(0xFFFF)
-    ok = ((low & np.uint64(case["require"])) == np.uint64(case["require"])) & ((low & np.uint64(case["exclude"])) == 0)
-    if case["min_mapq"] > 0:
-        ok &= case["mapq"] >= case["min_mapq"]
-    assert ok.shape == (n,)
+_EVERY_FLAG = np.arange(65536, dtype=np.uint64)
+
+
+class Definition:
+    """The headers' definitions, one method each, in the plain way.  reference() evaluates them; the wrong models of
+    tests/test_derived_plan_host.py override one method each, which is how the plan shows what it would notice."""
+
+    def any_of(self, f, include_any):
+        return (f & include_any) != 0
+
+    def all_of(self, f, exclude_all):
+        return (f & exclude_all) != exclude_all
+
+    def flag_pass(self, f, require, exclude, include_any, exclude_all):
+        """-f / -F / --rf / -G on FLAG values f (uint64): the last two are off at 0"""
+        ok = ((f & np.uint64(require)) == np.uint64(require)) & ((f & np.uint64(exclude)) == 0)
+        if include_any:
+            ok &= self.any_of(f, np.uint64(include_any))
+        if exclude_all:
+            ok &= self.all_of(f, np.uint64(exclude_all))
+        return ok
+
+    def masks(self, case):
+        return case["require"], case["exclude"], case.get("include_any", 0), case.get("exclude_all", 0)
+
+    def reads(self, case):
+        """False where no FLAG value at all passes the call's FLAG masks: such a call launches nothing and reads nothing.  Decided
+        by trying all 65,536 values, never by the library's reduction of the masks."""
+        return bool(self.flag_pass(_EVERY_FLAG, *self.masks(case)).any())
+
+    def mapq(self, case):
+        return case["mapq"]
+
+    def sel(self, case):
+        """bool[n], element j of the ARRAY at index j: the selection; every element where the kind takes none"""
+        return np.ones(case["n"], dtype=bool) if case["mask"] is None else case["mask"].astype(bool)
+
+    def passes(self, case):
+        """bool[n]: pass(j), the predicate alone"""
+        low = case["array"].view(UNSIGNED[case["W"]]).astype(np.uint64) & np.uint64(0xFFFF)
+        ok = self.flag_pass(low, *self.masks(case))
+        if case["min_mapq"] > 0:
+            ok &= self.mapq(case) >= case["min_mapq"]
+        return ok
+
+    def segment(self, offsets, i):
+        return int(offsets[i]), int(offsets[i + 1])
+
+    def selected(self, sel, counted):
+        """the number counted -- not the number selected"""
+        return int(counted.sum())
+
+    def high(self, case, above, sel, counted):
+        """OR over the selected elements, passing or not; a kind without a selection selects every element"""
+        return np.bitwise_or.reduce(above[sel]) if sel.any() else np.uint64(0)
+
+    def unread_high(self, case, above):
+        return np.uint64(0)
+
+
+def passing(case, d=None):
+    """bool[n]: counted(j) = pass(j) && sel(j)"""
+    d = d or Definition()
+    ok = d.passes(case) & d.sel(case)
+    assert ok.shape == (case["n"],)
     return ok
 
 
-def reference(case):
+def reference(case, d=None):
     """{"rows": uint64[nseg, 32] with the superset slots, "selected": uint64[nseg], "high": uint64[nseg], "length": uint64[nseg]}"""
     import oracle
+    d = d or Definition()
     W = case["W"]
     u = case["array"].view(UNSIGNED[W])
     o = segments_of(case)
     nseg = o.size - 1
     rows, selected, high = np.zeros((nseg, 32), dtype=np.uint64), np.zeros(nseg, dtype=np.uint64), np.zeros(nseg, dtype=np.uint64)
     length = np.diff(o).astype(np.uint64)
-    if case["require"] & case["exclude"]:
-        return {"rows": rows, "selected": selected, "high": high, "length": length}     # no element is read
-    ok = passing(case)
     above = u.astype(np.uint64) & ~np.uint64(0xFFFF)
+    if not d.reads(case):
+        high[:] = d.unread_high(case, above)
+        return {"rows": rows, "selected": selected, "high": high, "length": length}     # no element is read
+    ok, sel = passing(case, d), d.sel(case)
     for i in range(nseg):
-        a, b = int(o[i]), int(o[i + 1])
+        a, b = d.segment(o, i)
         if b <= a:
             continue
         seg = u[a:b]
@@ -258,9 +479,9 @@ def reference(case):
             rows[i] = oracle.flagstat_c(low)
             pair_all = oracle.samtools_counts(low)["n_pair_all"]
             rows[i, 0], rows[i, 16] = pair_all[0], pair_all[1]
-        selected[i] = low.size
+        selected[i] = d.selected(sel[a:b], ok[a:b])
         rows[i, 9] = np.uint64(low.size) - rows[i, 25]
-        high[i] = np.bitwise_or.reduce(above[a:b])
+        high[i] = d.high(case, above[a:b], sel[a:b], ok[a:b])
     return {"rows": rows, "selected": selected, "high": high, "length": length}
 
 
@@ -354,19 +575,49 @@ def expected_images(case, ref):
 
 
 def fixed_case(kind, form, array, mode, mask=None, sel_offset=0, require=0, exclude=0, mapq=None, min_mapq=0, offsets=None, phase=0,
-               mapq_align=0, sel_align=0, selected_at="together", high_at="together", index=-1):
+               mapq_align=0, sel_align=0, selected_at="together", high_at="together", index=-1, sel_bits=None, include_any=0,
+               exclude_all=0):
     """a case that is stated, not drawn: the dict that reference / expected / the images above take, for the tests with a fixed
-    sequence of calls"""
+    sequence of calls.  A later kind (LATER_KINDS) with a selection states its `sel_bits`; an rf kind its --rf / -G masks."""
     array = np.ascontiguousarray(array)
     W = array.dtype.itemsize
-    assert kind in KINDS and form in FORMS and (W == 2) == (kind not in WIDE) and phase % W == 0
-    assert (mask is not None) == (kind in ("where_bitmap", "where_bytes")) and (offsets is not None) == (kind in SEGMENTED)
-    assert kind in FILTERED or (require == exclude == min_mapq == 0 and mapq is None)
-    return {"index": index, "kind": kind, "family": family(kind), "form": form, "skip": None, "W": W, "dtype": array.dtype.name, "grid": None,
+    assert kind in KINDS + LATER_KINDS and form in FORMS and (W == 2) == (kind not in WIDE + LATER_WIDE) and phase % W == 0
+    if kind in LATER_KINDS:
+        assert (mask is not None) == (kind in MASKED) == (sel_bits in (1, 8)) and (offsets is not None) == (kind in LATER_SEGMENTED)
+        assert kind in LATER_FILTERED or (require == exclude == min_mapq == 0 and mapq is None)
+        assert kind in RF or include_any == exclude_all == 0
+        later = {"sel_bits": sel_bits, "include_any": include_any, "exclude_all": exclude_all, "rf_outcome": None}
+    else:
+        assert (mask is not None) == (kind in ("where_bitmap", "where_bytes")) and (offsets is not None) == (kind in SEGMENTED)
+        assert kind in FILTERED or (require == exclude == min_mapq == 0 and mapq is None)
+        assert sel_bits is None and include_any == exclude_all == 0
+        later = {}
+    return {**later,
+            "index": index, "kind": kind, "family": family(kind), "form": form, "skip": None, "W": W, "dtype": array.dtype.name, "grid": None,
             "chunk_flags": None, "policy": None, "n": array.size, "n_cluster": None, "phase": phase, "mapq_align": mapq_align,
             "sel_align": sel_align, "big_offset": False, "sel_offset": sel_offset, "values": "fixed", "high_style": None, "array": array,
             "require": require, "exclude": exclude, "min_mapq": min_mapq, "mapq": mapq, "mapq_null": mapq is None,
             "mask": None if mask is None else np.asarray(mask, dtype=bool),
             "offsets": None if offsets is None else np.asarray(offsets, dtype=np.int64), "layout": "fixed" if offsets is not None else None,
             "nseg": 1 if offsets is None else len(offsets) - 1, "mode": mode,
-            "selected_at": selected_at if kind in SELECTING else None, "high_at": high_at if kind in WIDE else None}
+            "selected_at": selected_at if kind in SELECTING + LATER_KINDS else None,
+            "high_at": high_at if kind in WIDE + LATER_WIDE else None}
+
+
+def sel_bits_of(case):
+    """1, 8 or None: the encoding of the case's selection"""
+    if case["mask"] is None:
+        return None
+    return case["sel_bits"] if "sel_bits" in case else 1 if case["kind"] == "where_bitmap" else 8
+
+
+def selection_image(case):
+    """(uint8 image, offset in it of the byte the selection pointer names) of the case's selection in its encoding, between poison:
+    bitmap_image for a bitmap; for a byte mask bytes_image of non-zero values other than 1 (1 + n % 255), element 0 at byte
+    sel_offset from the pointer on.  The offset may be negative: a bitmap offset of 2^33 + k moves the pointer 2^30 bytes back."""
+    if sel_bits_of(case) == 1:
+        img, at, back = bitmap_image(case)
+        return img, at - back
+    img, at = bytes_image(case["mask"].astype(np.uint8) * np.uint8(1 + case["n"] % 255), case["sel_align"])
+    assert case["sel_offset"] <= at
+    return img, at - case["sel_offset"]

@@ -13,6 +13,8 @@ slot indicators of the kept elements, ``selected`` and the high bits are built o
 ``[b, e)`` then reads as ``(t // L) * pre[L] + pre[t % L]`` at both ends.  No flag of F has bit 0x400 or 0x200, so the background
 leaves slot 10, slot 25 and every slot 16..31 at zero; a needle sets one of the two and carries a high bit that no H entry has,
 so every needle shows exactly.  The expectation is the background, minus the background at every needle's index, plus the needle.
+The predicate is samtools' whole one: ``include_any`` / ``exclude_all`` (--rf / -G) are off at 0, which every unit but the two rf
+units passes.
 
 ``expect`` also takes index maps -- where an element, a selection bit or byte and a MAPQ byte are really read from.  ``wrapped``
 makes the maps of an index held in 32 bits; they model a kernel that is subtly wrong, so that a CPU test can show that the GPU
@@ -63,10 +65,32 @@ def map_indices(pieces, idx) -> np.ndarray:
     return out
 
 
+_SATISFIABLE = {}
+
+
+def flag_pass(flag, require, exclude, include_any=0, exclude_all=0):
+    """bool[m]: -f / -F / --rf / -G on uint16 flags; the last two are off at 0"""
+    ok = ((flag & np.uint16(require)) == np.uint16(require)) & ((flag & np.uint16(exclude)) == 0)
+    if include_any:
+        ok &= (flag & np.uint16(include_any)) != 0
+    if exclude_all:
+        ok &= (flag & np.uint16(exclude_all)) != np.uint16(exclude_all)
+    return ok
+
+
+def satisfiable(require, exclude, include_any=0, exclude_all=0) -> bool:
+    """does any of the 65,536 FLAG values pass the four masks?  By trying them all, not by reducing the masks."""
+    key = (require, exclude, include_any, exclude_all)
+    if key not in _SATISFIABLE:
+        _SATISFIABLE[key] = bool(flag_pass(np.arange(65536, dtype=np.uint32).astype(np.uint16), *key).any())
+    return _SATISFIABLE[key]
+
+
 class Result:
     """rows uint64[nseg, 32], selected uint64[nseg], and ``high`` under both rules: ``high_read`` is the OR of the bits above 15
     over every element of the segment (the plain and the filtered entries), ``high_selected`` over the selected ones, passing or
-    not (the masked and the combined entries).  All are zero when ``require & exclude != 0``."""
+    not (the masked and the combined entries).  All are zero when no FLAG value can pass (``require & exclude != 0``, or --rf / -G
+    masks that leave none)."""
 
     def __init__(self, rows, selected, high_read, high_selected):
         self.rows, self.selected, self.high_read, self.high_selected = rows, selected, high_read, high_selected
@@ -104,10 +128,10 @@ class Column:
         self._tables = {}
 
     # ------------------------------------------------------------------ single elements
-    def _indicators(self, flag, hb, sel, q, require, exclude, min_mapq, masked):
+    def _indicators(self, flag, hb, sel, q, require, exclude, min_mapq, masked, include_any=0, exclude_all=0):
         """(row, bool[m]) pairs: which of m elements add 1 to which row of a table (rows without a pair stay 0)"""
         flag = np.ascontiguousarray(flag, dtype=np.uint16)
-        ok = ((flag & np.uint16(require)) == np.uint16(require)) & ((flag & np.uint16(exclude)) == 0)
+        ok = flag_pass(flag, require, exclude, include_any, exclude_all)
         if min_mapq > 0:
             ok &= np.asarray(q) >= min_mapq
         pick = np.asarray(sel, dtype=bool) if masked else np.ones(flag.shape, dtype=bool)
@@ -128,14 +152,14 @@ class Column:
             out[row] = m
         return out
 
-    def _table(self, pf, ph, ps, pq, require, exclude, min_mapq, masked):
+    def _table(self, pf, ph, ps, pq, require, exclude, min_mapq, masked, include_any=0, exclude_all=0):
         """int32[rows, JOINT + 1]: prefix sums of ``_contrib`` over one joint period of the background whose element t has flag
         F[(t + pf) % 977], high bits H[(t + ph) % 13], selection S[(t + ps) % 61] and MAPQ Q[(t + pq) % 13]"""
         if not masked:
             ps = 0
         if min_mapq == 0:
             pq = 0
-        key = (pf, ph, ps, pq, require, exclude, min_mapq, masked)
+        key = (pf, ph, ps, pq, require, exclude, min_mapq, masked, include_any, exclude_all)
         if key in self._tables:
             self._tables[key] = self._tables.pop(key)         # most recently used: last
         else:
@@ -143,7 +167,8 @@ class Column:
                 self._tables.pop(next(iter(self._tables)))
             tile = lambda p, shift: np.tile(np.roll(p, -shift), JOINT // p.size)  # noqa: E731
             tab = np.zeros((self.rows, JOINT + 1), dtype=np.int32)
-            for row, m in self._indicators(tile(self.F, pf), tile(self.H, ph), tile(self.S, ps), tile(self.Q, pq), require, exclude, min_mapq, masked):
+            for row, m in self._indicators(tile(self.F, pf), tile(self.H, ph), tile(self.S, ps), tile(self.Q, pq), require, exclude, min_mapq, masked,
+                                           include_any, exclude_all):
                 np.cumsum(m, dtype=np.int32, out=tab[row, 1:])
             self._tables[key] = tab
         return self._tables[key]
@@ -176,18 +201,21 @@ class Column:
 
     # ------------------------------------------------------------------ the expectation
     def expect(self, offsets, require: int = 0, exclude: int = 0, min_mapq: int = 0, masked: bool = False, sel_offset: int = 0,
-               superset: bool = False, array_map=IDENTITY, sel_map=IDENTITY, mapq_map=IDENTITY) -> Result:
+               superset: bool = False, array_map=IDENTITY, sel_map=IDENTITY, mapq_map=IDENTITY, include_any: int = 0,
+               exclude_all: int = 0) -> Result:
         """What a call over the segments ``offsets`` (element indices into this column, clamped to [0, n] as the kernels clamp
         them; a segment whose end lies before its begin is empty) must report.  ``masked``: the call takes a selection, element j
         being bit or byte ``sel_offset + j``.  The maps say where element j's value (``array_map``, in elements), its selection
-        bit or byte (``sel_map``, applied to ``sel_offset + j``) and its MAPQ (``mapq_map``) are read from."""
+        bit or byte (``sel_map``, applied to ``sel_offset + j``) and its MAPQ (``mapq_map``) are read from.  ``include_any`` /
+        ``exclude_all``: samtools' --rf / -G, off at 0; FLAG masks that no 16-bit value satisfies read nothing, like an
+        overlapping pair."""
         o = np.clip(np.asarray(offsets, dtype=np.int64).ravel(), 0, self.n)
         b, e = o[:-1], np.maximum(o[1:], o[:-1])
         nseg = b.size
         zero = lambda: np.zeros(nseg, dtype=np.uint64)  # noqa: E731
-        if require & exclude or nseg == 0:
+        if not satisfiable(require, exclude, include_any, exclude_all) or nseg == 0:
             return Result(np.zeros((nseg, 32), dtype=np.uint64), zero(), zero(), zero())
-        pred = (require, exclude, min_mapq, masked)
+        pred = (require, exclude, min_mapq, masked, include_any, exclude_all)
         acc = np.zeros((self.rows, nseg), dtype=np.int64)
         cuts = sorted({0, INF} | {lo for lo, _, _ in array_map} | {lo for lo, _, _ in mapq_map}
                       | {max(lo - sel_offset, 0) for lo, _, _ in sel_map})
@@ -400,9 +428,45 @@ def call_key(call: dict, filt: bool, mask: bool) -> tuple:
 def reduced(call: dict, filt: bool, mask: bool) -> dict:
     """the keyword arguments of ``Column.expect`` for a kernel with / without a filter and a selection"""
     require, exclude, min_mapq = call["pred"] if filt else (0, 0, 0)
-    return dict(require=require, exclude=exclude, min_mapq=min_mapq, masked=mask, sel_offset=call["sel_offset"] if mask else 0)
+    include_any, exclude_all = call.get("rf", (0, 0)) if filt else (0, 0)
+    return dict(require=require, exclude=exclude, min_mapq=min_mapq, masked=mask, sel_offset=call["sel_offset"] if mask else 0,
+                include_any=include_any, exclude_all=exclude_all)
 
 
 HOST_OFFSETS = {2: (5, 1000, (1 << 31) + 7, (1 << 32) - 3, (1 << 32) + 2, HOST_N - 2), 8: (0, HOST_WIDE_N)}
 HOST_CALL = dict(pred=(0, 0, 30), form="bitmap", sel_offset=3, local=False)      # a bitmap at an odd offset, -q 30
 DENSE_CALL = dict(pred=(0, 0, 1), form="bitmap", sel_offset=0, local=False)      # one workgroup: everything passes -q 1
+
+
+# ------------------------------------------------------------------ the two units of the whole predicate (--rf / -G)
+# (require, exclude, include_any, exclude_all, min_mapq): -F 0x904 --rf 0x60 -G 0x3 leaves both tests to the kernel (0x60 and 0x3
+# share no bit with 0x904); the second has -q 30 on top.  Of the eleven NEEDLE_FLAGS six have bit 5 or 6 and five neither; six
+# have bits 0 and 1 both and five do not.
+RF_PREDICATES = ((0, 0x904, 0x60, 0x3, 0), (0, 0x904, 0x60, 0x3, 30))
+# one workgroup: --rf of every bit a background flag can have, -G of the same -- all but a few background flags pass -- and -q 1
+RF_DENSE = (0, 0, 0xF9FF, 0xF9FF, 1)
+
+
+def rf_call(pred, offsets, case, layout) -> dict:
+    """a call of the flat rf units over [offsets[0], offsets[1]) in the form of slab_calls: no selection"""
+    require, exclude, include_any, exclude_all, min_mapq = pred
+    return dict(case=case, layout=layout, offsets=np.asarray(offsets, dtype=np.int64), pred=(require, exclude, min_mapq),
+                rf=(include_any, exclude_all), form="bytes", sel_offset=0, local=False)
+
+
+def rf_slab_calls(W: int) -> list:
+    """the calls of u16_filter_rf / wide_filter_rf over the resident slab of width W: the whole slab and the window that begins
+    past the mark, under both RF_PREDICATES"""
+    n = slab_n(W)
+    start, m = window(W)
+    return ([rf_call(p, (0, n), "rf-whole-p%d" % i, "whole") for i, p in enumerate(RF_PREDICATES)]
+            + [rf_call(p, (start, start + m), "rf-window-p%d" % i, "window") for i, p in enumerate(RF_PREDICATES)])
+
+
+def needle_rf_predicate(flag: int) -> tuple:
+    """a residue predicate with -q 60 (NEEDLE_MAPQ: no background element passes) that, of the NEEDLE_FLAGS, only `flag` passes:
+    -f / -F fix bits 0..8 and 11 to the needle's; 0x443 and 0x643 differ in bit 9 alone, which --rf and -G tell: a needle with
+    one of bits 9 and 10 passes --rf 0x600 -G 0x600, one with both --rf 0x1200 -G 0x5000"""
+    low = flag & 0x9FF
+    one = bin(flag & 0x600).count("1") == 1
+    return (low, 0x9FF & ~low, 0x600 if one else 0x1200, 0x600 if one else 0x5000, NEEDLE_MAPQ)

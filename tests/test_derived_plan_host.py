@@ -1,5 +1,7 @@
 """CPU: the case plan and the reference of the randomized sweep over the derived kernels (tests/derived_plan.py) -- the reference
 against the per-kernel oracles, the plan's determinism, what the default plan covers, and that it skips nothing.  No GPU."""
+import ctypes
+import hashlib
 import os
 import sys
 import time
@@ -10,12 +12,21 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import derived_plan as dp  # noqa: E402
 import filter_oracle  # noqa: E402
+import filter_rf_oracle  # noqa: E402
+import filter_where_oracle  # noqa: E402
+import segments_filter_where_oracle  # noqa: E402
 import segments_filter_oracle  # noqa: E402
 import segments_oracle  # noqa: E402
 import segments_wide_filter_oracle  # noqa: E402
+import segments_where_oracle  # noqa: E402
+import segments_wide_filter_where_oracle  # noqa: E402
 import segments_wide_oracle  # noqa: E402
+import segments_wide_where_oracle  # noqa: E402
 import where_oracle  # noqa: E402
 import wide_filter_oracle  # noqa: E402
+import wide_filter_rf_oracle  # noqa: E402
+import wide_filter_where_oracle  # noqa: E402
+import wide_where_oracle  # noqa: E402
 
 SEED = 20261019
 DEFAULT_ITERS = 240
@@ -207,3 +218,315 @@ def test_input_images_hold_the_inputs_between_poison(planned):
             assert 0 <= local < 64 and np.array_equal(bits[local:local + n].astype(bool), c["mask"])
             assert bits[:local].all() and bits[local + n:].all() and (b[:ba] == 0xFF).all()
             assert np.array_equal(where_oracle.pack(c["mask"], local), b[ba:ba + (local + n + 7) // 8])
+
+
+# ------------------------------------------------------------------ the old plan is what it was
+PLAN_DIGEST = "7f53b51ff32d1c7c94ca21df9c5291ea9ad9ee631bca4d1057d8d9868f1743f3"   # taken before plan_later was written
+
+
+def test_plan_is_byte_for_byte_what_it_was(planned):
+    """sha256 over every case's describe() and the bytes of its array, mapq, mask and offsets: sharing _draw's pieces with
+    plan_later has not moved one draw of plan()"""
+    h = hashlib.sha256()
+    for c in planned[0]:
+        h.update(repr(dp.describe(c)).encode())
+        for k in ("array", "mapq", "mask", "offsets"):
+            if c[k] is not None:
+                h.update(np.ascontiguousarray(c[k]).tobytes())
+    assert h.hexdigest() == PLAN_DIGEST
+
+
+# ------------------------------------------------------------------ the later plan: the nine units derived afterwards
+LATER_SEED = 20261021
+MASKED_WIDE = tuple(k for k in dp.MASKED if k in dp.LATER_WIDE)
+MASKED_SEGMENTED = tuple(k for k in dp.MASKED if k in dp.LATER_SEGMENTED)
+MASKED_FLAT = tuple(k for k in dp.MASKED if k not in dp.LATER_SEGMENTED)
+MASKED_FILTERED = tuple(k for k in dp.MASKED if k in dp.LATER_FILTERED)
+
+
+@pytest.fixture(scope="module")
+def planned_later(oracle_mod):
+    """planned, of plan_later(LATER_SEED, 300)"""
+    cases = dp.plan_later(LATER_SEED, 300)
+    refs, spent = [], 0.0
+    for c in cases:
+        t0 = time.perf_counter()
+        refs.append(dp.reference(c))
+        if c["index"] < DEFAULT_ITERS:
+            spent += time.perf_counter() - t0
+    return cases, refs, spent
+
+
+def later_oracle_of(oracle_mod, c):
+    """oracle_of for LATER_KINDS: (rows[nseg, 32], selected[nseg], high[nseg] or None) by the kernel's own oracle, superset form"""
+    kind, m, o = c["kind"], c["mask"], c["offsets"]
+    pred = (c["require"], c["exclude"], c["mapq"], c["min_mapq"])
+    rf = (c["require"], c["exclude"], c["include_any"], c["exclude_all"], c["mapq"], c["min_mapq"])
+    one = lambda v: np.array([v], dtype=np.uint64)  # noqa: E731
+    if kind == "segments_where":
+        return segments_where_oracle.want(low16(c), o, m, True) + (None,)
+    if kind == "wide_where":
+        rows, sel, high = wide_where_oracle.want(oracle_mod, c["array"], m, True)
+        return rows[None, :], one(sel), one(high)
+    if kind == "wide_segments_where":
+        return segments_wide_where_oracle.want(c["array"], o, m, True)
+    if kind == "filter_where":
+        rows, sel = filter_where_oracle.want_counters(oracle_mod, low16(c), m, *pred, True)
+        return rows[None, :], one(sel), None
+    if kind == "segments_filter_where":
+        return segments_filter_where_oracle.want(low16(c), o, m, *pred, True) + (None,)
+    if kind == "wide_filter_where":
+        rows, sel, high = wide_filter_where_oracle.want(oracle_mod, c["array"], m, *pred, True)
+        return rows[None, :], one(sel), one(high)
+    if kind == "wide_segments_filter_where":
+        return segments_wide_filter_where_oracle.want(c["array"], o, m, *pred, True)
+    if kind == "filter_rf":
+        rows, sel = filter_rf_oracle.want_counters(oracle_mod, low16(c), *rf, True)
+        return rows[None, :], one(sel), None
+    assert kind == "wide_filter_rf"
+    rows, sel, high = wide_filter_rf_oracle.want(oracle_mod, c["array"], *rf, True)
+    return rows[None, :], one(sel), one(high)
+
+
+def test_later_reference_agrees_with_the_per_kernel_oracles(oracle_mod, planned_later):
+    cases, refs, _ = planned_later
+    assert len(cases) == 300 and {c["kind"] for c in cases} == set(dp.LATER_KINDS)
+    for c, r in zip(cases, refs):
+        rows, sel, high = later_oracle_of(oracle_mod, c)
+        what = dp.describe(c)
+        assert rows.shape == r["rows"].shape and np.array_equal(rows, r["rows"]), what
+        assert np.array_equal(np.asarray(sel, dtype=np.uint64), r["selected"]), what
+        if high is not None:
+            assert np.array_equal(np.asarray(high, dtype=np.uint64), r["high"]), what
+        else:
+            assert not r["high"].any(), what
+        if c["require"] & c["exclude"] or c["rf_outcome"] == "empty":
+            assert not r["rows"].any() and not r["selected"].any() and not r["high"].any(), what
+
+
+def test_later_plan_is_deterministic_and_prefix_closed(planned_later):
+    cases = planned_later[0]
+    for k in (0, 1, 35, 36, 37, 80):
+        shorter, longer = dp.plan_later(LATER_SEED, k), dp.plan_later(LATER_SEED, k + 1)
+        assert len(shorter) == k and len(longer) == k + 1
+        for a, b in zip(shorter, longer):
+            same_case(a, b)
+        for a, b in zip(longer, cases):
+            same_case(a, b)
+    assert any(a["n"] != b["n"] for a, b in zip(dp.plan_later(LATER_SEED + 1, 10), cases))
+
+
+def rf_outcome(reduce_, c):
+    """which of dp.RF_OUTCOMES the library's host reduction makes of the case's four masks: a classification of the case for the
+    coverage floors below, never an expected value"""
+    out = (ctypes.c_uint32 * 4)()
+    rc = reduce_(c["require"], c["exclude"], c["include_any"], c["exclude_all"], out)
+    return ("empty", "pair", ("any" if out[2] else "all") if not (out[2] and out[3]) else "both")[rc]
+
+
+def high_over(c, which):
+    """OR of the bits above bit 15 over the whole array (which is None) or over the elements `which` marks"""
+    above = c["array"].view(dp.UNSIGNED[c["W"]]).astype(np.uint64) & ~np.uint64(0xFFFF)
+    return int(np.bitwise_or.reduce(above if which is None else above[which])) if above.size else 0
+
+
+def test_later_plan_covers_what_it_is_for(planned_later):
+    from libflagstats_amd import _lib
+    reduce_ = _lib.lib().fsk_filter_rf_reduce
+    cases, refs, _ = planned_later
+    cases, refs = cases[:DEFAULT_ITERS], refs[:DEFAULT_ITERS]
+    count = lambda pred: sum(1 for c in cases if pred(c))  # noqa: E731
+    for kind in dp.LATER_KINDS:
+        for form in dp.FORMS:
+            assert count(lambda c: c["kind"] == kind and c["form"] == form) >= 3, (kind, form)
+    for kind in dp.MASKED:
+        for bits in (1, 8):
+            assert count(lambda c: c["kind"] == kind and c["sel_bits"] == bits) >= 3, (kind, bits)
+            for form in dp.FORMS:
+                assert count(lambda c: c["kind"] == kind and c["sel_bits"] == bits and c["form"] == form) >= 1, (kind, bits, form)
+    for kind in dp.RF:
+        seen = [rf_outcome(reduce_, c) for c in cases if c["kind"] == kind]
+        assert seen == [c["rf_outcome"] for c in cases if c["kind"] == kind], kind      # the plan dealt what the reduction finds
+        for outcome in dp.RF_OUTCOMES:
+            assert seen.count(outcome) >= 3, (kind, outcome)
+        assert any((c["include_any"] | c["exclude_all"]) & 0xFF00 for c in cases if c["kind"] == kind), kind
+    for kind in MASKED_FLAT:
+        assert count(lambda c: c["kind"] == kind and c["big_offset"]) >= 1, kind
+    for kind in MASKED_WIDE:
+        mine = [c for c in cases if c["kind"] == kind and not c["require"] & c["exclude"]]
+        assert sum(1 for c in mine if high_over(c, None) != high_over(c, c["mask"])) >= 3, kind
+        ones = [c for c in mine if c["high_style"] == "one" and c["n"] >= 3]
+        assert any(high_over(c, c["mask"]) == 0 for c in ones) and any(high_over(c, c["mask"]) != 0 for c in ones), kind
+    for kind in MASKED_SEGMENTED:
+        assert count(lambda c: c["kind"] == kind and c["offsets"][0] > 0) >= 3, kind
+    # what test_default_plan_covers_what_it_is_for asserts of the old plan, where it applies
+    for W in (2, 4, 8):
+        assert count(lambda c: c["W"] == W) >= 5, W
+    for mode in range(4):
+        assert count(lambda c: c["mode"] == mode) >= 5, mode
+    for grid in dp.GRIDS:
+        assert count(lambda c: c["grid"] == grid) >= 5, grid
+    for chunk in dp.CHUNKS:
+        assert count(lambda c: c["chunk_flags"] == chunk) >= 5, chunk
+    for mu in dp.MIN_UNITS:
+        assert count(lambda c: c["policy"] is not None and c["policy"][0] == mu) >= 1, mu
+    for name in ("int16", "uint16", "int32", "uint32", "int64", "uint64"):
+        assert count(lambda c: c["dtype"] == name) >= 5, name
+    assert count(lambda c: c["sel_bits"] == 1 and c["sel_offset"] & 7) >= 5 and count(lambda c: c["sel_bits"] == 8 and c["sel_offset"] & 1) >= 5
+    assert {c["n_cluster"] for c in cases} == {0, 1, 2, 3} and max(c["n"] for c in cases) <= dp.CAP
+    assert sum(c["n"] for c in cases) < 40_000_000
+    # every later kind selects: a selection partly taken in some segment in all but 15 % of the cases
+    partial = [bool(((r["selected"] > 0) & (r["selected"] < r["length"])).any()) for r in refs]
+    assert sum(partial) >= 0.85 * len(cases), (sum(partial), len(cases))
+    overlapping = count(lambda c: bool(c["require"] & c["exclude"]) and c["kind"] not in dp.RF)
+    assert 1 <= overlapping <= DEFAULT_ITERS // 12
+    for kind in dp.LATER_WIDE:
+        mine = [(c, r) for c, r in zip(cases, refs) if c["kind"] == kind and not c["require"] & c["exclude"]]
+        if kind in dp.LATER_SEGMENTED:    # masks in some but not all segments of one call
+            assert sum(1 for c, r in mine if r["high"].any() and (r["high"][r["length"] > 0] == 0).any()) >= 3, kind
+        assert any(r["high"].any() for c, r in mine) and any(not r["high"].any() and c["n"] for c, r in mine), kind
+        assert any(int(r["high"].max()) >> (8 * c["W"] - 1) for c, r in mine), (kind, "the sign bit")
+    for kind in dp.LATER_SEGMENTED:
+        mine = [c for c in cases if c["kind"] == kind]
+        assert any((np.diff(c["offsets"]) == 0).any() and (np.diff(c["offsets"]) > 0).any() for c in mine), kind
+        assert any(c["offsets"][0] > 0 for c in mine) and any(c["offsets"][-1] < c["n"] for c in mine), kind
+        assert {c["nseg"] for c in mine} == set(dp.NSEGS), kind
+        assert {c["layout"] for c in mine} == {"random", "units", "runs"}, kind
+        assert any((np.diff(c["offsets"]) >= 2 * 8192 // c["W"]).any() for c in mine), (kind, "a segment of chain length")
+    for at in dp.PLACEMENTS:
+        assert count(lambda c: c["selected_at"] == at) >= 5 and count(lambda c: c["high_at"] == at) >= 5, at
+
+
+def test_no_later_case_is_skipped(planned_later):
+    cases = planned_later[0]
+    assert dp.skip_reasons(cases[:DEFAULT_ITERS]) == []
+    assert all(c["skip"] is None for c in cases)
+    for c in cases:
+        if c["form"] == "host":
+            assert c["n"] <= dp.MAX_CHUNKS * max(2, c["chunk_flags"] * 2 // c["W"])
+        assert not c["big_offset"] or (c["sel_bits"] == 1 and c["form"] in ("launcher", "host") and c["sel_offset"] >> 33 == 1)
+
+
+def test_reference_of_the_later_plan_is_quick(planned_later):
+    assert planned_later[2] < 20.0, planned_later[2]
+
+
+# ------------------------------------------------------------------ what the later plan would notice: a table of wrong models
+class HighOverAll(dp.Definition):
+    high = lambda self, case, above, sel, counted: np.bitwise_or.reduce(above)  # noqa: E731
+
+
+class HighOverCounted(dp.Definition):
+    high = lambda self, case, above, sel, counted: np.bitwise_or.reduce(above[counted]) if counted.any() else np.uint64(0)  # noqa: E731
+
+
+class SelectionBySegment(dp.Definition):
+    def sel(self, case):
+        m, o = case["mask"].copy(), case["offsets"]
+        for a, b in zip(o[:-1], o[1:]):
+            m[a:b] = case["mask"][:b - a]       # bit sel_offset + (j - offsets[i])
+        return m
+
+
+class SelectionFromItsByte(dp.Definition):
+    sel = lambda self, case: np.concatenate([np.ones(case["sel_offset"] & 7, dtype=bool), case["mask"]])[:case["n"]]  # noqa: E731
+
+
+class SelectionOneOn(dp.Definition):
+    sel = lambda self, case: np.append(case["mask"][1:], True)[:case["n"]]  # noqa: E731
+
+
+class SelectionByteAndOne(dp.Definition):
+    sel = lambda self, case: case["mask"] & bool(case["sel_bits"] == 1 or (1 + case["n"] % 255) & 1)  # noqa: E731
+
+
+class MapqOneOn(dp.Definition):
+    mapq = lambda self, case: np.append(case["mapq"][1:], np.uint8(255))[:case["n"]]  # noqa: E731
+
+
+class SelectedIsTheSelection(dp.Definition):
+    selected = lambda self, sel, counted: int(sel.sum())  # noqa: E731
+
+
+class SegmentOneLate(dp.Definition):
+    segment = lambda self, offsets, i: (int(offsets[i]) + 1, int(offsets[i + 1]))  # noqa: E731
+
+
+class AnyOfAsAllOf(dp.Definition):
+    any_of = lambda self, f, include_any: (f & include_any) == include_any  # noqa: E731
+
+
+class AllOfAsExclude(dp.Definition):
+    all_of = lambda self, f, exclude_all: (f & exclude_all) == 0  # noqa: E731
+
+
+class AnyOfLowByte(dp.Definition):
+    masks = lambda self, c: (c["require"], c["exclude"], c["include_any"] & 0xFF, c["exclude_all"])  # noqa: E731
+
+
+class AllOfLowByte(dp.Definition):
+    masks = lambda self, c: (c["require"], c["exclude"], c["include_any"], c["exclude_all"] & 0xFF)  # noqa: E731
+
+
+class UnreadColumnReported(dp.Definition):
+    unread_high = lambda self, case, above: np.bitwise_or.reduce(above) if above.size else np.uint64(0)  # noqa: E731
+
+
+WRONG_MODELS = (
+    ("high over all elements", HighOverAll, MASKED_WIDE),
+    ("high over the counted elements only", HighOverCounted, ("wide_filter_where", "wide_segments_filter_where", "wide_filter_rf")),
+    ("selection read at sel_offset + (j - offsets[i])", SelectionBySegment, MASKED_SEGMENTED),
+    ("selection bit (sel_offset & ~7) + j", SelectionFromItsByte, dp.MASKED),
+    ("selection bit sel_offset + j + 1", SelectionOneOn, dp.MASKED),
+    ("a selection byte tested as byte & 1", SelectionByteAndOne, dp.MASKED),
+    ("MAPQ of element j taken from j + 1", MapqOneOn, dp.LATER_FILTERED),
+    ("selected as the number of selected elements", SelectedIsTheSelection, MASKED_FILTERED),
+    ("a segment starting one element late", SegmentOneLate, dp.LATER_SEGMENTED),
+    ("any-of evaluated as all-of", AnyOfAsAllOf, dp.RF),
+    ("all-of evaluated as an exclude", AllOfAsExclude, dp.RF),
+    ("include_any & 0xFF", AnyOfLowByte, dp.RF),
+    ("exclude_all & 0xFF", AllOfLowByte, dp.RF),
+    ("an unsatisfiable rf predicate that still reports the column's high", UnreadColumnReported, ("wide_filter_rf",)),
+)
+
+
+@pytest.mark.parametrize("name,model,kinds", WRONG_MODELS, ids=[w[0] for w in WRONG_MODELS])
+def test_later_plan_notices_a_wrong_model(planned_later, name, model, kinds):
+    """the expected images of at least 5 cases of the default plan differ under each one-line variation of the reference"""
+    cases, refs, _ = planned_later
+    changed = []
+    for c, r in zip(cases[:DEFAULT_ITERS], refs):
+        if c["kind"] not in kinds:
+            continue
+        wrong = dp.expected_images(c, dp.reference(c, model()))
+        if any(not np.array_equal(a, b) for a, b in zip(dp.expected_images(c, r), wrong)):
+            changed.append(c["index"])
+    assert len(changed) >= 5, (name, changed)
+
+
+def test_later_input_images_hold_the_inputs_between_poison(planned_later):
+    seen = set()
+    for c in planned_later[0][:120]:
+        img, at = dp.array_image(c)
+        W, n = c["W"], c["n"]
+        assert at % 16 == c["phase"] and img[at:at + n * W].tobytes() == c["array"].tobytes()
+        assert (img[:at] == 0xFF).all() and (img[at + n * W:] == 0xFF).all() and at >= 64 * W and img.size - at - n * W >= 64 * W
+        if c["mapq"] is not None:
+            q, qa = dp.bytes_image(c["mapq"], c["mapq_align"])
+            assert qa % 16 == c["mapq_align"] and np.array_equal(q[qa:qa + n], c["mapq"]) and (q[:qa] == 0xFF).all() and (q[qa + n:] == 0xFF).all()
+        if c["mask"] is None:
+            assert dp.sel_bits_of(c) is None
+            continue
+        seen.add((c["sel_bits"], c["mapq"] is not None))
+        s, (b, ptr) = c["sel_offset"], dp.selection_image(c)
+        first = ptr + (s // 8 if c["sel_bits"] == 1 else s)        # the byte that holds element 0
+        packed = ptr if c["sel_bits"] == 1 and not c["big_offset"] else first     # a small bit offset lies within the packed bytes
+        assert packed % 16 == c["sel_align"] and 64 <= packed and (b[:packed] == 0xFF).all()
+        if c["sel_bits"] == 8:
+            assert ((b[first:first + n] != 0) == c["mask"]).all() and (b[first + n:] == 0xFF).all() and b.size - first - n >= 64
+            assert not (b[first:first + n] == 1).any() or n % 255 == 0
+        else:
+            bits = np.unpackbits(b[first:], bitorder="little")
+            assert np.array_equal(bits[s & 7:(s & 7) + n].astype(bool), c["mask"]) and bits[:s & 7].all() and bits[(s & 7) + n:].all()
+            assert (ptr < 0) == c["big_offset"]
+    assert seen == {(1, False), (1, True), (8, False), (8, True)}     # a case with a MAPQ column and a selection has both images

@@ -1,10 +1,12 @@
-"""GPU: the eight kernels derived from K1's step tree (where, filter, segments, segments_filter, wide, wide_filter, wide_segments,
-wide_segments_filter) under a randomized sweep, one after another over the engine's staging slots, and from several threads at
-once.  Cases, reference and the poisoned input / output images come from tests/derived_plan.py (checked on the CPU by
-tests/test_derived_plan_host.py); every comparison is exact, and every call is one the header documents as legal.
+"""GPU: the seventeen kernels derived from K1's step tree under a randomized sweep, one after another over the engine's staging
+slots, and from several threads at once -- the eight of the first family (where, filter, segments, segments_filter, wide,
+wide_filter, wide_segments, wide_segments_filter) and the nine derived later (derived_plan.LATER_KINDS: the masked kinds and the
+two of the whole predicate, --rf / -G), each family in tests of its own.  Cases, reference and the poisoned input / output images
+come from tests/derived_plan.py (checked on the CPU by tests/test_derived_plan_host.py); every comparison is exact, and every
+call is one the header documents as legal.
 
-To run one case of the sweep again: ``derived_plan.plan(SEED, index + 1)[index]`` -- a failure names the index and the drawn
-parameters."""
+To run one case of a sweep again: ``derived_plan.plan(SEED, index + 1)[index]``, or ``plan_later(LATER_SEED, index + 1)[index]``
+-- a failure names the index and the drawn parameters."""
 import ctypes
 import os
 import sys
@@ -19,23 +21,48 @@ import derived_plan as dp  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 SEED = 20261019     # tests/test_derived_plan_host.py checks this plan's coverage
+LATER_SEED = 20261021   # ... and that of dp.plan_later(LATER_SEED, ...), the nine later units
 
 # arguments of every entry, by name: A array, N n, W elem_bytes, S / SO / SB selection, its offset and encoding, R / X / Q / MQ
 # require, exclude, MAPQ column, min_mapq, O / NS offsets and nseg, OUT / SEL / HIGH outputs, Z a zero (the launchers' `base`)
 PUBLIC = {"where": "A N S SO SB OUT SEL MODE", "filter": "A N R X Q MQ OUT SEL MODE", "segments": "A N O NS OUT MODE",
           "segments_filter": "A N O NS R X Q MQ OUT SEL MODE", "wide": "A N W OUT HIGH MODE", "wide_filter": "A N W R X Q MQ OUT SEL HIGH MODE",
-          "wide_segments": "A N W O NS OUT HIGH MODE", "wide_segments_filter": "A N W O NS R X Q MQ OUT SEL HIGH MODE"}
+          "wide_segments": "A N W O NS OUT HIGH MODE", "wide_segments_filter": "A N W O NS R X Q MQ OUT SEL HIGH MODE",
+          # the nine later units: IA / XA include_any and exclude_all
+          "segments_where": "A N O NS S SO SB OUT SEL MODE", "wide_where": "A N W S SO SB OUT SEL HIGH MODE",
+          "wide_segments_where": "A N W O NS S SO SB OUT SEL HIGH MODE", "filter_where": "A N R X Q MQ S SO SB OUT SEL MODE",
+          "segments_filter_where": "A N O NS R X Q MQ S SO SB OUT SEL MODE", "wide_filter_where": "A N W R X Q MQ S SO SB OUT SEL HIGH MODE",
+          "wide_segments_filter_where": "A N W O NS R X Q MQ S SO SB OUT SEL HIGH MODE", "filter_rf": "A N R X IA XA Q MQ OUT SEL MODE",
+          "wide_filter_rf": "A N W R X IA XA Q MQ OUT SEL HIGH MODE"}
 LAUNCHER = {"where": ("fsk_launch_where", "A N S SO SB OUT SEL MODE GRID"), "filter": ("fsk_launch_filter", "A N R X Q MQ OUT SEL MODE GRID"),
             "segments": ("fsk_launch_segments", "A Z N O NS OUT MODE GRID"),
             "segments_filter": ("fsk_launch_segments_filter", "A Q Z N O NS R X MQ OUT SEL MODE GRID"),
             "wide": ("fsk_launch_wide", "A N W OUT HIGH MODE GRID"), "wide_filter": ("fsk_launch_wide_filter", "A N W R X Q MQ OUT SEL HIGH MODE GRID"),
             "wide_segments": ("fsk_launch_segments_wide", "A W Z N O NS OUT HIGH MODE GRID"),
-            "wide_segments_filter": ("fsk_launch_segments_wide_filter", "A W Q Z N O NS R X MQ OUT SEL HIGH MODE GRID")}
+            "wide_segments_filter": ("fsk_launch_segments_wide_filter", "A W Q Z N O NS R X MQ OUT SEL HIGH MODE GRID"),
+            "segments_where": ("fsk_launch_segments_where", "A S SO SB Z N O NS OUT SEL MODE GRID"),
+            "wide_where": ("fsk_launch_wide_where", "A N W S SO SB OUT SEL HIGH MODE GRID"),
+            "wide_segments_where": ("fsk_launch_segments_wide_where", "A W S SO SB Z N O NS OUT SEL HIGH MODE GRID"),
+            "filter_where": ("fsk_launch_filter_where", "A N R X Q MQ S SO SB OUT SEL MODE GRID"),
+            "segments_filter_where": ("fsk_launch_segments_filter_where", "A Q S SO SB Z N O NS R X MQ OUT SEL MODE GRID"),
+            "wide_filter_where": ("fsk_launch_wide_filter_where", "A N W R X Q MQ S SO SB OUT SEL HIGH MODE GRID"),
+            "wide_segments_filter_where": ("fsk_launch_segments_wide_masked_filter", "A W Q S SO SB Z N O NS R X MQ OUT SEL HIGH MODE GRID"),
+            "filter_rf": ("fsk_launch_filter_rf", "A N R X IA XA Q MQ OUT SEL MODE GRID"),
+            "wide_filter_rf": ("fsk_launch_wide_filter_rf", "A N W R X IA XA Q MQ OUT SEL HIGH MODE GRID")}
 STEM = {"where": "u16_where", "filter": "u16_filter", "segments": "u16_segments", "segments_filter": "u16_segments_filter", "wide": "wide",
-        "wide_filter": "wide_filter", "wide_segments": "wide_segments", "wide_segments_filter": "wide_segments_filter"}
+        "wide_filter": "wide_filter", "wide_segments": "wide_segments", "wide_segments_filter": "wide_segments_filter",
+        "segments_where": "u16_segments_where", "wide_where": "wide_where", "wide_segments_where": "wide_segments_where",
+        "filter_where": "u16_filter_where", "segments_filter_where": "u16_segments_filter_where", "wide_filter_where": "wide_filter_where",
+        "wide_segments_filter_where": "wide_segments_filter_where", "filter_rf": "u16_filter_rf", "wide_filter_rf": "wide_filter_rf"}
 HOST = {"where": "FLAGSTATS_hip_u16_x64_where", "filter": "FLAGSTATS_hip_u16_x64_filter", "segments": "FLAGSTATS_hip_u16_x64_segments",
         "segments_filter": "FLAGSTATS_hip_u16_x64_segments_filter", "wide": "FLAGSTATS_hip_wide_x64", "wide_filter": "FLAGSTATS_hip_wide_x64_filter",
-        "wide_segments": "FLAGSTATS_hip_wide_x64_segments", "wide_segments_filter": "FLAGSTATS_hip_wide_x64_segments_filter"}
+        "wide_segments": "FLAGSTATS_hip_wide_x64_segments", "wide_segments_filter": "FLAGSTATS_hip_wide_x64_segments_filter",
+        "segments_where": "FLAGSTATS_hip_u16_x64_segments_where", "wide_where": "FLAGSTATS_hip_wide_x64_where",
+        "wide_segments_where": "FLAGSTATS_hip_wide_x64_segments_where", "filter_where": "FLAGSTATS_hip_u16_x64_filter_where",
+        "segments_filter_where": "FLAGSTATS_hip_u16_x64_segments_filter_where", "wide_filter_where": "FLAGSTATS_hip_wide_x64_filter_where",
+        "wide_segments_filter_where": "FLAGSTATS_hip_wide_x64_segments_filter_where", "filter_rf": "FLAGSTATS_hip_u16_x64_filter_rf",
+        "wide_filter_rf": "FLAGSTATS_hip_wide_x64_filter_rf"}
+assert set(PUBLIC) == set(LAUNCHER) == set(STEM) == set(HOST) == {dp.family(k) for k in dp.KINDS} | set(dp.LATER_KINDS)
 
 
 def entry_name(case):
@@ -96,8 +123,8 @@ class Call:
         form = case["form"]
         put = host_at_16 if form == "host" else device_at_16
         a = {"N": case["n"], "W": case["W"], "Z": 0, "R": case["require"], "X": case["exclude"], "MQ": case["min_mapq"], "NS": case["nseg"],
-             "MODE": case["mode"], "GRID": case["grid"], "S": None, "SO": case["sel_offset"], "SB": 1 if case["kind"] == "where_bitmap" else 8,
-             "Q": None, "O": None}
+             "MODE": case["mode"], "GRID": case["grid"], "S": None, "SO": case["sel_offset"], "SB": dp.sel_bits_of(case) or 0,
+             "Q": None, "O": None, "IA": case.get("include_any", 0), "XA": case.get("exclude_all", 0)}
         img, at = dp.array_image(case)
         owner, base = put(img)
         self.keep.append(owner)
@@ -108,16 +135,11 @@ class Call:
             owner, base = put(img)
             self.keep.append(owner)
             a["Q"] = base + at
-        if case["kind"] == "where_bytes":
-            img, at = dp.bytes_image(case["mask"].astype(np.uint8) * np.uint8(1 + case["n"] % 255), case["sel_align"])
+        if case["mask"] is not None:
+            img, at = dp.selection_image(case)      # `at` is negative where a bitmap offset of 2^33 + k moves the pointer back
             owner, base = put(img)
             self.keep.append(owner)
             a["S"] = base + at
-        elif case["kind"] == "where_bitmap":
-            img, at, back = dp.bitmap_image(case)
-            owner, base = put(img)
-            self.keep.append(owner)
-            a["S"] = base + at - back
         if case["offsets"] is not None:
             if form in ("sync", "host"):
                 o = np.ascontiguousarray(case["offsets"], dtype=np.uint64)
@@ -204,10 +226,16 @@ def run_case(hip, case, ref, stream=None):
 
 # ------------------------------------------------------------------ 1. the randomized sweep
 def test_random_cases_every_derived_family(lib, oracle_mod):
+    sweep(lib, dp.plan(SEED, int(os.environ.get("FLAGSTATS_FUZZ_ITERS_DERIVED", "240"))))   # a soak run sets thousands
+
+
+def test_random_cases_every_later_family(lib, oracle_mod):
+    """the nine units derived after the sweep was written (dp.LATER_KINDS), under the same knob"""
+    sweep(lib, dp.plan_later(LATER_SEED, int(os.environ.get("FLAGSTATS_FUZZ_ITERS_DERIVED", "240"))))
+
+
+def sweep(hip, cases):
     import torch
-    hip = lib
-    iters = int(os.environ.get("FLAGSTATS_FUZZ_ITERS_DERIVED", "240"))   # a soak run sets thousands
-    cases = dp.plan(SEED, iters)
     assert dp.skip_reasons(cases) == []
     side = torch.cuda.Stream()
     stream = ctypes.c_void_p(side.cuda_stream)
@@ -233,7 +261,7 @@ def widened(low, dtype, rng, every):
 
 
 def interleaved_round(rng):
-    """the ten derived calls of one round, in order (the K1 calls around them are made by the test): sizes chosen so that the calls
+    """the nine derived calls of one round, in order (the K1 calls around them are made by the test): sizes chosen so that the calls
     at positions 0, 4 and 8 of a round, which never meet chunk_flags 8 in the three rounds, are the large ones"""
     u16 = lambda n: rng.randint(0, 65536, n).astype(np.uint16)  # noqa: E731
     q = lambda n: rng.randint(0, 256, n).astype(np.uint8)  # noqa: E731
@@ -264,14 +292,20 @@ def interleaved_round(rng):
 
 
 def test_entry_kinds_interleaved_over_the_staging_slots(lib, oracle_mod):
-    hip = lib
     rng = np.random.RandomState(77)
     derived = interleaved_round(rng)
     refs = [dp.reference(c) for c in derived]
     for c, r in zip(derived, refs):
         assert 100 <= c["n"] <= 200_000 and r["selected"].any() and (c["kind"] not in dp.WIDE or r["high"].any())
+    walk_the_slots(lib, oracle_mod, rng, derived, refs)
+
+
+def walk_the_slots(hip, oracle_mod, rng, derived, refs):
+    """three rounds of: a K1 host call, the derived host calls, a K1 host call -- chunk_flags advancing along CHUNK_WALK at every
+    call, a round later each time, so that every call but those a multiple of 4 from the round's first meets every chunk size"""
+    last_position = len(derived) + 1
     first, last = rng.randint(0, 65536, 200_000).astype(np.uint16), rng.randint(0, 65536, 5000).astype(np.uint16)
-    k1 = [(first, oracle_mod.flagstat_c(first)), (last, oracle_mod.flagstat_c(last))]
+    k1 = {0: (first, oracle_mod.flagstat_c(first)), last_position: (last, oracle_mod.flagstat_c(last))}
     old_chunk, old_small = hip.FLAGSTATS_hip_get(b"chunk_flags"), hip.FLAGSTATS_hip_get(b"small_flags")
     slots = set()
     try:
@@ -286,10 +320,11 @@ def test_entry_kinds_interleaved_over_the_staging_slots(lib, oracle_mod):
                 step += 1
                 return chunk
 
-            for position in range(11):
+            for position in range(last_position + 1):
                 chunk = next_chunk()
-                if position in (0, 10):
-                    x, want = k1[position // 10]
+                if position in k1:
+                    x, want = k1[position]
+                    assert chunk != 8 or x.size <= 5000
                     out = np.full(32, dp.BIAS, dtype=np.uint64)
                     assert hip.FLAGSTATS_u16_x64(x.ctypes.data, x.size, out.ctypes.data) == 0, err(hip)
                     assert np.array_equal(out, want + np.uint64(dp.BIAS)), (start, position, chunk, "FLAGSTATS_u16_x64")
@@ -308,9 +343,225 @@ def test_entry_kinds_interleaved_over_the_staging_slots(lib, oracle_mod):
     assert hip.FLAGSTATS_hip_get(b"chunk_flags") == old_chunk and hip.FLAGSTATS_hip_get(b"small_flags") == old_small
 
 
+def later_round(rng):
+    """the eleven derived calls of one round of the later kinds, in order: the host forms of the nine later kinds with `filter`
+    and `wide` of the old family in between.  With a K1 call at positions 0 and 12, positions 4 and 8 (calls 3 and 7 here) never
+    meet chunk_flags 8 and are the large ones."""
+    u16 = lambda n: rng.randint(0, 65536, n).astype(np.uint16)  # noqa: E731
+    q = lambda n: rng.randint(0, 256, n).astype(np.uint8)  # noqa: E731
+    half = lambda n: rng.randint(0, 2, n).astype(bool)  # noqa: E731
+    cuts = lambda n, first, k: np.concatenate([[first], np.sort(rng.randint(first, n - 3, k)), [n - 3]])  # noqa: E731
+    F = "host"
+    n = 3001
+    calls = [dp.fixed_case("segments_where", F, u16(n), 3, mask=half(n), sel_bits=1, sel_offset=5, offsets=cuts(n, 7, 9), phase=2, sel_align=3)]
+    n = 2203
+    calls.append(dp.fixed_case("wide_where", F, widened(u16(n), np.int64, rng, 300), 1, mask=half(n), sel_bits=8, sel_offset=3, phase=8,
+                               sel_align=7, high_at="apart"))
+    n = 4099
+    calls.append(dp.fixed_case("filter", F, u16(n), 0, require=1, exclude=0x904, mapq=q(n), min_mapq=30, mapq_align=1))
+    n = 150_001
+    calls.append(dp.fixed_case("wide_filter_where", F, widened(u16(n), np.uint32, rng, 5000), 2, exclude=0x704, mapq=q(n), min_mapq=20,
+                               mask=half(n), sel_bits=1, sel_offset=11, phase=4, mapq_align=7, sel_align=5, selected_at="apart"))
+    n = 2500      # --rf 0x50 -G 0xC beside -f 1 -F 0x900: the reduction leaves both tests
+    calls.append(dp.fixed_case("filter_rf", F, u16(n) & np.uint16(0x0FFF), 3, require=1, exclude=0x900, include_any=0x50, exclude_all=0xC,
+                               mapq=q(n), min_mapq=30, mapq_align=1))
+    n = 2999
+    calls.append(dp.fixed_case("wide_segments_where", F, widened(u16(n), np.int32, rng, 100), 0, mask=half(n), sel_bits=1, sel_offset=3,
+                               offsets=cuts(n, 1, 5), phase=12, sel_align=9))
+    n = 2203
+    calls.append(dp.fixed_case("wide", F, widened(u16(n), np.int64, rng, 300), 1, phase=8, high_at="apart"))
+    n = 120_003
+    calls.append(dp.fixed_case("wide_segments_filter_where", F, widened(u16(n), np.uint64, rng, 9000), 3, require=0x40, exclude=0x800,
+                               mapq=q(n), min_mapq=1, mask=half(n), sel_bits=8, offsets=cuts(n, 11, 16), mapq_align=9, sel_align=1,
+                               high_at="apart"))
+    n = 3777
+    calls.append(dp.fixed_case("segments_filter_where", F, u16(n), 1, require=2, exclude=0x100, mapq=q(n), min_mapq=100, mask=half(n),
+                               sel_bits=8, sel_offset=1, offsets=cuts(n, 0, 30), mapq_align=5, sel_align=15))
+    n = 2001      # every --rf bit is excluded: nothing can pass, nothing is read
+    calls.append(dp.fixed_case("wide_filter_rf", F, widened(u16(n), np.uint32, rng, 50), 1, exclude=0x30, include_any=0x30, mapq=q(n),
+                               min_mapq=5, phase=4, mapq_align=3))
+    n = 2100
+    calls.append(dp.fixed_case("filter_where", F, u16(n), 2, require=1, exclude=0x904, mapq=q(n), min_mapq=30, mask=half(n), sel_bits=1,
+                               sel_offset=9, mapq_align=11, sel_align=13, selected_at="apart"))
+    return calls
+
+
+def test_later_entry_kinds_interleaved_over_the_staging_slots(lib, oracle_mod):
+    rng = np.random.RandomState(78)
+    derived = later_round(rng)
+    refs = [dp.reference(c) for c in derived]
+    assert {c["kind"] for c in derived} == set(dp.LATER_KINDS) | {"filter", "wide"}
+    for c, r in zip(derived, refs):
+        empty = c["kind"] == "wide_filter_rf"
+        assert 2000 <= c["n"] <= 200_000 and r["selected"].any() != empty, c["kind"]
+        assert c["kind"] not in dp.WIDE + dp.LATER_WIDE or r["high"].any() != empty, c["kind"]
+    rf = {c["kind"]: c for c in derived if c["kind"] in dp.RF}
+    assert dp.Definition().reads(rf["filter_rf"]) and not dp.Definition().reads(rf["wide_filter_rf"])       # one counts, one is empty
+    both = rf["filter_rf"]                               # residue-both: no bit of --rf or -G is decided by -f / -F
+    assert bin(both["include_any"]).count("1") >= 2 and bin(both["exclude_all"]).count("1") >= 2
+    assert not (both["include_any"] | both["exclude_all"]) & (both["require"] | both["exclude"])
+    masked = [c for c in derived if c["mask"] is not None]
+    assert {c["sel_bits"] for c in masked} == {1, 8} and any(c["sel_offset"] & 1 for c in masked)
+    assert any(c["sel_align"] & 1 for c in masked) and any(c["mapq_align"] & 1 for c in derived if c["mapq"] is not None)
+    walk_the_slots(lib, oracle_mod, rng, derived, refs)
+
+
 # ------------------------------------------------------------------ 3. callers of different kinds at once
 CALLS_PER_THREAD = 30
 JOIN_SECONDS = 120
+
+
+def run_callers(hip, problems, bodies):
+    """one thread per body behind one barrier, CALLS_PER_THREAD calls each, at chunk_flags 8192 (knobs are global: set before the
+    threads, restored after); nothing is raised across the thread boundary: what goes wrong is appended to `problems`"""
+    barrier = threading.Barrier(len(bodies))
+
+    def worker(who, body):
+        try:
+            barrier.wait(timeout=JOIN_SECONDS)
+            for k in range(CALLS_PER_THREAD):
+                body(k)
+        except BaseException as exc:                       # nothing is raised across the thread boundary
+            problems.append((who, -1, "the thread itself", repr(exc), "no exception"))
+
+    old_chunk = hip.FLAGSTATS_hip_get(b"chunk_flags")
+    assert hip.FLAGSTATS_hip_set(b"chunk_flags", 8192) == 0, err(hip)
+    try:
+        threads = {who: threading.Thread(target=worker, args=(who, body), name="caller-" + who, daemon=True) for who, body in bodies.items()}
+        for t in threads.values():
+            t.start()
+        for t in threads.values():
+            t.join(JOIN_SECONDS)
+        stuck = [who for who, t in threads.items() if t.is_alive()]
+        assert not stuck, ("still running after %d s" % JOIN_SECONDS, stuck)
+        assert hip.FLAGSTATS_hip_get(b"chunk_flags") == 8192
+    finally:
+        hip.FLAGSTATS_hip_set(b"chunk_flags", old_chunk)
+    assert hip.FLAGSTATS_hip_get(b"chunk_flags") == old_chunk
+
+
+def checked_body(hip, problems, who, pairs):
+    """body of a thread that makes the calls of `pairs` [(Call, expected images)] in turn and compares each"""
+    def body(k):
+        call, want = pairs[k % len(pairs)]
+        call.fresh_outputs()
+        entry = entry_name(call.case)
+        rc = call(hip)
+        if rc != 0:
+            return problems.append((who, k, entry, "rc %d: %s" % (rc, err(hip)), "0"))
+        bad = mismatch(call.case, call.read(), want)
+        if bad is not None:
+            problems.append((who, k, entry, bad, "the reference"))
+    return body
+
+
+def adder_body(hip, problems, who, pairs, stream, shared_out):
+    """body of a thread that += the device-form calls of `pairs` into the shared words on its own stream"""
+    def body(k):
+        call = pairs[k % len(pairs)][0]
+        out = shared_out if call.case["high_at"] is not None else shared_out[:2] + (None,)
+        rc = call(hip, ctypes.c_void_p(stream.cuda_stream), out=out)
+        if rc != 0:
+            problems.append((who, k, entry_name(call.case), "rc %d: %s" % (rc, err(hip)), "0"))
+    return body
+
+
+def shared_sum(adders):
+    """the 34 words that the adder threads must leave: the sum of the rows, the sum of `selected`, the OR of `high`"""
+    want = np.zeros(34, dtype=np.uint64)
+    for pairs in adders:
+        for k in range(CALLS_PER_THREAD):
+            call, ref = pairs[k % len(pairs)]
+            rows = ref["rows"][0].copy()
+            if not call.case["mode"] & dp.SUPERSET:
+                rows[[0, 9, 16]] = 0
+            want[:32] += rows
+            want[32] += ref["selected"][0]
+            if call.case["high_at"] is not None:
+                want[33] |= ref["high"][0]
+    return want
+
+
+def k1_body(hip, problems, who, arrays, wants):
+    """body of a thread on K1's host entries (they move to a side engine when the default engine's lock is taken)"""
+    def body(k):
+        x, want = arrays[k % 3], wants[k % 3]
+        if k % 3 < 2:
+            out = np.full(32, dp.BIAS, dtype=np.uint32)
+            rc, entry = hip.FLAGSTATS_u16(x.ctypes.data, x.size, out.ctypes.data), "FLAGSTATS_u16"
+        else:
+            out = np.full(32, dp.BIAS, dtype=np.uint64)
+            rc, entry = hip.FLAGSTATS_u16_x64(x.ctypes.data, x.size, out.ctypes.data), "FLAGSTATS_u16_x64"
+        if rc != 0:
+            return problems.append((who, k, entry, "rc %d: %s" % (rc, err(hip)), "0"))
+        if not np.array_equal(out.astype(np.uint64), want + np.uint64(dp.BIAS)):
+            problems.append((who, k, entry, out.tolist(), (want + np.uint64(dp.BIAS)).tolist()))
+    return body
+
+
+def test_concurrent_callers_of_the_later_kinds(lib, oracle_mod):
+    import torch
+    hip = lib
+    rng = np.random.RandomState(92)
+    u16 = lambda n: rng.randint(0, 65536, n).astype(np.uint16)  # noqa: E731
+    q = lambda n: rng.randint(0, 256, n).astype(np.uint8)  # noqa: E731
+    half = lambda n: rng.randint(0, 2, n).astype(bool)  # noqa: E731
+    cuts = lambda n, first, k: np.concatenate([[first], np.sort(rng.randint(first, n - 3, k)), [n - 3]])  # noqa: E731
+    problems = []         # (thread, call number, entry, got, want): list.append is atomic
+
+    def checked(cases):
+        assert all(2000 <= c["n"] <= 200_000 for c in cases)
+        return [(Call(c), dp.expected_images(c, dp.reference(c))) for c in cases]
+
+    # A: host forms, several chunks each at chunk_flags 8192
+    na = (200_000, 90_001, 61_003)
+    thread_a = checked([
+        dp.fixed_case("filter_where", "host", u16(na[0]), 1, require=1, exclude=0x904, mapq=q(na[0]), min_mapq=30, mask=half(na[0]), sel_bits=1,
+                      sel_offset=3, phase=6, mapq_align=3, sel_align=5),
+        dp.fixed_case("wide_filter_where", "host", widened(u16(na[1]), np.int64, rng, 700), 3, exclude=0x104, mapq=q(na[1]), min_mapq=9,
+                      mask=half(na[1]), sel_bits=8, sel_offset=1, phase=8, mapq_align=2, sel_align=7),
+        dp.fixed_case("filter_rf", "host", u16(na[2]), 0, require=1, exclude=0x900, include_any=0x50, exclude_all=0xC, mapq=q(na[2]),
+                      min_mapq=30, mapq_align=1)])
+    # B: the _sync forms of the four segmented masked kinds
+    nb = (150_000, 70_001, 40_003, 33_333)
+    thread_b = checked([
+        dp.fixed_case("segments_where", "sync", u16(nb[0]), 3, mask=half(nb[0]), sel_bits=1, sel_offset=7, offsets=cuts(nb[0], 5, 40)),
+        dp.fixed_case("segments_filter_where", "sync", u16(nb[1]), 0, require=1, exclude=0x900, mapq=q(nb[1]), min_mapq=40, mask=half(nb[1]),
+                      sel_bits=8, offsets=cuts(nb[1], 0, 7), sel_align=3),
+        dp.fixed_case("wide_segments_where", "sync", widened(u16(nb[2]), np.int32, rng, 900), 1, mask=half(nb[2]), sel_bits=8, sel_offset=2,
+                      offsets=cuts(nb[2], 9, 12), phase=4),
+        dp.fixed_case("wide_segments_filter_where", "sync", widened(u16(nb[3]), np.uint64, rng, 900), 2, exclude=0x4, mapq=q(nb[3]),
+                      min_mapq=200, mask=half(nb[3]), sel_bits=1, sel_offset=13, offsets=cuts(nb[3], 1, 3), mapq_align=11)])
+    # C and D: device forms, each thread on its own stream, all of them += into the same 34 words
+    shared = torch.zeros(34, dtype=torch.int64, device="cuda")
+    shared_out = (shared.data_ptr(), shared.data_ptr() + 256, shared.data_ptr() + 264)
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    adders = []
+    for (n0, n1, n2), bits in (((180_000, 2000, 77_777), (1, 8)), ((3001, 199_999, 50_000), (8, 1))):
+        cases = [dp.fixed_case("wide_where", "device", widened(u16(n0), np.int32, rng, 700), 0, mask=half(n0), sel_bits=bits[0], sel_offset=3,
+                               phase=4),
+                 dp.fixed_case("wide_filter_where", "device", widened(u16(n1), np.int64, rng, 700), 2, exclude=0x104, mapq=q(n1), min_mapq=9,
+                               mask=half(n1), sel_bits=bits[1], sel_offset=6, phase=8, mapq_align=2),
+                 dp.fixed_case("wide_filter_rf", "device", widened(u16(n2), np.uint32, rng, 700), 2, exclude=0x800, include_any=0x1C1,
+                               exclude_all=0x30, mapq=q(n2), min_mapq=20, mapq_align=5)]
+        assert all(2000 <= c["n"] <= 200_000 for c in cases)
+        adders.append([(Call(c), dp.reference(c)) for c in cases])
+    want_shared = shared_sum(adders)
+    assert want_shared[33] and want_shared[0] and want_shared[32]
+    # E: K1's host entries
+    e_arrays = [u16(2000), u16(200_000), u16(123_457)]
+    e_wants = [oracle_mod.flagstat_c(x) for x in e_arrays]
+    torch.cuda.synchronize()
+    run_callers(hip, problems, {"A": checked_body(hip, problems, "A", thread_a), "B": checked_body(hip, problems, "B", thread_b),
+                                "C": adder_body(hip, problems, "C", adders[0], streams[0], shared_out),
+                                "D": adder_body(hip, problems, "D", adders[1], streams[1], shared_out),
+                                "E": k1_body(hip, problems, "E", e_arrays, e_wants)})
+    for s in streams:
+        s.synchronize()
+    torch.cuda.synchronize()
+    assert problems == [], "%d mismatches, the first: %r" % (len(problems), problems[:4])
+    got_shared = shared.cpu().numpy().view(np.uint64)
+    assert np.array_equal(got_shared, want_shared), ([hex(int(v)) for v in got_shared], [hex(int(v)) for v in want_shared])
 
 
 def test_concurrent_callers_of_different_kinds(lib, oracle_mod):
@@ -353,17 +604,7 @@ def test_concurrent_callers_of_different_kinds(lib, oracle_mod):
     for sizes in ((180_000, 2000, 77_777), (3001, 199_999, 50_000)):
         cases = three("device", (0, 2, 2), sizes)
         adders.append([(Call(c), dp.reference(c)) for c in cases])
-    want_shared = np.zeros(34, dtype=np.uint64)
-    for pairs in adders:
-        for k in range(CALLS_PER_THREAD):
-            call, ref = pairs[k % len(pairs)]
-            rows = ref["rows"][0].copy()
-            if not call.case["mode"] & dp.SUPERSET:
-                rows[[0, 9, 16]] = 0
-            want_shared[:32] += rows
-            want_shared[32] += ref["selected"][0]
-            if call.case["kind"] in dp.WIDE:
-                want_shared[33] |= ref["high"][0]
+    want_shared = shared_sum(adders)
     assert want_shared[33] and want_shared[0] and want_shared[32]
     # E: K1's host entries (they move to a side engine when the default engine's lock is taken)
     e_arrays = [u16(1000), u16(300_000), u16(123_457)]
@@ -376,50 +617,12 @@ def test_concurrent_callers_of_different_kinds(lib, oracle_mod):
     f_want16 = oracle_mod.flagstat_c(f_low)
     torch.cuda.synchronize()
 
-    def record(who, k, entry, got, want):
-        problems.append((who, k, entry, got, want))
-
-    def run_checked(who, pairs, k):
-        call, want = pairs[k % len(pairs)]
-        call.fresh_outputs()
-        entry = entry_name(call.case)
-        rc = call(hip)
-        if rc != 0:
-            return record(who, k, entry, "rc %d: %s" % (rc, err(hip)), "0")
-        bad = mismatch(call.case, call.read(), want)
-        if bad is not None:
-            record(who, k, entry, bad, "the reference")
-
-    def body_a(k):
-        run_checked("A", thread_a, k)
-
-    def body_b(k):
-        run_checked("B", thread_b, k)
-
-    def adder(who, pairs, stream):
-        def body(k):
-            call = pairs[k % len(pairs)][0]
-            rc = call(hip, ctypes.c_void_p(stream.cuda_stream), out=shared_out if call.case["kind"] in dp.WIDE else shared_out[:2] + (None,))
-            if rc != 0:
-                record(who, k, entry_name(call.case), "rc %d: %s" % (rc, err(hip)), "0")
-        return body
-
-    def body_e(k):
-        x, want = e_arrays[k % 3], e_wants[k % 3]
-        if k % 3 < 2:
-            out = np.full(32, dp.BIAS, dtype=np.uint32)
-            rc, entry = hip.FLAGSTATS_u16(x.ctypes.data, x.size, out.ctypes.data), "FLAGSTATS_u16"
-        else:
-            out = np.full(32, dp.BIAS, dtype=np.uint64)
-            rc, entry = hip.FLAGSTATS_u16_x64(x.ctypes.data, x.size, out.ctypes.data), "FLAGSTATS_u16_x64"
-        if rc != 0:
-            return record("E", k, entry, "rc %d: %s" % (rc, err(hip)), "0")
-        if not np.array_equal(out.astype(np.uint64), want + np.uint64(dp.BIAS)):
-            record("E", k, entry, out.tolist(), (want + np.uint64(dp.BIAS)).tolist())
+    record = lambda *what: problems.append(what)  # noqa: E731
+    wide_sync = checked_body(hip, problems, "F", f_pairs)
 
     def body_f(k):
         if k % 2:
-            return run_checked("F", f_pairs, k)
+            return wide_sync(k)
         out = np.full(32, dp.BIAS, dtype=np.uint64)
         rc = hip.FLAGSTATS_hip_device_u16_sync(f_ptr16, f_low.size, out.ctypes.data)
         if rc != 0:
@@ -427,32 +630,10 @@ def test_concurrent_callers_of_different_kinds(lib, oracle_mod):
         if not np.array_equal(out, f_want16 + np.uint64(dp.BIAS)):
             record("F", k, "FLAGSTATS_hip_device_u16_sync", out.tolist(), (f_want16 + np.uint64(dp.BIAS)).tolist())
 
-    bodies = {"A": body_a, "B": body_b, "C": adder("C", adders[0], streams[0]), "D": adder("D", adders[1], streams[1]), "E": body_e,
-              "F": body_f}
-    barrier = threading.Barrier(len(bodies))
-
-    def worker(who, body):
-        try:
-            barrier.wait(timeout=JOIN_SECONDS)
-            for k in range(CALLS_PER_THREAD):
-                body(k)
-        except BaseException as exc:                       # nothing is raised across the thread boundary
-            record(who, -1, "the thread itself", repr(exc), "no exception")
-
-    old_chunk = hip.FLAGSTATS_hip_get(b"chunk_flags")
-    assert hip.FLAGSTATS_hip_set(b"chunk_flags", 8192) == 0, err(hip)   # knobs are global: set before the threads, restored after
-    try:
-        threads = {who: threading.Thread(target=worker, args=(who, body), name="caller-" + who, daemon=True) for who, body in bodies.items()}
-        for t in threads.values():
-            t.start()
-        for t in threads.values():
-            t.join(JOIN_SECONDS)
-        stuck = [who for who, t in threads.items() if t.is_alive()]
-        assert not stuck, ("still running after %d s" % JOIN_SECONDS, stuck)
-        assert hip.FLAGSTATS_hip_get(b"chunk_flags") == 8192
-    finally:
-        hip.FLAGSTATS_hip_set(b"chunk_flags", old_chunk)
-    assert hip.FLAGSTATS_hip_get(b"chunk_flags") == old_chunk
+    run_callers(hip, problems, {"A": checked_body(hip, problems, "A", thread_a), "B": checked_body(hip, problems, "B", thread_b),
+                                "C": adder_body(hip, problems, "C", adders[0], streams[0], shared_out),
+                                "D": adder_body(hip, problems, "D", adders[1], streams[1], shared_out),
+                                "E": k1_body(hip, problems, "E", e_arrays, e_wants), "F": body_f})
     for s in streams:
         s.synchronize()
     torch.cuda.synchronize()

@@ -1,6 +1,6 @@
-"""GPU: the fifteen kernels derived from K1 -- flat and segmented, on uint16, int32 and int64 columns, under samtools' filter, a
-selection, or both -- past 2^31 and 2^32 elements and bytes, against tests/periodic_oracle.py: an exact reference that needs no
-host copy of the column.  Every comparison is exact.
+"""GPU: the seventeen kernels derived from K1 -- flat and segmented, on uint16, int32 and int64 columns, under samtools' filter, a
+selection, or both, and the two flat units of the whole predicate (--rf / -G) -- past 2^31 and 2^32 elements and bytes, against
+tests/periodic_oracle.py: an exact reference that needs no host copy of the column.  Every comparison is exact.
 
 The columns: 2^32 + 3 * 2^20 + 5 uint16 or int32 elements (8 and 16 GiB), 2^31 + 3 * 2^20 + 5 int64 elements (16 GiB), a MAPQ
 column, a byte mask and bitmaps for the selection offsets 0, 5 and 2^32 + 13, all filled on the device from periods of 977, 61
@@ -29,12 +29,13 @@ TORCH = {2: "int16", 4: "int32", 8: "int64"}
 # (wide, segmented, filtered, masked): the fifteen derived units -- all sixteen combinations but K1 itself
 FLAT = [(w, False, f, m) for w in (False, True) for f in (False, True) for m in (False, True) if w or f or m]
 SEGMENTED = [(w, True, f, m) for w in (False, True) for f in (False, True) for m in (False, True)]
-assert len(FLAT) + len(SEGMENTED) == 15
+RF = [(False, False, True, False, "rf"), (True, False, True, False, "rf")]     # u16_filter_rf, wide_filter_rf: flat, whole columns
+assert len(FLAT) + len(SEGMENTED) == 15 and len(FLAT) + len(SEGMENTED) + len(RF) == 17
 
 
 def stem(unit):
-    wide, seg, filt, mask = unit
-    return ("wide" if wide else "u16") + ("_segments" if seg else "") + ("_filter" if filt else "") + ("_where" if mask else "")
+    wide, seg, filt, mask = unit[:4]
+    return ("wide" if wide else "u16") + ("_segments" if seg else "") + ("_filter" if filt else "") + ("_where" if mask else "") + "_rf" * (len(unit) > 4)
 
 
 def entry_name(unit, form):
@@ -43,9 +44,10 @@ def entry_name(unit, form):
 
 def arguments(unit, a, with_stream):
     """the argument list of a public entry of the unit: array, n, [elem_bytes], [offsets, nseg], [require, exclude, mapq,
-    min_mapq], [sel, sel_offset, sel_bits], out, [selected], [high], flags, [stream]"""
-    wide, seg, filt, mask = unit
-    names = ["A", "N"] + (["W"] if wide else []) + (["O", "NS"] if seg else []) + (["R", "X", "Q", "MQ"] if filt else [])
+    [include_any, exclude_all], mapq, min_mapq], [sel, sel_offset, sel_bits], out, [selected], [high], flags, [stream]"""
+    wide, seg, filt, mask = unit[:4]
+    pred = ["R", "X", "IA", "XA", "Q", "MQ"] if len(unit) > 4 else ["R", "X", "Q", "MQ"]
+    names = ["A", "N"] + (["W"] if wide else []) + (["O", "NS"] if seg else []) + (pred if filt else [])
     names += (["S", "SO", "SB"] if mask else []) + ["OUT"] + (["SEL"] if filt or mask else []) + (["HIGH"] if wide else []) + ["FLAGS"]
     return [a[k] for k in names] + ([None] if with_stream else [])
 
@@ -165,9 +167,9 @@ def run_unit(hip, shared, slab, unit, form, store, call, first=None):
     takes the whole slab and the call's offsets -- or, with ``first``, the window from there on with the offsets relative to it.
     Returns None or what differs."""
     import torch
-    wide, seg, filt, mask = unit
+    wide, seg, filt, mask = unit[:4]
     W = slab.W
-    assert wide == (W > 2)
+    assert wide == (W > 2) and (len(unit) > 4) == ("rf" in call)
     o_abs = np.asarray(call["offsets"], dtype=np.int64)
     want = slab.want(call, filt, mask)
     if seg and first is None:
@@ -181,6 +183,7 @@ def run_unit(hip, shared, slab, unit, form, store, call, first=None):
     require, exclude, min_mapq = call["pred"]
     S, SO, SB = selection(shared, call, first)
     a = {"A": slab.base + first * W, "N": n, "W": W, "NS": nseg, "R": require, "X": exclude, "MQ": min_mapq,
+         "IA": call.get("rf", (0, 0))[0], "XA": call.get("rf", (0, 0))[1],
          "Q": shared.mapq.data_ptr() + PAD + first if min_mapq else None, "S": S, "SO": SO, "SB": SB,
          "FLAGS": (STORE if store else 0) | SUPERSET}
     fills = (GARBAGE, GARBAGE, GARBAGE) if store else (BIAS, SEL_BIAS, MASK_BIAS)
@@ -251,6 +254,36 @@ def test_windows_that_begin_past_the_mark(hip, shared, slab):
                 assert run_unit(hip, shared, slab, unit, form, True, call, first=first) is None
 
 
+def test_rf_units_whole_slab_and_window(hip, shared, slab):
+    """u16_filter_rf / wide_filter_rf under the two residue predicates: the whole slab in the device form (store and +=) and the
+    _sync form, and the window that begins past the mark at a base 2, 4 or 8 bytes past a 16-byte boundary"""
+    unit = units_of(slab, RF)[0]
+    calls = po.rf_slab_calls(slab.W)
+    assert [c["layout"] for c in calls] == ["whole", "whole", "window", "window"]
+    for call in calls:
+        want = slab.want(call, True, False)
+        assert 0 < int(want.selected[0]) < int(call["offsets"][1] - call["offsets"][0])
+        for store in (True, False):
+            assert run_unit(hip, shared, slab, unit, "device", store, call) is None
+        if call["layout"] == "whole":
+            assert run_unit(hip, shared, slab, unit, "sync", False, call) is None
+        else:
+            first = int(call["offsets"][0])
+            assert first > po.MARK[slab.W] and (slab.base + first * slab.W) % 16 == slab.W
+
+
+def test_rf_units_needles_one_at_a_time(hip, shared, slab):
+    """for every needle a residue predicate with -q 60 that this needle alone passes (po.needle_rf_predicate): counters and
+    selected are those of exactly that element, wherever in the 8 or 16 GiB it lies; high is the whole column's"""
+    unit = units_of(slab, RF)[0]
+    col = slab.col
+    for k, (flag, _, _, _) in sorted(col.needles.items()):
+        call = po.rf_call(po.needle_rf_predicate(flag), (0, slab.n), "rf-needle-%d" % k, "whole")
+        want, alone = slab.want(call, True, False), col.expect([k, k + 1], superset=True)
+        assert int(want.selected[0]) == 1 and np.array_equal(want.rows, alone.rows)
+        assert run_unit(hip, shared, slab, unit, "device", True, call) is None
+
+
 # ------------------------------------------------------------------ 3: needles one at a time
 def test_needles_one_at_a_time(hip, shared, slab):
     """a bitmap that selects needle k and 4,000 background elements far from it, and -q 60, which only a needle passes:
@@ -317,6 +350,7 @@ def test_python_layer_on_the_resident_slab(hip, shared, slab):
     from libflagstats_amd import (filter, filter_where, segments, segments_filter, segments_filter_where, segments_where,  # noqa: F401
                                   segments_wide, segments_wide_filter, segments_wide_filter_where, segments_wide_where, where, wide,
                                   wide_filter, wide_filter_where, wide_where)
+    from libflagstats_amd import filter_rf, wide_filter_rf
     W, t, n = slab.W, slab.body, slab.n
     calls = {c["case"]: c for c in po.slab_calls(W)}
     flat, seg = calls["whole-bitmap-big-p1"], calls["one"]
@@ -348,8 +382,16 @@ def test_python_layer_on_the_resident_slab(hip, shared, slab):
                 ((True, True, True, False), seg, lambda: segments_wide_filter.count_segments_torch_ints_filter(t, offsets, **sp, **common)),
                 ((True, True, True, True), seg,
                  lambda: segments_wide_filter_where.count_segments_torch_ints_filter_where(t, offsets, bitmap, **sp, **sel, **common))]
+    rf_call = po.rf_slab_calls(W)[1]                 # the whole slab under -F 0x904 --rf 0x60 -G 0x3 -q 30
+    rp = dict(require=rf_call["pred"][0], exclude=rf_call["pred"][1], include_any=rf_call["rf"][0], exclude_all=rf_call["rf"][1], mapq=mapq,
+              min_mapq=rf_call["pred"][2])
+    assert rp["min_mapq"] == 30 and rf_call["layout"] == "whole"
+    if W == 2:
+        runs.append((RF[0], rf_call, lambda: filter_rf.count_torch_filter_rf(t, **rp, **common)))
+    else:
+        runs.append((RF[1], rf_call, lambda: wide_filter_rf.count_torch_ints_filter_rf(t, **rp, **common)))
     for unit, call, run in runs:
-        wide_, _, filt, mask = unit
+        wide_, _, filt, mask = unit[:4]
         want = slab.want(call, filt, mask)
         got = [x.cpu().numpy().view(np.uint64) for x in run()]
         torch.cuda.synchronize()
@@ -416,6 +458,38 @@ def test_one_workgroup_past_2_pow_32(hip, shared, slab):
         shared.mapq[quiet] = po.NEEDLE_MAPQ
         torch.cuda.synchronize()
     del dense
+
+
+@pytest.mark.parametrize("slab", [2, 4], indirect=True)
+def test_rf_units_one_workgroup_past_2_pow_32(hip, shared, slab):
+    """grid 1 through fsk_launch_filter_rf (uint16) and fsk_launch_wide_filter_rf (int32) under po.RF_DENSE, a residue predicate
+    that all but a few background flags pass, and -q 1 with the MAPQ of every other needle 0: ``selected`` and slot 9 of the one
+    workgroup pass 2^32 (the oracle says so).  Launch-only times beside the positional-popcount yardstick:
+    tests/perf/grid1_rf_vs_pospopcnt.py -- int32 491 ms, inside the yardstick scaled by bytes plus 15 % (516 ms); uint16 403 ms
+    against 310 ms, over it (DESIGN.md section 7 says why)"""
+    import torch
+    W, n = slab.W, slab.n
+    col = po.column(W, dense=True)
+    quiet = torch.tensor([p for p, i in po.needle_positions(n).items() if i % 2 == 1], dtype=torch.int64, device="cuda") + PAD
+    require, exclude, include_any, exclude_all, min_mapq = po.RF_DENSE
+    want = col.expect(np.array([0, n], dtype=np.int64), require, exclude, min_mapq, superset=True, include_any=include_any, exclude_all=exclude_all)
+    assert int(want.selected[0]) > 1 << 32 and int(want.rows[0, 9]) > 1 << 32 and int(want.selected[0]) < n
+    A, Q = slab.base, shared.mapq.data_ptr() + PAD
+    out = torch.full((34,), GARBAGE, dtype=torch.int64, device="cuda")
+    OUT, SEL, HIGH = out.data_ptr(), out.data_ptr() + 256, out.data_ptr() + 264
+    try:
+        shared.mapq[quiet] = 0
+        if W == 2:
+            launch(hip, "fsk_launch_filter_rf", A, n, require, exclude, include_any, exclude_all, Q, min_mapq, OUT, SEL, STORE | SUPERSET, 1)
+        else:
+            launch(hip, "fsk_launch_wide_filter_rf", A, n, 4, require, exclude, include_any, exclude_all, Q, min_mapq, OUT, SEL, HIGH,
+                   STORE | SUPERSET, 1)
+        got = out.cpu().numpy().view(np.uint64)
+    finally:
+        shared.mapq[quiet] = po.NEEDLE_MAPQ
+        torch.cuda.synchronize()
+    assert np.array_equal(got[:32], want.rows[0]) and got[32] == want.selected[0], (W, got.tolist(), want.rows[0].tolist())
+    assert W == 2 or got[33] == want.high_read[0], (hex(int(got[33])), hex(int(want.high_read[0])))
 
 
 # ------------------------------------------------------------------ 6: host forms, default chunk_flags
@@ -497,3 +571,17 @@ def test_host_form_wide_past_2_pow_32_bytes(hip):
                                           out.ctypes.data + 264, STORE | SUPERSET)
     assert rc == 0, hip.FLAGSTATS_hip_last_error()
     assert np.array_equal(out[:32], want.rows[0]) and out[32] == want.selected[0] and out[33] == want.high_selected[0]
+
+
+def test_host_form_rf_past_2_pow_32_flags(hip, host_flags):
+    """FLAGSTATS_hip_u16_x64_filter_rf on the host column: -F 0x904 --rf 0x60 -G 0x3 -q 30"""
+    col, _, values, mapq, _ = host_flags
+    require, exclude, include_any, exclude_all, min_mapq = po.RF_PREDICATES[1]
+    want = col.expect(np.array([0, col.n], dtype=np.int64), require, exclude, min_mapq, superset=True, include_any=include_any,
+                      exclude_all=exclude_all)
+    assert min_mapq == 30 and 0 < int(want.selected[0]) < col.n
+    out, selected = np.full(32, BIAS, dtype=np.uint64), np.full(1, SEL_BIAS, dtype=np.uint64)
+    rc = hip.FLAGSTATS_hip_u16_x64_filter_rf(values.ctypes.data, col.n, require, exclude, include_any, exclude_all, mapq.ctypes.data, min_mapq,
+                                             out.ctypes.data, selected.ctypes.data, SUPERSET)
+    assert rc == 0, hip.FLAGSTATS_hip_last_error()
+    assert np.array_equal(out, want.rows[0] + np.uint64(BIAS)) and selected[0] == want.selected[0] + np.uint64(SEL_BIAS)

@@ -4,7 +4,10 @@
 (b) For every call of the GPU module, the wrapped models: a kernel that held the array's byte offset, the selection index, the
     MAPQ index or a segment offset in 32 bits (modulo 2^31, modulo 2^32, or sign-extended) would report something else than the
     truth in the very quantities the GPU test compares -- so a subtly wrong kernel fails there, and no GPU run of broken code is
-    needed to know it."""
+    needed to know it.
+(c) The same two for the units of the whole predicate (--rf / -G): the oracle with include_any / exclude_all against
+    filter_rf_oracle and wide_filter_rf_oracle, what the chosen predicates do to the needles and to the library's dispatch, and
+    the wrapped models against every rf call of the GPU module."""
 import os
 import sys
 
@@ -13,6 +16,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import filter_oracle  # noqa: E402
+import filter_rf_oracle  # noqa: E402
 import filter_where_oracle  # noqa: E402
 import periodic_oracle as po  # noqa: E402
 import segments_filter_oracle  # noqa: E402
@@ -25,6 +29,7 @@ import segments_wide_oracle  # noqa: E402
 import segments_wide_where_oracle  # noqa: E402
 import where_oracle  # noqa: E402
 import wide_filter_oracle  # noqa: E402
+import wide_filter_rf_oracle  # noqa: E402
 import wide_filter_where_oracle  # noqa: E402
 import wide_where_oracle  # noqa: E402
 
@@ -187,3 +192,95 @@ def test_wrapped_models_fail_the_host_calls():
     found = wide.detects(np.array(po.HOST_OFFSETS[8]), **po.reduced(po.HOST_CALL, False, True))
     # 2^29 + 65541 elements: only the byte offset pos * W passes 2^32 -- no selection index does
     assert_detected(found, ("array",), "wide")
+
+
+# ------------------------------------------------------------------ the two units of the whole predicate (--rf / -G)
+def rf_kw(pred):
+    require, exclude, include_any, exclude_all, min_mapq = pred
+    return dict(require=require, exclude=exclude, include_any=include_any, exclude_all=exclude_all, min_mapq=min_mapq)
+
+
+def all_rf_predicates():
+    return po.RF_PREDICATES + (po.RF_DENSE,) + tuple(po.needle_rf_predicate(f) for f in po.NEEDLE_FLAGS)
+
+
+@pytest.mark.parametrize("W", [2, 4, 8])
+def test_oracle_matches_the_rf_brute_force_oracles(W, oracle_mod):
+    """``expect`` with include_any / exclude_all against filter_rf_oracle and wide_filter_rf_oracle on a materialized window:
+    the predicates of the GPU tests, two of the one-needle predicates, and masks that no FLAG value satisfies"""
+    rng = np.random.RandomState(200 + W)
+    n = 2_000_003 + W
+    col = random_column(W, rng, n)
+    o = random_offsets(col, rng)
+    a, b = int(o[1]), int(o[-2])
+    v, _, q = col.materialize(0, n)
+    preds = po.RF_PREDICATES + (po.RF_DENSE, po.needle_rf_predicate(po.NEEDLE_FLAGS[0]), po.needle_rf_predicate(po.NEEDLE_FLAGS[3]),
+                                (0, 0x30, 0x30, 0, 0), (0x3, 0, 0, 0x3, 20), (0, 0, 0x8100, 0xC001, 0))
+    for trial, pred in enumerate(preds):
+        superset = bool(trial % 2)
+        kw = rf_kw(pred)
+        got = col.expect(np.array([a, b]), superset=superset, **kw)
+        args = (kw["require"], kw["exclude"], kw["include_any"], kw["exclude_all"], q[a:b] if kw["min_mapq"] else None, kw["min_mapq"], superset)
+        if W == 2:
+            rows, selected = filter_rf_oracle.want_counters(oracle_mod, v[a:b], *args)
+            high = 0
+        else:
+            rows, selected, high = wide_filter_rf_oracle.want(oracle_mod, v[a:b], *args)
+        assert np.array_equal(got.rows[0], rows) and int(got.selected[0]) == selected and int(got.high_read[0]) == high, (W, pred)
+        assert selected == 0 if trial in (5, 6) else selected > 0 or trial in (3, 4), (pred, selected)     # (the random needles' MAPQ)
+    assert not po.satisfiable(0, 0x30, 0x30, 0) and not po.satisfiable(0x3, 0, 0, 0x3) and po.satisfiable(*po.RF_DENSE[:4])
+
+
+def test_rf_predicates_are_what_the_gpu_tests_need():
+    """among the eleven needle flags at least three pass and three fail each of the two tests of RF_PREDICATES; every predicate of
+    the GPU tests leaves a residue, so that the rf kernel and not the parent's runs (the dispatch kind of the library's own host
+    reduction -- a classification, no expected value); every one-needle predicate passes exactly its needle"""
+    import ctypes
+    from libflagstats_amd import _lib
+    reduce_ = _lib.lib().fsk_filter_rf_reduce
+    flags = np.array(po.NEEDLE_FLAGS, dtype=np.uint16)
+    for require, exclude, include_any, exclude_all, _ in po.RF_PREDICATES:
+        assert po.flag_pass(flags, require, exclude).all()
+        any_of, all_of = po.flag_pass(flags, 0, 0, include_any, 0), po.flag_pass(flags, 0, 0, 0, exclude_all)
+        assert 3 <= any_of.sum() <= flags.size - 3 and 3 <= all_of.sum() <= flags.size - 3
+    assert po.RF_PREDICATES[0][4] == 0 and po.RF_PREDICATES[1] == po.RF_PREDICATES[0][:4] + (30,)
+    out = (ctypes.c_uint32 * 4)()
+    for pred in all_rf_predicates():
+        assert reduce_(*pred[:4], out) == 2 and (out[2] or out[3]), pred
+    for require, exclude, include_any, exclude_all, _ in po.RF_PREDICATES + (po.RF_DENSE,):
+        assert reduce_(require, exclude, include_any, exclude_all, out) == 2 and out[2] and out[3]       # both tests are left
+    for f in po.NEEDLE_FLAGS:
+        pred = po.needle_rf_predicate(f)
+        assert pred[4] == po.NEEDLE_MAPQ and po.flag_pass(flags, *pred[:4]).tolist() == [g == f for g in po.NEEDLE_FLAGS], hex(f)
+
+
+@pytest.mark.parametrize("W", [2, 4, 8])
+def test_wrapped_models_fail_the_rf_calls(W):
+    """the new GPU calls of the rf units: the whole slab under both predicates, the needles one at a time, one workgroup and the
+    host form -- each of the three index models, in the array's byte offset and in the MAPQ index, would miss the asserted values
+    (a window is handed pointers to its first element: no index of it passes the mark)"""
+    col = po.column(W)
+    whole = np.array([0, col.n], dtype=np.int64)
+    for call in po.rf_slab_calls(W):
+        if call["layout"] == "window":
+            continue
+        kw = po.reduced(call, True, False)
+        whats = ("array", "mapq") if kw["min_mapq"] else ("array",)
+        assert_detected(col.detects(call["offsets"], superset=True, **kw), whats, (W, call["case"]))
+    found = {}
+    for k, (flag, _, _, _) in col.needles.items():
+        kw = rf_kw(po.needle_rf_predicate(flag))
+        truth = col.expect(whole, superset=True, **kw)
+        assert int(truth.selected[0]) == 1 and np.array_equal(truth.rows, col.expect([k, k + 1], superset=True).rows)
+        for key, hit in col.detects(whole, superset=True, **kw).items():
+            found[key] = found.get(key) or hit
+    assert_detected(found, ("array", "mapq"), (W, "needles"))
+    if W in (2, 4):
+        dense = po.column(W, dense=True)
+        kw = rf_kw(po.RF_DENSE)
+        truth = dense.expect(whole, superset=True, **kw)
+        assert int(truth.selected[0]) > 1 << 32 and int(truth.rows[0, 9]) > 1 << 32
+        assert_detected(dense.detects(whole, superset=True, **kw), ("array", "mapq"), (W, "one workgroup"))
+    if W == 2:
+        host = po.column(2, n=po.HOST_N)
+        assert_detected(host.detects(np.array([0, host.n]), superset=True, **rf_kw(po.RF_PREDICATES[1])), ("array", "mapq"), "host")
