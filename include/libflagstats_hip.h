@@ -946,6 +946,54 @@ int FLAGSTATS_hip_stream_finish(FLAGSTATS_hip_stream* s, uint64_t* out);     /* 
 uint64_t FLAGSTATS_hip_stream_flags(const FLAGSTATS_hip_stream* s);          /* flags committed since the last finish */
 void FLAGSTATS_hip_stream_close(FLAGSTATS_hip_stream* s);
 
+/* ================= filtered segments, the whole predicate: -f / -F / --rf / -G / -q per segment of a uint16 column =================
+ * Per-contig, per-sample or per-block tables of the reads that pass `-F 0x904 --rf 0x50 -q 30`: the filtered segmented entries
+ * with the two options of `samtools view` that no require / exclude pair can express once they name two bits, --rf include_any
+ * (AT LEAST ONE of these bits) and -G exclude_all (not ALL of these bits), in one launch.  uint16 arrays only: per segment of a
+ * 4-byte or 8-byte column, and together with a bitmap or byte mask, the two options are not built.
+ *   pass(j) = (array[j] & require) == require && (array[j] & exclude) == 0
+ *             && (include_any == 0 || (array[j] & include_any) != 0)
+ *             && (exclude_all == 0 || (array[j] & exclude_all) != exclude_all)
+ *             && (min_mapq == 0 || mapq[j] >= min_mapq)
+ * include_any == 0 and exclude_all == 0 switch those tests off; with both 0 the entries are the filtered segmented entries.
+ * Everything else is the union of the two parents' contracts.  Segment i is [offsets[i], offsets[i+1]) under the contract of the
+ * segmented entries; row i of out[nseg][32] holds FLAGSTAT_scalar's counters over {array[j] : j in segment i, pass(j)}, and
+ * selected[i] (nseg uint64; the pointer may be NULL: nothing is reported) the number of such j.  Flags outside every segment
+ * count nowhere.  min_mapq == 0 reads no byte of `mapq`, which may then be NULL; otherwise only bytes of elements in [0, n) are
+ * read.
+ * `flags`: bit 0 = store (rows and selected[0 .. nseg) are zeroed in front, every slot of every row is written, empty segments
+ * read 0) instead of +=; bit 1 = superset (slots 0 / 16 = primary paired reads among those that pass, slot 9 = selected[i]
+ * minus slot 25).  nseg == 0 succeeds and touches nothing.
+ * The four masks are first reduced exactly on the host (a single --rf bit is a required bit, a single -G bit an excluded one, a
+ * bit that -f / -F already decide leaves --rf / -G), and by what is left a call is one of three things:
+ *   nothing can pass (require & exclude != 0, every --rf bit excluded, every -G bit required): nothing is launched and no
+ *       element, MAPQ byte or offset is read (the host form moves nothing); the store form still zeroes rows and counts, the +=
+ *       form leaves both as they are
+ *   a plain require / exclude pair is left: the launch is the filtered segmented entries' kernel, at its speed
+ *   a residue of two or more free bits in --rf or -G is left: one kernel of its own (fsk::flagstat_segments_filter_rf)
+ * Refused (non-zero, message in FLAGSTATS_hip_last_error, out and selected untouched, nothing launched): what the filtered
+ * segmented entries refuse, and include_any or exclude_all above 0xFFFF (asked after require / exclude / min_mapq and before
+ * `flags`).  Device offsets are not checked (that would synchronise): every offset the kernel reads is clamped to [0, n], so
+ * malformed offsets give undefined counters and never an access outside the array, the column, the rows or the counts. */
+/* DEVICE array, column and offsets, DEVICE d_out[nseg][32] and d_selected[nseg] (uint64); asynchronous on `stream`: ONE kernel
+ * (the store form puts one memset per pointer in front of it), no workspace, nothing synchronised; may be captured into a graph.
+ * Adds are atomic: launches on several streams may share d_out and d_selected in the += form. */
+int FLAGSTATS_hip_device_u16_segments_filter_rf(const uint16_t* d_array, uint64_t n, const uint64_t* d_offsets, uint64_t nseg,
+                                                uint32_t require, uint32_t exclude, uint32_t include_any, uint32_t exclude_all,
+                                                const uint8_t* d_mapq, uint32_t min_mapq, uint64_t* d_out, uint64_t* d_selected,
+                                                int flags, void* stream);
+/* DEVICE array and column, HOST offsets, HOST out[nseg][32] and selected[nseg]; synchronous */
+int FLAGSTATS_hip_device_u16_segments_filter_rf_sync(const uint16_t* d_array, uint64_t n, const uint64_t* offsets, uint64_t nseg,
+                                                     uint32_t require, uint32_t exclude, uint32_t include_any, uint32_t exclude_all,
+                                                     const uint8_t* d_mapq, uint32_t min_mapq, uint64_t* out, uint64_t* selected,
+                                                     int flags);
+/* HOST array, column and offsets, HOST out[nseg][32] and selected[nseg]; synchronous.  Only [offsets[0], offsets[nseg]) of array
+ * and column crosses the bus, in the engine's chunks (knob "chunk_flags"), each chunk's slice of the column behind its flags; a
+ * segment that spans chunks is summed on the device. */
+int FLAGSTATS_hip_u16_x64_segments_filter_rf(const uint16_t* array, uint64_t n, const uint64_t* offsets, uint64_t nseg,
+                                             uint32_t require, uint32_t exclude, uint32_t include_any, uint32_t exclude_all,
+                                             const uint8_t* mapq, uint32_t min_mapq, uint64_t* out, uint64_t* selected, int flags);
+
 #ifdef __cplusplus
 }
 #endif

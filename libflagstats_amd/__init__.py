@@ -21,6 +21,8 @@ Only what the path needs:
                      ``-q`` AND are selected (the non-null rows of an Arrow FLAG column), with their number, in one pass
 * ``segments_filter`` the filter per segment: rows of counters and the number of reads that pass, for
                      every CSR segment in one launch
+* ``segments_filter_rf`` ``segments_filter`` under samtools' whole FLAG predicate: ``--rf`` (at least one of these bits) and
+                     ``-G`` (not all of these bits) per segment of a ``uint16`` array, for every CSR segment in one launch
 * ``segments_where`` the mask or bitmap per segment: rows of counters and the number of selected reads, for every CSR
                      segment in one launch (the selection is indexed by array element)
 * ``segments_filter_where`` the filter and the mask or bitmap together per segment: rows of counters and the number of reads
@@ -74,6 +76,11 @@ from .segments_filter import (  # noqa: F401
     count_segments_torch_filter,
     flagstats_segments_filter,
     segment_filter_dicts,
+)
+from .segments_filter_rf import (  # noqa: F401
+    count_segments_device_ptr_filter_rf,
+    count_segments_torch_filter_rf,
+    flagstats_segments_filter_rf,
 )
 from .segments_wide import (  # noqa: F401
     count_segments_device_ptr_ints,
@@ -157,4 +164,5 @@ __all__ = ["flagstats", "flagstats_x64", "SAM_FLAG_NAMES", "flagstats_segments",
            "flagstats_segments_ints_filter_where", "count_segments_device_ptr_ints_filter_where",
            "count_segments_torch_ints_filter_where", "counters_filter_rf", "flagstats_filter_rf", "count_device_ptr_filter_rf",
            "count_torch_filter_rf", "counters_ints_filter_rf", "flagstats_ints_filter_rf", "count_device_ptr_ints_filter_rf",
-           "count_torch_ints_filter_rf"]
+           "count_torch_ints_filter_rf", "flagstats_segments_filter_rf", "count_segments_device_ptr_filter_rf",
+           "count_segments_torch_filter_rf"]
