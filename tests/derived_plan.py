@@ -30,6 +30,15 @@ masked wide kinds, decoys: an unselected element with every bit above bit 15 set
 high bit in an unselected slot about half the time.  The big bitmap offset is dealt to half of the launcher- and host-form
 bitmap cases.
 
+``plan_rf_segmented(seed, iters)`` is a third sequence, for the segmented units of the whole predicate (RF_SEGMENTED_KINDS: so far
+``segments_filter_rf``), dealt in blocks of one case a form -- ``_deal`` takes its block size from the kinds it is given, which
+leaves the two sequences above byte for byte what they were (both digests are pinned).  Its cases are drawn with _draw_later's
+pieces.  What the dice do not produce in a few hundred cases is dealt: a position of the array's first or last vector that lies
+outside the array is zero-filled by the kernel, and flag 0 with MAPQ 0 passes an all-of test that stands alone (nothing required,
+no -q); only the per-flag count's valid-bits mask keeps it out.  ``hazard_dealt`` says which cases get such a predicate and a
+segment that touches such a vector (``case["hazard"]``: "front" or "back"), half of them short enough for the per-flag regime
+under any policy.
+
 ``Definition`` states what the headers define, one method each: counted(j) = pass(j) && sel(j), ``selected`` the number counted,
 ``high`` over the selected elements, passing or not (every element where the kind takes no selection), nothing read where no FLAG
 value can pass.  ``reference`` evaluates it; the wrong models of test_derived_plan_host.py override one method each."""
@@ -71,6 +80,12 @@ LATER_FILTERED = tuple(k for k in LATER_KINDS if "filter" in k)
 LATER_WIDE = tuple(k for k in LATER_KINDS if k.startswith("wide"))
 RF_OUTCOMES = ("empty", "pair", "any", "all", "both")       # what the host reduction can leave of the four FLAG masks
 assert len(LATER_KINDS) * len(FORMS) == PAIRS
+
+# the segmented units of the whole predicate: plan_rf_segmented deals them, in blocks of their own size.  The wide and the masked
+# ones join this tuple when they are built.
+RF_SEGMENTED_KINDS = ("segments_filter_rf",)
+UNIT_FLAGS = 4096                                           # flags of one unit of the segmented uint16 kernels (8192 bytes)
+HAZARD_EVERY = 3                                            # of the all-of cases of a form, every third is dealt the hazard
 
 
 def family(kind):
@@ -247,10 +262,11 @@ def _deal(seed, iters, kinds, draw):
     rs = np.random.RandomState(seed)
     cases = []
     perm = None
+    pairs = len(kinds) * len(FORMS)                           # a block holds every (kind, form) once
     for it in range(iters):
-        block, j = divmod(it, PAIRS)
+        block, j = divmod(it, pairs)
         if j == 0:
-            perm = rs.permutation(PAIRS)
+            perm = rs.permutation(pairs)
         kind, form = kinds[perm[j] // len(FORMS)], FORMS[perm[j] % len(FORMS)]
         cases.append(draw(rs, it, kind, form, block))
     return cases
@@ -363,12 +379,91 @@ def plan_later(seed, iters):
     return _deal(seed, iters, LATER_KINDS, _draw_later)
 
 
+def hazard_dealt(outcome, block):
+    """None, or the number 0, 1, 2, ... of the dealt zero-fill case that the rf-segmented plan makes of a case of `block` with the
+    dealt `outcome`: a (kind, form) pair is dealt `all` once in five blocks, and every HAZARD_EVERY-th of those is taken"""
+    turn = block // len(RF_OUTCOMES)
+    return turn // HAZARD_EVERY if outcome == "all" and turn % HAZARD_EVERY == 0 else None
+
+
+def _hazard_shape(case, h):
+    """Before the column is drawn: n, phase and policy of dealt zero-fill case number `h`.  The array starts off a 16-byte boundary
+    and ends off one, so its first vector holds positions before element 0 and its last one positions past element n - 1; an even
+    `h` keeps the drawn n under two thirds of a unit, so that no segment has a whole unit and every policy counts flag by flag,
+    an odd one makes room for a segment of five units (six or more in the array) and takes one of the four smallest MIN_UNITS."""
+    index, lanes = case["index"], 8
+    case["phase"] = case["phase"] or 2 * (1 + index % 7)
+    n = case["n"]
+    if h % 2 == 0:
+        n = 9 + n % (2 * UNIT_FLAGS // 3)
+    else:
+        n = max(n, 6 * UNIT_FLAGS + index % 1000)
+        case["policy"] = (MIN_UNITS[index % 4], case["policy"][1])
+        if case["form"] == "host":
+            n = min(n, MAX_CHUNKS * max(2, case["chunk_flags"]))
+    while n % lanes == 0 or (case["phase"] // 2 + n) % lanes == 0:    # a ragged end in memory, and in a staged chunk as well
+        n += 1
+    case["n"] = n
+
+
+def _hazard_layout(case, h):
+    """After the layout is drawn: its first segment becomes [0, L) (`h // 2` even; the device forms only, a staged chunk starts on
+    a boundary) or its last one [n - L, n), L under a unit for an even `h` and five units and a bit for an odd one, and nothing
+    else moves but to stay in order."""
+    n, o = case["n"], case["offsets"].copy()
+    L = min(n, 1 + case["index"] % 1000 if h % 2 == 0 else 5 * UNIT_FLAGS + case["index"] % 1000)
+    front = (h // 2) % 2 == 0 and case["form"] != "host"
+    if front:
+        o[0], o[1] = 0, L
+        o[2:] = np.maximum(o[2:], L)
+    else:
+        o[-1], o[-2] = n, n - L
+        o[:-2] = np.minimum(o[:-2], n - L)
+    case["offsets"], case["hazard"] = o, "front" if front else "back"
+
+
+def _draw_rf_segmented(rs, index, kind, form, block):
+    """_draw_later for RF_SEGMENTED_KINDS: the pieces of _draw_later that a segmented uint16 kind of the whole predicate has, in
+    that order.  Dealt on top of the dice: the zero-fill hazard (hazard_dealt says where) -- an all-of test alone, nothing
+    required, no -q, the MAPQ column NULL or given in turn, and a segment that touches the ragged first or last vector of the
+    array; a position there holds flag 0 and MAPQ 0, which such a predicate passes."""
+    case = {"index": index, "kind": kind, "family": kind, "form": form, "skip": None, "hazard": None}
+    ki, fi = RF_SEGMENTED_KINDS.index(kind), FORMS.index(form)
+    case["rf_outcome"] = RF_OUTCOMES[(block * len(FORMS) + fi + ki) % len(RF_OUTCOMES)]      # _draw_later's rotation
+    h = hazard_dealt(case["rf_outcome"], block)
+    _geometry(rs, case, ki + block, False, True)
+    if h is not None:
+        _hazard_shape(case, h)
+    case["sel_bits"], case["big_offset"], case["sel_offset"] = None, False, 0
+    low, _, _ = _column(rs, case, False)
+    p = _predicate(rs, low)
+    case.update(require=p["require"], exclude=p["exclude"], min_mapq=p["min_mapq"], mapq=p["mapq"], mapq_null=p["mapq_null"])
+    _selection(rs, case["n"])                                 # drawn as _draw_later draws it; the kind takes none
+    case["mask"] = None
+    _segments(rs, case, True)
+    _outputs(rs, case, True, False)
+    masks = _rf_masks(rs, case["rf_outcome"], 0 if h is not None else p["require"], p["exclude"], p["value"])
+    case["require"], case["exclude"], case["include_any"], case["exclude_all"] = masks
+    if h is not None:
+        assert case["require"] == 0
+        case["include_any"], case["min_mapq"] = 0, 0
+        case["mapq_null"] = (h // 2 % 2 == 1) if form == "host" else (h % 4 in (1, 2))       # both ways beside either segment
+        _hazard_layout(case, h)
+    return case
+
+
+def plan_rf_segmented(seed, iters):
+    """plan() for RF_SEGMENTED_KINDS, in blocks of one case a form: the first `iters` cases of the sequence that `seed` names,
+    under plan()'s contract"""
+    return _deal(seed, iters, RF_SEGMENTED_KINDS, _draw_rf_segmented)
+
+
 def describe(case):
     """the drawn parameters of a case, without its arrays: what a failure message carries"""
     keep = ("index", "kind", "form", "W", "dtype", "n", "phase", "grid", "chunk_flags", "policy", "mode", "sel_offset", "sel_align",
             "mapq_align", "require", "exclude", "min_mapq", "mapq_null", "values", "high_style", "nseg", "layout", "selected_at", "high_at")
     d = {k: case[k] for k in keep}
-    d.update({k: case[k] for k in ("sel_bits", "include_any", "exclude_all", "rf_outcome") if k in case})   # later kinds
+    d.update({k: case[k] for k in ("sel_bits", "include_any", "exclude_all", "rf_outcome", "hazard") if k in case})   # later kinds
     if case["offsets"] is not None:
         d["offsets"] = (int(case["offsets"][0]), int(case["offsets"][-1]))
     return d
@@ -444,6 +539,10 @@ class Definition:
     def unread_high(self, case, above):
         return np.uint64(0)
 
+    def stray(self, case, ok, a, b):
+        """uint16[k]: flags that the non-empty segment [a, b) counts beside those of its own elements that pass -- none"""
+        return np.zeros(0, dtype=np.uint16)
+
 
 def passing(case, d=None):
     """bool[n]: counted(j) = pass(j) && sel(j)"""
@@ -474,12 +573,13 @@ def reference(case, d=None):
             continue
         seg = u[a:b]
         kept = seg[ok[a:b]]
-        low = np.ascontiguousarray((kept & UNSIGNED[W](0xFFFF)).astype(np.uint16))
+        extra = d.stray(case, ok, a, b)
+        low = np.ascontiguousarray(np.concatenate([(kept & UNSIGNED[W](0xFFFF)).astype(np.uint16), extra]))
         if low.size:
             rows[i] = oracle.flagstat_c(low)
             pair_all = oracle.samtools_counts(low)["n_pair_all"]
             rows[i, 0], rows[i, 16] = pair_all[0], pair_all[1]
-        selected[i] = d.selected(sel[a:b], ok[a:b])
+        selected[i] = d.selected(sel[a:b], ok[a:b]) + extra.size
         rows[i, 9] = np.uint64(low.size) - rows[i, 25]
         high[i] = d.high(case, above[a:b], sel[a:b], ok[a:b])
     return {"rows": rows, "selected": selected, "high": high, "length": length}
@@ -578,14 +678,17 @@ def fixed_case(kind, form, array, mode, mask=None, sel_offset=0, require=0, excl
                mapq_align=0, sel_align=0, selected_at="together", high_at="together", index=-1, sel_bits=None, include_any=0,
                exclude_all=0):
     """a case that is stated, not drawn: the dict that reference / expected / the images above take, for the tests with a fixed
-    sequence of calls.  A later kind (LATER_KINDS) with a selection states its `sel_bits`; an rf kind its --rf / -G masks."""
+    sequence of calls.  A later kind (LATER_KINDS, RF_SEGMENTED_KINDS) with a selection states its `sel_bits`; an rf kind its
+    --rf / -G masks."""
     array = np.ascontiguousarray(array)
     W = array.dtype.itemsize
-    assert kind in KINDS + LATER_KINDS and form in FORMS and (W == 2) == (kind not in WIDE + LATER_WIDE) and phase % W == 0
-    if kind in LATER_KINDS:
-        assert (mask is not None) == (kind in MASKED) == (sel_bits in (1, 8)) and (offsets is not None) == (kind in LATER_SEGMENTED)
-        assert kind in LATER_FILTERED or (require == exclude == min_mapq == 0 and mapq is None)
-        assert kind in RF or include_any == exclude_all == 0
+    later_kinds = LATER_KINDS + RF_SEGMENTED_KINDS
+    assert kind in KINDS + later_kinds and form in FORMS and (W == 2) == (kind not in WIDE + LATER_WIDE) and phase % W == 0
+    if kind in later_kinds:
+        assert (mask is not None) == (kind in MASKED) == (sel_bits in (1, 8))
+        assert (offsets is not None) == (kind in LATER_SEGMENTED + RF_SEGMENTED_KINDS)
+        assert kind in LATER_FILTERED + RF_SEGMENTED_KINDS or (require == exclude == min_mapq == 0 and mapq is None)
+        assert kind in RF + RF_SEGMENTED_KINDS or include_any == exclude_all == 0
         later = {"sel_bits": sel_bits, "include_any": include_any, "exclude_all": exclude_all, "rf_outcome": None}
     else:
         assert (mask is not None) == (kind in ("where_bitmap", "where_bytes")) and (offsets is not None) == (kind in SEGMENTED)
@@ -600,7 +703,7 @@ def fixed_case(kind, form, array, mode, mask=None, sel_offset=0, require=0, excl
             "mask": None if mask is None else np.asarray(mask, dtype=bool),
             "offsets": None if offsets is None else np.asarray(offsets, dtype=np.int64), "layout": "fixed" if offsets is not None else None,
             "nseg": 1 if offsets is None else len(offsets) - 1, "mode": mode,
-            "selected_at": selected_at if kind in SELECTING + LATER_KINDS else None,
+            "selected_at": selected_at if kind in SELECTING + later_kinds else None,
             "high_at": high_at if kind in WIDE + LATER_WIDE else None}
 
 

@@ -13,8 +13,8 @@ slot indicators of the kept elements, ``selected`` and the high bits are built o
 ``[b, e)`` then reads as ``(t // L) * pre[L] + pre[t % L]`` at both ends.  No flag of F has bit 0x400 or 0x200, so the background
 leaves slot 10, slot 25 and every slot 16..31 at zero; a needle sets one of the two and carries a high bit that no H entry has,
 so every needle shows exactly.  The expectation is the background, minus the background at every needle's index, plus the needle.
-The predicate is samtools' whole one: ``include_any`` / ``exclude_all`` (--rf / -G) are off at 0, which every unit but the two rf
-units passes.
+The predicate is samtools' whole one: ``include_any`` / ``exclude_all`` (--rf / -G) are off at 0, which every unit but the three
+rf units passes.
 
 ``expect`` also takes index maps -- where an element, a selection bit or byte and a MAPQ byte are really read from.  ``wrapped``
 makes the maps of an index held in 32 bits; they model a kernel that is subtly wrong, so that a CPU test can show that the GPU
@@ -448,7 +448,8 @@ RF_DENSE = (0, 0, 0xF9FF, 0xF9FF, 1)
 
 
 def rf_call(pred, offsets, case, layout) -> dict:
-    """a call of the flat rf units over [offsets[0], offsets[1]) in the form of slab_calls: no selection"""
+    """a call of the rf units in the form of slab_calls, no selection: over [offsets[0], offsets[1]) for the flat ones, over the
+    segments `offsets` for the segmented one"""
     require, exclude, include_any, exclude_all, min_mapq = pred
     return dict(case=case, layout=layout, offsets=np.asarray(offsets, dtype=np.int64), pred=(require, exclude, min_mapq),
                 rf=(include_any, exclude_all), form="bytes", sel_offset=0, local=False)
@@ -461,6 +462,42 @@ def rf_slab_calls(W: int) -> list:
     start, m = window(W)
     return ([rf_call(p, (0, n), "rf-whole-p%d" % i, "whole") for i, p in enumerate(RF_PREDICATES)]
             + [rf_call(p, (start, start + m), "rf-window-p%d" % i, "window") for i, p in enumerate(RF_PREDICATES)])
+
+
+# ------------------------------------------------------------------ the segmented unit of the whole predicate
+# The `one` and `around` layouts leave elements [0, 7) or [0, 3) in front and [n - 3, n) behind to no segment, so that a kernel
+# that ignored offsets[0] or offsets[nseg] counts them -- if they pass.  Under RF_PREDICATES none of them does (-F 0x904 and -G 0x3
+# keep all of them out), so these two layouts run under predicates of their own: -F 0x4 --rf 0x60 -G 0x11, a residue of both
+# tests, without and with -q 30.  Element 0 (flag 0xA9E9, MAPQ 1) passes the first, element 4 (0x6128, MAPQ 31) both, and so does
+# the needle at n - 1 (0x223 or 0x643, MAPQ 60).  The MAPQ of elements 0, 1 and 2 is 1, 7 and 29: under -q 30 the three elements
+# in front of `around` cannot count, and that one bound is tested by the call without -q alone
+# (tests/test_periodic_oracle_host.py asserts all of this).
+RF_BOUNDS_PREDICATES = ((0, 0x4, 0x60, 0x11, 0), (0, 0x4, 0x60, 0x11, 30))
+RF_SEGMENTED_UNIT = (False, True, True, False, "rf")      # u16_segments_filter_rf: uint16 only
+
+
+def rf_segments_slab_calls() -> list:
+    """the calls of u16_segments_filter_rf over the resident uint16 slab: the three layouts -- `blocks` under RF_PREDICATES, `one`
+    and `around` under RF_BOUNDS_PREDICATES -- and the window that begins past the mark under RF_PREDICATES (``local``: it is
+    handed pointers to its first element)"""
+    n = slab_n(2)
+    lay = layouts(2, n)
+    start, m = window(2)
+    calls = []
+    for i in (0, 1):
+        calls.append(rf_call(RF_PREDICATES[i], lay["blocks"], "rf-blocks-p%d" % i, "blocks"))
+        calls.append(rf_call(RF_BOUNDS_PREDICATES[i], lay["one"], "rf-one-b%d" % i, "one"))
+        calls.append(rf_call(RF_BOUNDS_PREDICATES[i], lay["around"], "rf-around-b%d" % i, "around"))
+        calls.append(dict(rf_call(RF_PREDICATES[i], (start, start + m), "rf-segments-window-p%d" % i, "window"), local=True))
+    return calls
+
+
+def rf_needle_calls(col: Column, offsets) -> list:
+    """(needle, call) for every needle of the column that lies inside the layout `offsets`: the layout under the residue predicate
+    that this needle alone passes"""
+    o = np.asarray(offsets, dtype=np.int64)
+    return [(k, rf_call(needle_rf_predicate(flag), o, "rf-around-needle-%d" % k, "around"))
+            for k, (flag, _, _, _) in sorted(col.needles.items()) if o[0] <= k < o[-1]]
 
 
 def needle_rf_predicate(flag: int) -> tuple:

@@ -16,6 +16,7 @@ import filter_rf_oracle  # noqa: E402
 import filter_where_oracle  # noqa: E402
 import segments_filter_where_oracle  # noqa: E402
 import segments_filter_oracle  # noqa: E402
+import segments_filter_rf_oracle  # noqa: E402
 import segments_oracle  # noqa: E402
 import segments_wide_filter_oracle  # noqa: E402
 import segments_where_oracle  # noqa: E402
@@ -224,16 +225,20 @@ def test_input_images_hold_the_inputs_between_poison(planned):
 PLAN_DIGEST = "7f53b51ff32d1c7c94ca21df9c5291ea9ad9ee631bca4d1057d8d9868f1743f3"   # taken before plan_later was written
 
 
-def test_plan_is_byte_for_byte_what_it_was(planned):
-    """sha256 over every case's describe() and the bytes of its array, mapq, mask and offsets: sharing _draw's pieces with
-    plan_later has not moved one draw of plan()"""
+def plan_digest(cases):
     h = hashlib.sha256()
-    for c in planned[0]:
+    for c in cases:
         h.update(repr(dp.describe(c)).encode())
         for k in ("array", "mapq", "mask", "offsets"):
             if c[k] is not None:
                 h.update(np.ascontiguousarray(c[k]).tobytes())
-    assert h.hexdigest() == PLAN_DIGEST
+    return h.hexdigest()
+
+
+def test_plan_is_byte_for_byte_what_it_was(planned):
+    """sha256 over every case's describe() and the bytes of its array, mapq, mask and offsets: sharing _draw's pieces with
+    plan_later has not moved one draw of plan()"""
+    assert plan_digest(planned[0]) == PLAN_DIGEST
 
 
 # ------------------------------------------------------------------ the later plan: the nine units derived afterwards
@@ -504,6 +509,14 @@ def test_later_plan_notices_a_wrong_model(planned_later, name, model, kinds):
     assert len(changed) >= 5, (name, changed)
 
 
+LATER_PLAN_DIGEST = "345770c44eb04cf10be5f1282b8e0bed1239f5afc9af9e036b680b17647315b5"   # taken before plan_rf_segmented was written
+
+
+def test_later_plan_is_byte_for_byte_what_it_was(planned_later):
+    """test_plan_is_byte_for_byte_what_it_was, of plan_later: a block size taken from the kinds has not moved one draw of it"""
+    assert plan_digest(planned_later[0]) == LATER_PLAN_DIGEST
+
+
 def test_later_input_images_hold_the_inputs_between_poison(planned_later):
     seen = set()
     for c in planned_later[0][:120]:
@@ -530,3 +543,217 @@ def test_later_input_images_hold_the_inputs_between_poison(planned_later):
             assert np.array_equal(bits[s & 7:(s & 7) + n].astype(bool), c["mask"]) and bits[:s & 7].all() and bits[(s & 7) + n:].all()
             assert (ptr < 0) == c["big_offset"]
     assert seen == {(1, False), (1, True), (8, False), (8, True)}     # a case with a MAPQ column and a selection has both images
+
+
+# ------------------------------------------------------------------ the third plan: the segmented units of the whole predicate
+# chosen on the CPU, before any GPU run, by the coverage test below alone: the share of partly taken selections is 82 to 90 % over
+# the seeds 20261021 .. 20261027 (tiny arrays and single-valued columns take all or nothing), and this is the first of them to
+# meet the 85 % that the other two plans meet
+RF_SEGMENTED_SEED = 20261024
+
+
+@pytest.fixture(scope="module")
+def planned_rf_segmented(oracle_mod):
+    """planned, of plan_rf_segmented(RF_SEGMENTED_SEED, 300)"""
+    cases = dp.plan_rf_segmented(RF_SEGMENTED_SEED, 300)
+    refs, spent = [], 0.0
+    for c in cases:
+        t0 = time.perf_counter()
+        refs.append(dp.reference(c))
+        if c["index"] < DEFAULT_ITERS:
+            spent += time.perf_counter() - t0
+    return cases, refs, spent
+
+
+def test_rf_segmented_reference_agrees_with_the_per_kernel_oracle(planned_rf_segmented):
+    cases, refs, _ = planned_rf_segmented
+    assert len(cases) == 300 and {c["kind"] for c in cases} == set(dp.RF_SEGMENTED_KINDS)
+    for c, r in zip(cases, refs):
+        rows, sel = segments_filter_rf_oracle.want(low16(c), c["offsets"], c["require"], c["exclude"], c["include_any"], c["exclude_all"],
+                                                   c["mapq"], c["min_mapq"], True)
+        what = dp.describe(c)
+        assert rows.shape == r["rows"].shape and np.array_equal(rows, r["rows"]), what
+        assert np.array_equal(np.asarray(sel, dtype=np.uint64), r["selected"]) and not r["high"].any(), what
+        if c["rf_outcome"] == "empty":
+            assert not r["rows"].any() and not r["selected"].any(), what
+
+
+def test_rf_segmented_plan_is_deterministic_and_prefix_closed(planned_rf_segmented):
+    cases = planned_rf_segmented[0]
+    for k in (0, 1, 3, 4, 5, 80):
+        shorter, longer = dp.plan_rf_segmented(RF_SEGMENTED_SEED, k), dp.plan_rf_segmented(RF_SEGMENTED_SEED, k + 1)
+        assert len(shorter) == k and len(longer) == k + 1
+        for a, b in zip(shorter, longer):
+            same_case(a, b)
+        for a, b in zip(longer, cases):
+            same_case(a, b)
+    assert any(a["n"] != b["n"] for a, b in zip(dp.plan_rf_segmented(RF_SEGMENTED_SEED + 1, 10), cases))
+    for block in range(0, 300 - 3, 4):                  # a block is the four forms
+        assert sorted(c["form"] for c in cases[block:block + 4]) == sorted(dp.FORMS)
+
+
+def whole_units(c, a, b):
+    """whole units of the kernel that the segment [a, b) holds: units lie at multiples of UNIT_FLAGS from the 16-byte boundary in
+    front of the array (a staged chunk of the host form starts on one)"""
+    lo = 0 if c["form"] == "host" else c["phase"] // 2
+    return max(0, (b + lo) // dp.UNIT_FLAGS - -(-(a + lo) // dp.UNIT_FLAGS))
+
+
+def hazard_segment(c):
+    """(a, b) of the segment that the dealt zero-fill case is about"""
+    o = c["offsets"]
+    return (int(o[0]), int(o[1])) if c["hazard"] == "front" else (int(o[-2]), int(o[-1]))
+
+
+def test_rf_segmented_plan_covers_what_it_is_for(planned_rf_segmented):
+    from libflagstats_amd import _lib
+    reduce_ = _lib.lib().fsk_filter_rf_reduce
+    cases, refs, _ = planned_rf_segmented
+    cases, refs = cases[:DEFAULT_ITERS], refs[:DEFAULT_ITERS]
+    count = lambda pred: sum(1 for c in cases if pred(c))  # noqa: E731
+    truth = dp.Definition()
+    for kind in dp.RF_SEGMENTED_KINDS:
+        mine = [c for c in cases if c["kind"] == kind]
+        # ... of an rf kind: the plan dealt what the reduction finds, every outcome in every form, a bit in the high byte plane
+        assert [rf_outcome(reduce_, c) for c in mine] == [c["rf_outcome"] for c in mine], kind
+        for form in dp.FORMS:
+            for outcome in dp.RF_OUTCOMES:
+                assert sum(1 for c in mine if c["form"] == form and c["rf_outcome"] == outcome) >= 3, (kind, form, outcome)
+        assert any((c["include_any"] | c["exclude_all"]) & 0xFF00 for c in mine), kind
+        # ... of a segmented kind
+        assert any((np.diff(c["offsets"]) == 0).any() and (np.diff(c["offsets"]) > 0).any() for c in mine), kind
+        assert any(c["offsets"][0] > 0 for c in mine) and any(c["offsets"][-1] < c["n"] for c in mine), kind
+        assert {c["nseg"] for c in mine} == set(dp.NSEGS), kind
+        assert {c["layout"] for c in mine} == {"random", "units", "runs"}, kind
+        assert any((np.diff(c["offsets"]) >= 2 * 8192 // c["W"]).any() for c in mine), (kind, "a segment of chain length")
+        assert all(c["W"] == 2 and c["mask"] is None and c["mapq"] is not None for c in mine), kind
+    for mode in range(4):
+        assert count(lambda c: c["mode"] == mode) >= 5, mode
+    for grid in dp.GRIDS:
+        assert count(lambda c: c["grid"] == grid) >= 5, grid
+    for chunk in dp.CHUNKS:
+        assert count(lambda c: c["chunk_flags"] == chunk) >= 5, chunk
+    for mu in dp.MIN_UNITS:
+        assert count(lambda c: c["policy"][0] == mu) >= 5, mu
+    for nseg in dp.NSEGS:
+        assert count(lambda c: c["nseg"] == nseg) >= 5, nseg
+    for at in dp.PLACEMENTS:
+        assert count(lambda c: c["selected_at"] == at) >= 5, at
+    for name in ("int16", "uint16"):
+        assert count(lambda c: c["dtype"] == name) >= 5, name
+    assert count(lambda c: c["min_mapq"] > 0) >= 20 and count(lambda c: c["min_mapq"] == 0) >= 20
+    assert count(lambda c: c["min_mapq"] == 0 and not c["mapq_null"]) >= 5 and count(lambda c: c["mapq_align"] & 1) >= 5
+    assert {c["n_cluster"] for c in cases} == {0, 1, 2, 3} and max(c["n"] for c in cases) <= dp.CAP
+    assert sum(c["n"] for c in cases) < 40_000_000
+    # the dealt zero-fill cases: in every form at least twice, each with all of what makes a position outside the array pass
+    dealt = [c for c in cases if c["hazard"] is not None]
+    out = (ctypes.c_uint32 * 4)()
+    for c in dealt:
+        what = dp.describe(c)
+        assert reduce_(c["require"], c["exclude"], c["include_any"], c["exclude_all"], out) == 2 and out[0] == 0 and out[2] == 0 and out[3], what
+        assert c["require"] == 0 and c["include_any"] == 0 and c["min_mapq"] == 0 and c["rf_outcome"] == "all", what
+        assert bool(truth.flag_pass(np.zeros(1, dtype=np.uint64), *truth.masks(c))[0]), what     # flag 0 passes
+        a, b = hazard_segment(c)
+        assert b > a, what
+        if c["hazard"] == "front":
+            assert a == 0 and c["phase"] != 0 and c["form"] != "host", what
+        else:
+            assert b == c["n"] and (c["phase"] // 2 + c["n"]) % 8 != 0 and c["n"] % 8 != 0, what
+    per_flag = [whole_units(c, *hazard_segment(c)) < max(1, c["policy"][0]) for c in dealt]
+    assert 2 * sum(per_flag) == len(dealt), per_flag
+    assert any(whole_units(c, *hazard_segment(c)) >= max(1, c["policy"][0]) and c["form"] == "launcher" for c in dealt)
+    for form in dp.FORMS:
+        mine = [c for c in dealt if c["form"] == form]
+        assert len(mine) >= 2 and {c["mapq_null"] for c in mine} == {False, True}, form
+    assert {c["hazard"] for c in dealt} == {"front", "back"}
+    assert any(c["form"] == "host" and c["chunk_flags"] == 8 for c in dealt)
+    # a selection partly taken in some segment: all but 15 % of the cases that can pass anything (a fifth is dealt `empty`)
+    can = [(c, r) for c, r in zip(cases, refs) if truth.reads(c)]
+    assert len(can) == count(lambda c: c["rf_outcome"] != "empty") >= 180
+    partial = [bool(((r["selected"] > 0) & (r["selected"] < r["length"])).any()) for c, r in can]
+    assert sum(partial) >= 0.85 * len(can), (sum(partial), len(can))
+
+
+def test_no_rf_segmented_case_is_skipped(planned_rf_segmented):
+    cases = planned_rf_segmented[0]
+    assert dp.skip_reasons(cases[:DEFAULT_ITERS]) == []
+    assert all(c["skip"] is None for c in cases)
+    for c in cases:
+        if c["form"] == "host":
+            assert c["n"] <= dp.MAX_CHUNKS * max(2, c["chunk_flags"])
+        assert not c["big_offset"] and c["sel_offset"] == 0
+
+
+def test_reference_of_the_rf_segmented_plan_is_quick(planned_rf_segmented):
+    assert planned_rf_segmented[2] < 20.0, planned_rf_segmented[2]
+
+
+class RfIgnoredBesideAPair(dp.Definition):
+    """--rf / -G dropped where the reduction leaves a plain pair: the parent's kernel called with the caller's pair, not the
+    reduced one"""
+    def masks(self, c):
+        return (c["require"], c["exclude"]) + ((0, 0) if c["rf_outcome"] == "pair" else (c["include_any"], c["exclude_all"]))
+
+
+class ValidBitsDropped(dp.Definition):
+    """the per-flag count without its valid-bits mask: a non-empty segment also counts the positions of its first and last vector
+    of 8 flags that lie outside it.  Vectors are aligned to 16 bytes in memory: element index = -phase / 2 modulo 8.  A position
+    inside [0, n) carries its own flag and MAPQ; one outside carries flag 0 and MAPQ 0."""
+    inside, outside = True, True
+
+    def stray(self, case, ok, a, b):
+        lo, n = case["phase"] // case["W"], case["n"]
+        first, last = (a + lo) // 8 * 8 - lo, (b - 1 + lo) // 8 * 8 - lo           # element index of position 0 of either vector
+        j = np.array([k for k in sorted(set(range(first, first + 8)) | set(range(last, last + 8))) if not a <= k < b], dtype=np.int64)
+        real = (j >= 0) & (j < n)
+        zero_passes = bool(self.flag_pass(np.zeros(1, dtype=np.uint64), *self.masks(case))[0]) and case["min_mapq"] == 0
+        kept = j[real][ok[j[real]]] if self.inside else j[:0]
+        flags = (case["array"].view(dp.UNSIGNED[case["W"]])[kept] & dp.UNSIGNED[case["W"]](0xFFFF)).astype(np.uint16)
+        zeros = int((~real).sum()) if self.outside and zero_passes else 0
+        return np.concatenate([flags, np.zeros(zeros, dtype=np.uint16)])
+
+
+class ValidBitsDroppedOutsideTheArray(ValidBitsDropped):
+    """... of the positions outside [0, n) alone: what no neighbouring element shows"""
+    inside = False
+
+
+RF_SEGMENTED_WRONG_MODELS = (
+    ("any-of evaluated as all-of", AnyOfAsAllOf),
+    ("all-of evaluated as an exclude", AllOfAsExclude),
+    ("include_any & 0xFF", AnyOfLowByte),
+    ("exclude_all & 0xFF", AllOfLowByte),
+    ("MAPQ of element j taken from j + 1", MapqOneOn),
+    ("a segment starting one element late", SegmentOneLate),
+    ("--rf / -G ignored where the reduction leaves a pair", RfIgnoredBesideAPair),
+    ("the per-flag count without its valid-bits mask", ValidBitsDropped),
+)
+
+
+def changed_by(cases, refs, model):
+    """indices of the cases whose expected images differ under the model"""
+    changed = []
+    for c, r in zip(cases, refs):
+        wrong = dp.expected_images(c, dp.reference(c, model()))
+        if any(not np.array_equal(a, b) for a, b in zip(dp.expected_images(c, r), wrong)):
+            changed.append(c["index"])
+    return changed
+
+
+@pytest.mark.parametrize("name,model", RF_SEGMENTED_WRONG_MODELS, ids=[w[0] for w in RF_SEGMENTED_WRONG_MODELS])
+def test_rf_segmented_plan_notices_a_wrong_model(planned_rf_segmented, name, model):
+    """the expected images of at least 5 cases of the default plan differ under each one-line variation of the reference"""
+    cases, refs, _ = planned_rf_segmented
+    changed = changed_by(cases[:DEFAULT_ITERS], refs, model)
+    assert len(changed) >= 5, (name, changed)
+
+
+def test_rf_segmented_plan_notices_a_zero_filled_position_that_counts(planned_rf_segmented):
+    """the valid-bits mask dropped for the positions outside [0, n) alone: only the dealt cases can tell, and at least 5 do"""
+    cases, refs, _ = planned_rf_segmented
+    cases = cases[:DEFAULT_ITERS]
+    changed = changed_by(cases, refs, ValidBitsDroppedOutsideTheArray)
+    assert len(changed) >= 5, changed
+    assert all(cases[i]["hazard"] is not None for i in changed), changed
+    for form in dp.FORMS:
+        assert any(cases[i]["form"] == form for i in changed), (form, changed)

@@ -1,12 +1,13 @@
-"""GPU: the seventeen kernels derived from K1's step tree under a randomized sweep, one after another over the engine's staging
+"""GPU: the eighteen kernels derived from K1's step tree under a randomized sweep, one after another over the engine's staging
 slots, and from several threads at once -- the eight of the first family (where, filter, segments, segments_filter, wide,
-wide_filter, wide_segments, wide_segments_filter) and the nine derived later (derived_plan.LATER_KINDS: the masked kinds and the
-two of the whole predicate, --rf / -G), each family in tests of its own.  Cases, reference and the poisoned input / output images
+wide_filter, wide_segments, wide_segments_filter), the nine derived later (derived_plan.LATER_KINDS: the masked kinds and the
+two of the whole predicate, --rf / -G) and the segmented unit of the whole predicate (derived_plan.RF_SEGMENTED_KINDS), each
+family in tests of its own.  Cases, reference and the poisoned input / output images
 come from tests/derived_plan.py (checked on the CPU by tests/test_derived_plan_host.py); every comparison is exact, and every
 call is one the header documents as legal.
 
-To run one case of a sweep again: ``derived_plan.plan(SEED, index + 1)[index]``, or ``plan_later(LATER_SEED, index + 1)[index]``
--- a failure names the index and the drawn parameters."""
+To run one case of a sweep again: ``derived_plan.plan(SEED, index + 1)[index]``, ``plan_later(LATER_SEED, index + 1)[index]`` or
+``plan_rf_segmented(RF_SEGMENTED_SEED, index + 1)[index]`` -- a failure names the index and the drawn parameters."""
 import ctypes
 import os
 import sys
@@ -22,6 +23,7 @@ pytestmark = pytest.mark.gpu
 
 SEED = 20261019     # tests/test_derived_plan_host.py checks this plan's coverage
 LATER_SEED = 20261021   # ... and that of dp.plan_later(LATER_SEED, ...), the nine later units
+RF_SEGMENTED_SEED = 20261024    # ... and that of dp.plan_rf_segmented(RF_SEGMENTED_SEED, ...), fixed there before any GPU run
 
 # arguments of every entry, by name: A array, N n, W elem_bytes, S / SO / SB selection, its offset and encoding, R / X / Q / MQ
 # require, exclude, MAPQ column, min_mapq, O / NS offsets and nseg, OUT / SEL / HIGH outputs, Z a zero (the launchers' `base`)
@@ -33,7 +35,7 @@ PUBLIC = {"where": "A N S SO SB OUT SEL MODE", "filter": "A N R X Q MQ OUT SEL M
           "wide_segments_where": "A N W O NS S SO SB OUT SEL HIGH MODE", "filter_where": "A N R X Q MQ S SO SB OUT SEL MODE",
           "segments_filter_where": "A N O NS R X Q MQ S SO SB OUT SEL MODE", "wide_filter_where": "A N W R X Q MQ S SO SB OUT SEL HIGH MODE",
           "wide_segments_filter_where": "A N W O NS R X Q MQ S SO SB OUT SEL HIGH MODE", "filter_rf": "A N R X IA XA Q MQ OUT SEL MODE",
-          "wide_filter_rf": "A N W R X IA XA Q MQ OUT SEL HIGH MODE"}
+          "wide_filter_rf": "A N W R X IA XA Q MQ OUT SEL HIGH MODE", "segments_filter_rf": "A N O NS R X IA XA Q MQ OUT SEL MODE"}
 LAUNCHER = {"where": ("fsk_launch_where", "A N S SO SB OUT SEL MODE GRID"), "filter": ("fsk_launch_filter", "A N R X Q MQ OUT SEL MODE GRID"),
             "segments": ("fsk_launch_segments", "A Z N O NS OUT MODE GRID"),
             "segments_filter": ("fsk_launch_segments_filter", "A Q Z N O NS R X MQ OUT SEL MODE GRID"),
@@ -48,12 +50,14 @@ LAUNCHER = {"where": ("fsk_launch_where", "A N S SO SB OUT SEL MODE GRID"), "fil
             "wide_filter_where": ("fsk_launch_wide_filter_where", "A N W R X Q MQ S SO SB OUT SEL HIGH MODE GRID"),
             "wide_segments_filter_where": ("fsk_launch_segments_wide_masked_filter", "A W Q S SO SB Z N O NS R X MQ OUT SEL HIGH MODE GRID"),
             "filter_rf": ("fsk_launch_filter_rf", "A N R X IA XA Q MQ OUT SEL MODE GRID"),
-            "wide_filter_rf": ("fsk_launch_wide_filter_rf", "A N W R X IA XA Q MQ OUT SEL HIGH MODE GRID")}
+            "wide_filter_rf": ("fsk_launch_wide_filter_rf", "A N W R X IA XA Q MQ OUT SEL HIGH MODE GRID"),
+            "segments_filter_rf": ("fsk_launch_segments_filter_rf", "A Q Z N O NS R X IA XA MQ OUT SEL MODE GRID")}
 STEM = {"where": "u16_where", "filter": "u16_filter", "segments": "u16_segments", "segments_filter": "u16_segments_filter", "wide": "wide",
         "wide_filter": "wide_filter", "wide_segments": "wide_segments", "wide_segments_filter": "wide_segments_filter",
         "segments_where": "u16_segments_where", "wide_where": "wide_where", "wide_segments_where": "wide_segments_where",
         "filter_where": "u16_filter_where", "segments_filter_where": "u16_segments_filter_where", "wide_filter_where": "wide_filter_where",
-        "wide_segments_filter_where": "wide_segments_filter_where", "filter_rf": "u16_filter_rf", "wide_filter_rf": "wide_filter_rf"}
+        "wide_segments_filter_where": "wide_segments_filter_where", "filter_rf": "u16_filter_rf", "wide_filter_rf": "wide_filter_rf",
+        "segments_filter_rf": "u16_segments_filter_rf"}
 HOST = {"where": "FLAGSTATS_hip_u16_x64_where", "filter": "FLAGSTATS_hip_u16_x64_filter", "segments": "FLAGSTATS_hip_u16_x64_segments",
         "segments_filter": "FLAGSTATS_hip_u16_x64_segments_filter", "wide": "FLAGSTATS_hip_wide_x64", "wide_filter": "FLAGSTATS_hip_wide_x64_filter",
         "wide_segments": "FLAGSTATS_hip_wide_x64_segments", "wide_segments_filter": "FLAGSTATS_hip_wide_x64_segments_filter",
@@ -61,8 +65,9 @@ HOST = {"where": "FLAGSTATS_hip_u16_x64_where", "filter": "FLAGSTATS_hip_u16_x64
         "wide_segments_where": "FLAGSTATS_hip_wide_x64_segments_where", "filter_where": "FLAGSTATS_hip_u16_x64_filter_where",
         "segments_filter_where": "FLAGSTATS_hip_u16_x64_segments_filter_where", "wide_filter_where": "FLAGSTATS_hip_wide_x64_filter_where",
         "wide_segments_filter_where": "FLAGSTATS_hip_wide_x64_segments_filter_where", "filter_rf": "FLAGSTATS_hip_u16_x64_filter_rf",
-        "wide_filter_rf": "FLAGSTATS_hip_wide_x64_filter_rf"}
-assert set(PUBLIC) == set(LAUNCHER) == set(STEM) == set(HOST) == {dp.family(k) for k in dp.KINDS} | set(dp.LATER_KINDS)
+        "wide_filter_rf": "FLAGSTATS_hip_wide_x64_filter_rf", "segments_filter_rf": "FLAGSTATS_hip_u16_x64_segments_filter_rf"}
+assert set(PUBLIC) == set(LAUNCHER) == set(STEM) == set(HOST) == ({dp.family(k) for k in dp.KINDS} | set(dp.LATER_KINDS)
+                                                                    | set(dp.RF_SEGMENTED_KINDS)) and len(PUBLIC) == 18
 
 
 def entry_name(case):
@@ -234,6 +239,11 @@ def test_random_cases_every_later_family(lib, oracle_mod):
     sweep(lib, dp.plan_later(LATER_SEED, int(os.environ.get("FLAGSTATS_FUZZ_ITERS_DERIVED", "240"))))
 
 
+def test_random_cases_every_rf_segmented_family(lib, oracle_mod):
+    """the segmented unit of the whole predicate (dp.RF_SEGMENTED_KINDS), the dealt zero-fill cases among them, under the same knob"""
+    sweep(lib, dp.plan_rf_segmented(RF_SEGMENTED_SEED, int(os.environ.get("FLAGSTATS_FUZZ_ITERS_DERIVED", "240"))))
+
+
 def sweep(hip, cases):
     import torch
     assert dp.skip_reasons(cases) == []
@@ -344,9 +354,10 @@ def walk_the_slots(hip, oracle_mod, rng, derived, refs):
 
 
 def later_round(rng):
-    """the eleven derived calls of one round of the later kinds, in order: the host forms of the nine later kinds with `filter`
-    and `wide` of the old family in between.  With a K1 call at positions 0 and 12, positions 4 and 8 (calls 3 and 7 here) never
-    meet chunk_flags 8 and are the large ones."""
+    """the thirteen derived calls of one round of the later kinds, in order: the host forms of the nine later kinds with `filter`
+    and `wide` of the old family in between, then two of the segmented unit of the whole predicate.  With a K1 call at positions
+    0 and 14, positions 4, 8 and 12 (calls 3, 7 and 11 here) never meet chunk_flags 8: the first two are the large ones, the
+    third is the call that can pass nothing and moves nothing."""
     u16 = lambda n: rng.randint(0, 65536, n).astype(np.uint16)  # noqa: E731
     q = lambda n: rng.randint(0, 256, n).astype(np.uint8)  # noqa: E731
     half = lambda n: rng.randint(0, 2, n).astype(bool)  # noqa: E731
@@ -383,6 +394,13 @@ def later_round(rng):
     n = 2100
     calls.append(dp.fixed_case("filter_where", F, u16(n), 2, require=1, exclude=0x904, mapq=q(n), min_mapq=30, mask=half(n), sel_bits=1,
                                sel_offset=9, mapq_align=11, sel_align=13, selected_at="apart"))
+    n = 2801      # every -G bit is required: nothing can pass, nothing is read, the store form still zeroes
+    calls.append(dp.fixed_case("segments_filter_rf", F, u16(n), 1, require=0x41, exclude_all=0x41, mapq=q(n), min_mapq=5,
+                               offsets=cuts(n, 3, 12), mapq_align=3))
+    n = 3333      # --rf 0x50 -G 0xC beside -f 1 -F 0x900 -q 30: both tests are left; the MAPQ slice rides behind a chunk's flags
+    calls.append(dp.fixed_case("segments_filter_rf", F, u16(n) & np.uint16(0x0FFF), 2, require=1, exclude=0x900, include_any=0x50,
+                               exclude_all=0xC, mapq=q(n), min_mapq=30, offsets=cuts(n, 5, 20), phase=6, mapq_align=7,
+                               selected_at="apart"))
     return calls
 
 
@@ -390,11 +408,21 @@ def test_later_entry_kinds_interleaved_over_the_staging_slots(lib, oracle_mod):
     rng = np.random.RandomState(78)
     derived = later_round(rng)
     refs = [dp.reference(c) for c in derived]
-    assert {c["kind"] for c in derived} == set(dp.LATER_KINDS) | {"filter", "wide"}
-    for c, r in zip(derived, refs):
-        empty = c["kind"] == "wide_filter_rf"
+    assert {c["kind"] for c in derived} == set(dp.LATER_KINDS) | set(dp.RF_SEGMENTED_KINDS) | {"filter", "wide"}
+    empties = [i for i, c in enumerate(derived) if not dp.Definition().reads(c)]
+    assert [derived[i]["kind"] for i in empties] == ["wide_filter_rf", "segments_filter_rf"]
+    for i, (c, r) in enumerate(zip(derived, refs)):
+        empty = i in empties
         assert 2000 <= c["n"] <= 200_000 and r["selected"].any() != empty, c["kind"]
         assert c["kind"] not in dp.WIDE + dp.LATER_WIDE or r["high"].any() != empty, c["kind"]
+    # positions 4, 8 and 12 of a round never meet chunk_flags 8: the two large calls and the empty segmented one
+    assert len(derived) == 13 and [i for i, c in enumerate(derived) if c["n"] > 5000] == [3, 7] and empties[1] == 11
+    reduced = (ctypes.c_uint32 * 4)()
+    nothing, residue = derived[11], derived[12]          # the segmented unit of the whole predicate: an empty call, a residue of both
+    assert lib.fsk_filter_rf_reduce(nothing["require"], nothing["exclude"], nothing["include_any"], nothing["exclude_all"], reduced) == 0
+    assert lib.fsk_filter_rf_reduce(residue["require"], residue["exclude"], residue["include_any"], residue["exclude_all"], reduced) == 2
+    assert reduced[2] and reduced[3] and residue["min_mapq"] > 0 and residue["mapq_align"] & 1 and 2000 <= residue["n"] <= 5000
+    assert (refs[12]["selected"] > 0).sum() >= 10 and refs[12]["selected"].sum() < refs[12]["length"].sum() // 4
     rf = {c["kind"]: c for c in derived if c["kind"] in dp.RF}
     assert dp.Definition().reads(rf["filter_rf"]) and not dp.Definition().reads(rf["wide_filter_rf"])       # one counts, one is empty
     both = rf["filter_rf"]                               # residue-both: no bit of --rf or -G is decided by -f / -F
@@ -514,17 +542,21 @@ def test_concurrent_callers_of_the_later_kinds(lib, oracle_mod):
         return [(Call(c), dp.expected_images(c, dp.reference(c))) for c in cases]
 
     # A: host forms, several chunks each at chunk_flags 8192
-    na = (200_000, 90_001, 61_003)
+    na = (200_000, 90_001, 61_003, 70_007)
     thread_a = checked([
         dp.fixed_case("filter_where", "host", u16(na[0]), 1, require=1, exclude=0x904, mapq=q(na[0]), min_mapq=30, mask=half(na[0]), sel_bits=1,
                       sel_offset=3, phase=6, mapq_align=3, sel_align=5),
         dp.fixed_case("wide_filter_where", "host", widened(u16(na[1]), np.int64, rng, 700), 3, exclude=0x104, mapq=q(na[1]), min_mapq=9,
                       mask=half(na[1]), sel_bits=8, sel_offset=1, phase=8, mapq_align=2, sel_align=7),
         dp.fixed_case("filter_rf", "host", u16(na[2]), 0, require=1, exclude=0x900, include_any=0x50, exclude_all=0xC, mapq=q(na[2]),
-                      min_mapq=30, mapq_align=1)])
-    # B: the _sync forms of the four segmented masked kinds
-    nb = (150_000, 70_001, 40_003, 33_333)
+                      min_mapq=30, mapq_align=1),
+        dp.fixed_case("segments_filter_rf", "host", u16(na[3]), 2, exclude=0x904, include_any=0x210, exclude_all=0x480, mapq=q(na[3]),
+                      min_mapq=20, offsets=cuts(na[3], 3, 25), phase=10, mapq_align=9)])
+    # B: the _sync forms of the four segmented masked kinds and of the segmented unit of the whole predicate
+    nb = (150_000, 70_001, 40_003, 33_333, 55_555)
     thread_b = checked([
+        dp.fixed_case("segments_filter_rf", "sync", u16(nb[4]), 1, require=1, exclude=0x804, include_any=0x110, exclude_all=0x2200,
+                      mapq=q(nb[4]), min_mapq=10, offsets=cuts(nb[4], 2, 30), phase=4, mapq_align=5, selected_at="apart"),
         dp.fixed_case("segments_where", "sync", u16(nb[0]), 3, mask=half(nb[0]), sel_bits=1, sel_offset=7, offsets=cuts(nb[0], 5, 40)),
         dp.fixed_case("segments_filter_where", "sync", u16(nb[1]), 0, require=1, exclude=0x900, mapq=q(nb[1]), min_mapq=40, mask=half(nb[1]),
                       sel_bits=8, offsets=cuts(nb[1], 0, 7), sel_align=3),
@@ -544,6 +576,10 @@ def test_concurrent_callers_of_the_later_kinds(lib, oracle_mod):
                                mask=half(n1), sel_bits=bits[1], sel_offset=6, phase=8, mapq_align=2),
                  dp.fixed_case("wide_filter_rf", "device", widened(u16(n2), np.uint32, rng, 700), 2, exclude=0x800, include_any=0x1C1,
                                exclude_all=0x30, mapq=q(n2), min_mapq=20, mapq_align=5)]
+        if not adders:      # one segment, so that its row and its count += into the shared words like a flat call's
+            n3 = 66_001
+            cases.append(dp.fixed_case("segments_filter_rf", "device", u16(n3), 2, exclude=0x904, include_any=0x50, mapq=q(n3), min_mapq=15,
+                                       offsets=[9, n3 - 5], phase=2, mapq_align=3))
         assert all(2000 <= c["n"] <= 200_000 for c in cases)
         adders.append([(Call(c), dp.reference(c)) for c in cases])
     want_shared = shared_sum(adders)

@@ -1,5 +1,5 @@
-"""GPU: the seventeen kernels derived from K1 -- flat and segmented, on uint16, int32 and int64 columns, under samtools' filter, a
-selection, or both, and the two flat units of the whole predicate (--rf / -G) -- past 2^31 and 2^32 elements and bytes, against
+"""GPU: the eighteen kernels derived from K1 -- flat and segmented, on uint16, int32 and int64 columns, under samtools' filter, a
+selection, or both, and the three units of the whole predicate (--rf / -G) -- past 2^31 and 2^32 elements and bytes, against
 tests/periodic_oracle.py: an exact reference that needs no host copy of the column.  Every comparison is exact.
 
 The columns: 2^32 + 3 * 2^20 + 5 uint16 or int32 elements (8 and 16 GiB), 2^31 + 3 * 2^20 + 5 int64 elements (16 GiB), a MAPQ
@@ -29,8 +29,9 @@ TORCH = {2: "int16", 4: "int32", 8: "int64"}
 # (wide, segmented, filtered, masked): the fifteen derived units -- all sixteen combinations but K1 itself
 FLAT = [(w, False, f, m) for w in (False, True) for f in (False, True) for m in (False, True) if w or f or m]
 SEGMENTED = [(w, True, f, m) for w in (False, True) for f in (False, True) for m in (False, True)]
-RF = [(False, False, True, False, "rf"), (True, False, True, False, "rf")]     # u16_filter_rf, wide_filter_rf: flat, whole columns
-assert len(FLAT) + len(SEGMENTED) == 15 and len(FLAT) + len(SEGMENTED) + len(RF) == 17
+# u16_filter_rf and wide_filter_rf, flat, on whole columns; u16_segments_filter_rf, on uint16 columns only
+RF = [(False, False, True, False, "rf"), (True, False, True, False, "rf"), po.RF_SEGMENTED_UNIT]
+assert len(FLAT) + len(SEGMENTED) == 15 and len(FLAT) + len(SEGMENTED) + len(RF) == 18 and RF[2] == (False, True, True, False, "rf")
 
 
 def stem(unit):
@@ -388,6 +389,13 @@ def test_python_layer_on_the_resident_slab(hip, shared, slab):
     assert rp["min_mapq"] == 30 and rf_call["layout"] == "whole"
     if W == 2:
         runs.append((RF[0], rf_call, lambda: filter_rf.count_torch_filter_rf(t, **rp, **common)))
+        from libflagstats_amd import segments_filter_rf
+        rs_call = [c for c in po.rf_segments_slab_calls() if c["case"] == "rf-one-b1"][0]      # [7, n - 3) under -F 0x4 --rf 0x60 -G 0x11 -q 30
+        rsp = dict(require=rs_call["pred"][0], exclude=rs_call["pred"][1], include_any=rs_call["rf"][0], exclude_all=rs_call["rf"][1],
+                   mapq=mapq, min_mapq=rs_call["pred"][2])
+        rs_offsets = torch.from_numpy(rs_call["offsets"]).cuda()
+        assert rsp["min_mapq"] == 30 and rs_call["layout"] == "one"
+        runs.append((RF[2], rs_call, lambda: segments_filter_rf.count_segments_torch_filter_rf(t, rs_offsets, **rsp, **common)))
     else:
         runs.append((RF[1], rf_call, lambda: wide_filter_rf.count_torch_ints_filter_rf(t, **rp, **common)))
     for unit, call, run in runs:
@@ -403,11 +411,15 @@ def test_python_layer_on_the_resident_slab(hip, shared, slab):
 
 # ------------------------------------------------------------------ 5: one workgroup past 2^32
 def launch(hip, name, *argv):
+    """one direct launch, synchronized on both sides; its wall time is printed (``pytest -s`` shows it), never asserted"""
+    import time
     import torch
     torch.cuda.synchronize()
+    t0 = time.perf_counter()
     rc = getattr(hip, name)(*argv, None)
     assert rc == 0, (name, rc)
     torch.cuda.synchronize()
+    print("%s at grid %d: %.1f ms" % (name, argv[-1], 1e3 * (time.perf_counter() - t0)))
 
 
 @pytest.mark.parametrize("slab", [2, 4], indirect=True)
@@ -492,6 +504,79 @@ def test_rf_units_one_workgroup_past_2_pow_32(hip, shared, slab):
     assert W == 2 or got[33] == want.high_read[0], (hex(int(got[33])), hex(int(want.high_read[0])))
 
 
+# ------------------------------------------------------------------ 8: the segmented unit of the whole predicate (uint16 only)
+@pytest.mark.parametrize("slab", [2], indirect=True)
+@pytest.mark.parametrize("layout", ["blocks", "one", "around"])
+def test_rf_segmented_unit_on_layouts(hip, shared, slab, layout):
+    """u16_segments_filter_rf on the three layouts, without and with -q 30, in the device form (store and +=) and the _sync form:
+    `blocks` under po.RF_PREDICATES; `one` and `around` under po.RF_BOUNDS_PREDICATES, which an element in front of the first
+    segment and one behind the last pass (tests/test_periodic_oracle_host.py), so that offsets[0] and offsets[nseg] are tested"""
+    calls = [c for c in po.rf_segments_slab_calls() if c["layout"] == layout]
+    assert [c["pred"][2] for c in calls] == [0, 30] and all(np.array_equal(c["offsets"], po.layouts(2, slab.n)[layout]) for c in calls)
+    for call in calls:
+        want = slab.want(call, True, False)
+        length = np.diff(call["offsets"]).astype(np.uint64)
+        assert (want.selected > 0).sum() > length.size // 2 and (want.selected <= length).all() and want.selected.sum() < length.sum() // 2
+        for form in ("device", "sync"):
+            for store in (True, False):
+                assert run_unit(hip, shared, slab, RF[2], form, store, call) is None
+
+
+@pytest.mark.parametrize("slab", [2], indirect=True)
+def test_rf_segmented_unit_window_past_the_mark(hip, shared, slab):
+    """the window that begins past the mark, 2 bytes past a 16-byte boundary, as the whole array of both segmented forms"""
+    calls = [c for c in po.rf_segments_slab_calls() if c["local"]]
+    assert len(calls) == 2
+    for call in calls:
+        first = int(call["offsets"][0])
+        assert first > po.MARK[2] and (slab.base + first * 2) % 16 == 2
+        assert 0 < int(slab.want(call, True, False).selected[0]) < int(call["offsets"][1]) - first
+        for form in ("device", "sync"):
+            assert run_unit(hip, shared, slab, RF[2], form, True, call, first=first) is None
+
+
+@pytest.mark.parametrize("slab", [2], indirect=True)
+def test_rf_segmented_unit_needles_one_at_a_time(hip, shared, slab):
+    """the `around` layout under the residue predicate with -q 60 that one needle alone passes, for every needle inside it:
+    exactly one of the 3,002 segments has selected == 1 and the rows of that element, every other row is zero"""
+    col = slab.col
+    around = po.layouts(2, slab.n)["around"]
+    calls = po.rf_needle_calls(col, around)
+    assert len(calls) == len(col.needles) - 1 and po.MARK[2] + 1 in dict(calls)
+    for k, call in calls:
+        want = slab.want(call, True, False)
+        seg = int(np.searchsorted(around, k, side="right")) - 1
+        assert int(want.selected[seg]) == 1 and int(want.selected.sum()) == 1 and not np.delete(want.rows, seg, axis=0).any()
+        assert np.array_equal(want.rows[seg], col.expect([k, k + 1], superset=True).rows[0])
+        assert run_unit(hip, shared, slab, RF[2], "device", True, call) is None
+
+
+@pytest.mark.parametrize("slab", [2], indirect=True)
+def test_rf_segmented_unit_one_workgroup_past_2_pow_32(hip, shared, slab):
+    """grid 1 through fsk_launch_segments_filter_rf: one segment over the whole slab under po.RF_DENSE and -q 1, the MAPQ of every
+    other needle 0 -- ``selected[0]`` and slot 9 of the one workgroup pass 2^32"""
+    import torch
+    n = slab.n
+    col = po.column(2, dense=True)
+    quiet = torch.tensor([p for p, i in po.needle_positions(n).items() if i % 2 == 1], dtype=torch.int64, device="cuda") + PAD
+    require, exclude, include_any, exclude_all, min_mapq = po.RF_DENSE
+    whole = np.array([0, n], dtype=np.int64)
+    want = col.expect(whole, require, exclude, min_mapq, superset=True, include_any=include_any, exclude_all=exclude_all)
+    assert int(want.selected[0]) == 4_298_113_024 > 1 << 32 and int(want.rows[0, 9]) > 1 << 32 and int(want.selected[0]) < n
+    offsets = torch.from_numpy(whole).cuda()
+    rows = torch.full((1, 32), GARBAGE, dtype=torch.int64, device="cuda")
+    selected = torch.full((1,), GARBAGE, dtype=torch.int64, device="cuda")
+    try:
+        shared.mapq[quiet] = 0
+        launch(hip, "fsk_launch_segments_filter_rf", slab.base, shared.mapq.data_ptr() + PAD, 0, n, offsets.data_ptr(), 1, require, exclude,
+               include_any, exclude_all, min_mapq, rows.data_ptr(), selected.data_ptr(), STORE | SUPERSET, 1)
+        got, got_selected = rows.cpu().numpy().view(np.uint64), int(selected.item())
+    finally:
+        shared.mapq[quiet] = po.NEEDLE_MAPQ
+        torch.cuda.synchronize()
+    assert np.array_equal(got, want.rows) and got_selected == int(want.selected[0]), (got.tolist(), want.rows.tolist(), got_selected)
+
+
 # ------------------------------------------------------------------ 6: host forms, default chunk_flags
 def host_bitmap(col, so):
     """the packed selection of a host column whose element j is bit so + j (so < 8): ones in the unused bits at either end"""
@@ -555,6 +640,24 @@ def test_host_form_segments_past_2_pow_32_flags(hip, host_flags):
     rows, selected = np.full((nseg, 32), GARBAGE, dtype=np.uint64), np.full(nseg, GARBAGE, dtype=np.uint64)
     rc = hip.FLAGSTATS_hip_u16_x64_segments_filter_where(values.ctypes.data, col.n, offsets.ctypes.data, nseg, 0, 0, mapq.ctypes.data, 30,
                                                          bitmap.ctypes.data, so, 1, rows.ctypes.data, selected.ctypes.data, STORE | SUPERSET)
+    assert rc == 0, hip.FLAGSTATS_hip_last_error()
+    assert np.array_equal(rows, want.rows) and np.array_equal(selected, want.selected)
+
+
+def test_host_form_rf_segments_past_2_pow_32_flags(hip, host_flags):
+    """FLAGSTATS_hip_u16_x64_segments_filter_rf on the host column: -F 0x4 --rf 0x60 -G 0x11 -q 30 over po.HOST_OFFSETS[2], which
+    leave elements that pass in front of the first segment and behind the last; a chunk's MAPQ slice rides behind its flags and
+    the launcher's `base` passes 2^32"""
+    col, _, values, mapq, _ = host_flags
+    offsets = np.array(po.HOST_OFFSETS[2], dtype=np.uint64)
+    require, exclude, include_any, exclude_all, min_mapq = po.RF_BOUNDS_PREDICATES[1]
+    want = col.expect(offsets.astype(np.int64), require, exclude, min_mapq, superset=True, include_any=include_any, exclude_all=exclude_all)
+    nseg = offsets.size - 1
+    assert min_mapq == 30 and (want.selected > 0).all() and (want.selected < np.diff(offsets)).all()
+    rows, selected = np.full((nseg, 32), GARBAGE, dtype=np.uint64), np.full(nseg, GARBAGE, dtype=np.uint64)
+    rc = hip.FLAGSTATS_hip_u16_x64_segments_filter_rf(values.ctypes.data, col.n, offsets.ctypes.data, nseg, require, exclude, include_any,
+                                                      exclude_all, mapq.ctypes.data, min_mapq, rows.ctypes.data, selected.ctypes.data,
+                                                      STORE | SUPERSET)
     assert rc == 0, hip.FLAGSTATS_hip_last_error()
     assert np.array_equal(rows, want.rows) and np.array_equal(selected, want.selected)
 

@@ -7,7 +7,10 @@
     needed to know it.
 (c) The same two for the units of the whole predicate (--rf / -G): the oracle with include_any / exclude_all against
     filter_rf_oracle and wide_filter_rf_oracle, what the chosen predicates do to the needles and to the library's dispatch, and
-    the wrapped models against every rf call of the GPU module."""
+    the wrapped models against every rf call of the GPU module.
+(d) And for the segmented unit of the whole predicate: the oracle against segments_filter_rf_oracle, that the predicates of the
+    `one` and `around` layouts test the segment bounds, what the one-needle calls of `around` must report, and the wrapped
+    models -- the segment offsets among them -- against every call of that unit."""
 import os
 import sys
 
@@ -20,6 +23,7 @@ import filter_rf_oracle  # noqa: E402
 import filter_where_oracle  # noqa: E402
 import periodic_oracle as po  # noqa: E402
 import segments_filter_oracle  # noqa: E402
+import segments_filter_rf_oracle  # noqa: E402
 import segments_filter_where_oracle  # noqa: E402
 import segments_oracle  # noqa: E402
 import segments_where_oracle  # noqa: E402
@@ -284,3 +288,132 @@ def test_wrapped_models_fail_the_rf_calls(W):
     if W == 2:
         host = po.column(2, n=po.HOST_N)
         assert_detected(host.detects(np.array([0, host.n]), superset=True, **rf_kw(po.RF_PREDICATES[1])), ("array", "mapq"), "host")
+
+
+# ------------------------------------------------------------------ the segmented unit of the whole predicate
+def rf_segmented_want(v, o, q, pred, superset):
+    kw = rf_kw(pred)
+    return segments_filter_rf_oracle.want(v, o, kw["require"], kw["exclude"], kw["include_any"], kw["exclude_all"],
+                                          q if kw["min_mapq"] else None, kw["min_mapq"], superset)
+
+
+def test_oracle_matches_the_rf_segmented_brute_force_oracle():
+    """``expect`` with include_any / exclude_all over segments against segments_filter_rf_oracle: a random column of two million
+    elements under every kind of predicate of the GPU tests, then materialized windows of the slab's own column -- its first and
+    last elements and those around 2^32 -- under the `around` layout"""
+    rng = np.random.RandomState(302)
+    n = 2_000_005
+    col = random_column(2, rng, n)
+    v, _, q = col.materialize(0, n)
+    preds = po.RF_PREDICATES + po.RF_BOUNDS_PREDICATES + (po.RF_DENSE, po.needle_rf_predicate(po.NEEDLE_FLAGS[0]),
+                                                          po.needle_rf_predicate(po.NEEDLE_FLAGS[3]), (0, 0x30, 0x30, 0, 0), (0x3, 0, 0, 0x3, 20))
+    for trial, pred in enumerate(preds):
+        o, superset = random_offsets(col, rng), bool(trial % 2)
+        got = col.expect(o, superset=superset, **rf_kw(pred))
+        rows, selected = rf_segmented_want(v, o, q, pred, superset)
+        assert np.array_equal(got.rows, rows) and np.array_equal(got.selected, selected), pred
+        # the one-needle predicates pass what the random needles' MAPQ lets them; the last two pass nothing
+        assert selected.any() if trial < 5 else not selected.any() or trial < 7, (pred, selected)
+    slab = po.column(2)
+    around = po.layouts(2, slab.n)["around"]
+    mark = po.MARK[2]
+    preds = po.RF_PREDICATES + po.RF_BOUNDS_PREDICATES + (po.needle_rf_predicate(slab.needles[mark + 1][0]),)
+    for b, e in ((0, 6000), (mark - 5000, mark + 5000), (slab.n - 6000, slab.n)):
+        o = np.unique(np.clip(around, b, e))
+        assert o.size >= 2 and (o.size > 5 or not b < mark < e)       # several short segments cross the mark
+        v, _, q = slab.materialize(b, e)
+        for pred in preds:
+            got = slab.expect(o, superset=True, **rf_kw(pred))
+            rows, selected = rf_segmented_want(v, o - b, q, pred, True)
+            assert np.array_equal(got.rows, rows) and np.array_equal(got.selected, selected), (b, e, pred)
+
+
+def test_rf_bounds_predicates_test_the_segment_bounds():
+    """the condition that a call tests offsets[0] and offsets[nseg]: an element in front of the first segment and one behind the
+    last would count.  RF_BOUNDS_PREDICATES meet it on `one` and `around` (but for the three elements in front of `around` under
+    -q 30, whose MAPQ is below 30), RF_PREDICATES meet it nowhere; every one of them leaves both tests to the kernel."""
+    import ctypes
+    from libflagstats_amd import _lib
+    reduce_ = _lib.lib().fsk_filter_rf_reduce
+    out = (ctypes.c_uint32 * 4)()
+    for pred in po.RF_BOUNDS_PREDICATES + po.RF_PREDICATES + (po.RF_DENSE,):
+        assert reduce_(*pred[:4], out) == 2 and out[2] and out[3], pred
+    assert po.RF_BOUNDS_PREDICATES[0][4] == 0 and po.RF_BOUNDS_PREDICATES[1] == po.RF_BOUNDS_PREDICATES[0][:4] + (30,)
+    col = po.column(2)
+    lay = po.layouts(2, col.n)
+
+    def outside(column, o, pred):
+        head = column.expect([0, int(o[0])], **rf_kw(pred)).selected[0]
+        tail = column.expect([int(o[-1]), column.n], **rf_kw(pred)).selected[0]
+        return int(head), int(tail)
+
+    for name in ("one", "around"):
+        o = lay[name]
+        assert 0 < o[0] and o[-1] < col.n
+        for pred in po.RF_BOUNDS_PREDICATES:
+            head, tail = outside(col, o, pred)
+            assert tail >= 1, (name, pred)
+            if name == "around" and pred[4] == 30:
+                assert head == 0 and (col.materialize(0, int(o[0]))[2] < 30).all()
+            else:
+                assert head >= 1, (name, pred)
+        for pred in po.RF_PREDICATES:
+            assert outside(col, o, pred) == (0, 0), (name, pred)
+    host = po.column(2, n=po.HOST_N)
+    head, tail = outside(host, np.array(po.HOST_OFFSETS[2]), po.RF_BOUNDS_PREDICATES[1])
+    assert head >= 1 and tail >= 1
+
+
+def test_rf_needle_calls_name_one_segment_of_the_around_layout():
+    """every needle inside the `around` layout under its own predicate: one segment with selected == 1 and the rows of that
+    element alone, every other row zero -- the needle at 2^32 + 1 among them, in one of the short segments that cross the mark"""
+    col = po.column(2)
+    around = po.layouts(2, col.n)["around"]
+    calls = po.rf_needle_calls(col, around)
+    assert [k for k, _ in calls] == sorted(k for k in col.needles if k != col.n - 1) and po.MARK[2] + 1 in dict(calls)
+    for k, call in calls:
+        want = col.expect(around, superset=True, **po.reduced(call, True, False))
+        seg = int(np.searchsorted(around, k, side="right")) - 1
+        assert want.selected[seg] == 1 and want.selected.sum() == 1
+        assert np.array_equal(want.rows[seg], col.expect([k, k + 1], superset=True).rows[0]) and want.rows[seg].any()
+        assert not np.delete(want.rows, seg, axis=0).any()
+    seg = int(np.searchsorted(around, po.MARK[2] + 1, side="right")) - 1
+    assert 0 < seg < around.size - 2 and around[seg + 1] - around[seg] <= 2000
+
+
+def detects_over_segments(col, offsets, **kw):
+    """``col.detects`` of a segmented call, with the models that move none of the call's own offsets taken out (``detects`` asks
+    whether a model moves an index between the first and the last offset; [7, n - 3) has no offset for "sext" to move)"""
+    found = col.detects(offsets, superset=True, **kw)
+    for model in po.MODELS:
+        if np.array_equal(po.map_indices(po.wrapped(model), offsets), np.asarray(offsets, dtype=np.int64)):
+            found[("offsets", model)] = None
+    return found
+
+
+def test_wrapped_models_fail_the_rf_segmented_calls():
+    """the GPU calls of u16_segments_filter_rf: the three layouts, the needles one at a time, one workgroup and the host form --
+    each of the three index models, in the array's byte offset, the MAPQ index and the segment offsets, would miss the asserted
+    values (a window is handed pointers to its first element and offsets relative to it: no index of it passes the mark)"""
+    col = po.column(2)
+    calls = po.rf_segments_slab_calls()
+    assert sorted(c["layout"] for c in calls) == sorted(2 * ["blocks", "one", "around", "window"])
+    for call in calls:
+        if call["local"]:
+            continue
+        kw = po.reduced(call, True, False)
+        whats = ("array", "offsets", "mapq") if kw["min_mapq"] else ("array", "offsets")
+        assert_detected(detects_over_segments(col, call["offsets"], **kw), whats, call["case"])
+    found = {}
+    for k, call in po.rf_needle_calls(col, po.layouts(2, col.n)["around"]):
+        for key, hit in detects_over_segments(col, call["offsets"], **po.reduced(call, True, False)).items():
+            found[key] = found.get(key) or hit
+    assert_detected(found, ("array", "offsets", "mapq"), "needles")
+    dense = po.column(2, dense=True)
+    whole = np.array([0, dense.n], dtype=np.int64)
+    truth = dense.expect(whole, superset=True, **rf_kw(po.RF_DENSE))
+    assert int(truth.selected[0]) == 4_298_113_024 and int(truth.rows[0, 9]) > 1 << 32
+    assert_detected(detects_over_segments(dense, whole, **rf_kw(po.RF_DENSE)), ("array", "offsets", "mapq"), "one workgroup")
+    host = po.column(2, n=po.HOST_N)
+    assert_detected(detects_over_segments(host, np.array(po.HOST_OFFSETS[2]), **rf_kw(po.RF_BOUNDS_PREDICATES[1])),
+                    ("array", "offsets", "mapq"), "host")
